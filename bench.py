@@ -10,13 +10,17 @@ gather -> sum-product -> normalize -> per-variable marginals) reading the
 column-major uint8 evidence resident in HBM and writing the [17, rows] fp64
 marginals to HBM.
 
-    python bench.py [--gpus N --steps K --warmup W --rows R]
+    python bench.py [--gpus N --steps K --warmup W --rows R] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, rows sharded: weak scaling)
 
-Prints ONE JSON line (rank 0) with the roofline of the dominant kernel
-(pgm_rows_jit, the plan-specialised kernel, for the C3 template; achieved = algorithmic bytes per launch / HIP-event launch time) and a
-CPU baseline (the numpy oracle's per-row predict_probability, single core,
-bounded sample) timed on this host.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the
+headline (value, ms_per_step) with the roofline its own dispatch timestamps give (pgm_rows_jit, the
+plan-specialised kernel, for the C3 template; achieved = algorithmic bytes per launch / GPU span per
+launch).  --dump-outputs DIR writes the last timed step's outputs as DIR/<name>.npy.  --full adds
+everything that takes runs of its own: the CPU baselines (the numpy oracle's per-row
+predict_probability on this host, one core and a worker pool), the parity check against the oracle,
+the dispatch floor, the single-launch and streamed rooflines, the DataFrame API rate and the c5 / c1 /
+c2 / c4 sub-objects.
 Other workloads for DESIGN.md numbers: --workload c2 (single munin query,
 greedy device contraction) and c4 (pathfinder batched BP calibration).
 """
@@ -41,6 +45,47 @@ METRIC = "evidence-batched marginal queries/sec on munin; achieved HBM GB/s vs p
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(args, arrays, rank=0):
+    """--dump-outputs DIR: what the timed path computed in its last timed step, DIR/<name>.npy each
+    (float32 / float64 kept, everything else as float64).  Past DUMP_MAX_BYTES in all, every array is cut
+    to a fixed seeded sample of its flattened entries (same entries every run).  Returns what was written,
+    for the result line."""
+    if not args.dump_outputs:
+        return None
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+              for k, a in ((k, np.asarray(a)) for k, a in arrays.items())}
+    total = sum(a.nbytes for a in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        sampled = False
+        if total > DUMP_MAX_BYTES:
+            keep = max(1, int(a.size * (DUMP_MAX_BYTES / total) * 0.99))
+            idx = np.sort(np.random.default_rng(20240).choice(a.size, keep, replace=False))
+            a, sampled = a.ravel()[idx], True
+        fname = f"{name}.npy" if rank == 0 else f"{name}_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, fname), a)
+        written[fname] = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": sampled}
+    return written
+
+
+def sorted_marginals(plan, marg):
+    """[n_acc, rows] marginals with the variables' row blocks in sorted-name order (the plan's own order
+    follows set iteration, which differs from process to process; a dump must not)."""
+    blocks = {v: marg[o:o + c] for v, o, c in zip(plan.variables, plan.acc_off, plan.cards)}
+    return np.concatenate([blocks[v] for v in sorted(blocks)], axis=0)
+
+
+def c3_last_step_arrays(plan, out):
+    """The fp64 marginals of one C3 batch as a caller of the fused row plan receives them."""
+    from pgmpy_amd.inference.batch import download
+
+    return {"marginals": sorted_marginals(plan, download(out["marg"]))}
 
 
 _BACKEND = "nccl"
@@ -611,13 +656,18 @@ def bench_c3(args, dist, rank, world):
         kern_ms = (t_end - t_start) * 1e3 / args.steps
     bpr = plan.algorithmic_bytes_per_row(marginals=True)
     achieved = bpr * rows / (kern_ms * 1e-3) / 1e9
-    floor_ms, single_ms = dispatch_floor_ms(plan, d_codes, rows, args, Launcher)
+    # the last timed step ran batch (_next - 1) % nb; read before anything below launches again
+    dumped = dump_outputs(args, c3_last_step_arrays(plan, outs[(launcher._next - 1) % nb]), rank) \
+        if args.dump_outputs else None
+    # everything from here to the result line that launches or computes again is --full only: the plain
+    # line is the timed window and what its own timestamps give
+    floor_ms, single_ms = dispatch_floor_ms(plan, d_codes, rows, args, Launcher) if args.full else (None, None)
     working_set = bpr * rows * nb
     stream = None
-    if args.launch == "direct" and working_set <= MALL_BYTES:
+    if args.full and args.launch == "direct" and working_set <= MALL_BYTES:
         stream = hbm_stream_roofline(plan, d_codes, rows, nb, args, err, launcher.qs)
     ring_roof = None
-    if not args.no_ring_roofline:
+    if args.full and not args.no_ring_roofline:
         try:
             ring_roof = ring_launch_roofline(plan, d_codes, outs, rows, err)
         except Exception as e:  # reported, never silently dropped; the headline above stands on its own
@@ -637,6 +687,7 @@ def bench_c3(args, dist, rank, world):
         "ms_per_step": elapsed * 1e3 / args.steps,
         "higher_is_better": True,
         "scaling": "weak",
+        "full": bool(args.full),
         "vs_baseline": None,
         "dtype": "f64",
         "data": "synthetic (forward-sampled munin evidence rows, seed 42+rank)",
@@ -709,7 +760,10 @@ def bench_c3(args, dist, rank, world):
             "single_launch_ring": ring_roof,
         },
     }
-    if rank == 0:
+    if dumped is not None:
+        result["outputs"] = {"dir": args.dump_outputs, "files": dumped,
+                             "of": "the last timed step's batch, variables in sorted-name order"}
+    if rank == 0 and args.full:
         n_chk = max(16, 64 // nb)
         checks = [parity_spot_check(model, missing, plan, outs[i], codes_all[:, perms[i][:n_chk]], nodes,
                                     n_check=n_chk) for i in range(nb)]
@@ -722,10 +776,10 @@ def bench_c3(args, dist, rank, world):
             result["cpu_baseline"]["cores_on_host"] = os.cpu_count()
         if world == 1 and not args.no_api_e2e:
             result["api_e2e"] = api_e2e_rate(model, codes_all, nodes, missing)
-    if not args.no_c5:
+    if args.full and not args.no_c5:
         result["c5"] = c5_subline(args, dist, rank, world, model, variables, observed, plan, codes_ev, d_codes,
                                   rows * nb)
-    if dist is not None:
+    if dist is not None and args.full:
         # the result delivery (outside the timed region in this weak-scaling line; --workload c5
         # times it inside the step): every rank's [17, rows] marginals to rank 0
         from pgmpy_amd.distributed import gather_rows
@@ -806,7 +860,7 @@ def c5_subline(args, dist, rank, world, model, variables, observed, plan, codes_
     for name, fn, output in (("host", bench_c5_host, "marginals"), ("host_map", bench_c5_host, "map"),
                              ("rccl", bench_c5, "marginals")):
         a = copy.copy(args)
-        a.rows, a.c5_output = total, output
+        a.rows, a.c5_output, a.dump_outputs = total, output, None
         try:
             r = fn(a, dist, rank, world, inp=inp)
             out[name] = {k: r[k] for k in keep if k in r}
@@ -868,9 +922,12 @@ def bench_c3_ring(args, dist, rank, world, model, missing, variables, plan, d_co
     bpr = plan.algorithmic_bytes_per_row(marginals=True)
     achieved = bpr * rows / (kern_ms * 1e-3) / 1e9
     ms_per_step = elapsed * 1e3 / args.steps
+    # batch b (0-based) runs on buffer set b % nb: the last timed step is batch steps - 1
+    dumped = dump_outputs(args, c3_last_step_arrays(plan, outs[(args.steps - 1) % nb]), rank) \
+        if args.dump_outputs else None
     hip_args = copy.copy(args)
     hip_args.launch = "hip"
-    floor_ms, single_ms = dispatch_floor_ms(plan, d_codes, rows, hip_args, Launcher)
+    floor_ms, single_ms = dispatch_floor_ms(plan, d_codes, rows, hip_args, Launcher) if args.full else (None, None)
     traffic, traffic_rows = load_traffic(kname)
     if traffic is not None and traffic_rows:
         traffic = traffic * rows / traffic_rows
@@ -885,6 +942,7 @@ def bench_c3_ring(args, dist, rank, world, model, missing, variables, plan, d_co
         "ms_per_step": ms_per_step,
         "higher_is_better": True,
         "scaling": "weak",
+        "full": bool(args.full),
         "vs_baseline": None,
         "dtype": "f64",
         "data": "synthetic (forward-sampled munin evidence rows, seed 42+rank)",
@@ -932,7 +990,10 @@ def bench_c3_ring(args, dist, rank, world, model, missing, variables, plan, d_co
             "working_set_exceeds_mall": working_set > MALL_BYTES,
         },
     }
-    if rank == 0:
+    if dumped is not None:
+        result["outputs"] = {"dir": args.dump_outputs, "files": dumped,
+                             "of": "the last timed step's batch, variables in sorted-name order"}
+    if rank == 0 and args.full:
         n_chk = max(16, 64 // nb)
         checks = [parity_spot_check(model, missing, plan, outs[i], codes_all[:, perms[i][:n_chk]], nodes,
                                     n_check=n_chk) for i in range(nb)]
@@ -1074,6 +1135,9 @@ def bench_c5_host(args, dist, rank, world, inp=None):
     barrier(dist)
     elapsed = max_over_ranks(dist, t_end - t_start)
     assert int(err.item()) == 0
+    if args.dump_outputs:  # the last timed step's delivery, as it lies in pinned host memory (rank r's block)
+        last = np.array(hosts[(args.steps - 1) % 2].numpy())
+        dump_outputs(args, {"map": last} if want_map else {"marginals": sorted_marginals(plan, last)}, rank)
     # the parts alone, outside the window: the launch over rotating HBM-sized buffers (the roofline),
     # and the copy-out (back to back, one stream)
     roof = rotating_roofline(plan, codes_ev, rows, want_map, err, args.steps)
@@ -1210,6 +1274,11 @@ def bench_c5(args, dist, rank, world, inp=None):
     barrier(dist)
     elapsed = max_over_ranks(dist, t_end - t_start)
     assert int(err.item()) == 0
+    if args.dump_outputs:  # the last timed step's send buffer (rank r's block, before the gather)
+        from pgmpy_amd.inference.batch import download
+
+        last = download(sends[(args.steps - 1) % nbuf])[:, :rows]
+        dump_outputs(args, {"map": last} if want_map else {"marginals": sorted_marginals(plan, last)}, rank)
     # the launches alone, then the gathers alone, outside the timed region (wall per step, max over ranks)
     barrier(dist)
     l0 = time.perf_counter()
@@ -1334,6 +1403,7 @@ def bench_c2(args):
         r = ve.query(q, rows[k % len(rows)], show_progress=False)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    dump_outputs(args, {"posterior": np.asarray(r.values, dtype=np.float64)})  # the last timed query's
     runner, = ve._compiled.values()
     plan = runner.plan
     ps = plan.path_stats(1)
@@ -1421,9 +1491,10 @@ def bench_c1(args):
     reps = max(1, args.steps // 10)
     for _ in range(reps):
         for q, e in pats:
-            ve.query(q, e, show_progress=False)
+            r = ve.query(q, e, show_progress=False)
     torch.cuda.synchronize()
     warm = (time.perf_counter() - t0) / (reps * len(pats))
+    dump_outputs(args, {"joint": np.asarray(r.values, dtype=np.float64)})  # the last timed query's
     worst, ok = 0.0, True
     for p in g["patterns"]:
         r = ve.query(p["variables"], p["evidence"], show_progress=False)
@@ -1514,6 +1585,10 @@ def bench_c4(args):
         return (time.perf_counter() - t0) / args.steps, c
 
     dt, cal = rate(1)
+    if args.dump_outputs:  # the last timed calibration: every clique belief of 64 seeded rows, cliques in order
+        pick = sorted(int(x) for x in np.random.default_rng(11).choice(n, min(n, 64), replace=False))
+        bel = cal.clique_beliefs_rows(pick)
+        dump_outputs(args, {"clique_beliefs": np.concatenate([bel[c] for c in bjt.cliques], axis=1)})
     two = None
     if args.c4_inflight > 1:  # lane 0's compiled schedule is shared with the one-at-a-time run
         dt2, _ = rate(args.c4_inflight)
@@ -1605,7 +1680,7 @@ def subconfigs(args):
                            ("c2", bench_c2, dict(steps=400, warmup=40)),
                            ("c4", bench_c4, dict(steps=20, warmup=3, rows=4000))):
         a = copy.copy(args)
-        vars(a).update(over)
+        vars(a).update(over, dump_outputs=None)  # --dump-outputs holds the headline path's outputs only
         t0 = time.perf_counter()
         try:
             out[name] = fn(a)
@@ -1631,6 +1706,14 @@ def main():
     ap.add_argument("--c5-delivery", default="host", choices=["host", "rccl"],
                     help="c5: each rank DMAs its block's results into pinned host memory (host, no collective) "
                          "or gathers them into rank 0's GPU over RCCL (rccl)")
+    ap.add_argument("--full", action="store_true",
+                    help="c3: besides the timed steps, everything else the line can carry: the CPU baselines, the "
+                         "parity check against the oracle, the dispatch floor, the single-launch and streamed "
+                         "rooflines, the DataFrame API rate, the c5 sub-object and the c1 / c2 / c4 sub-objects "
+                         "(minutes; the --no-* options below drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all; same arguments, same inputs)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--c4-inflight", type=int, default=2,
@@ -1676,12 +1759,12 @@ def main():
     build(verbose=False)
     args.cpu_pre = None
     single_process = int(os.environ.get("WORLD_SIZE", "1")) == 1
-    if args.workload == "c3" and single_process and not args.no_cpu_baseline:
+    if args.workload == "c3" and single_process and args.full and not args.no_cpu_baseline:
         args.cpu_pre = cpu_baselines_c3(args)  # before dist_setup: no GPU state in the forked workers
     dist, rank, world = dist_setup(args.gpus, args.dist_backend)
     if args.workload == "c3":
         res = bench_c3(args, dist, rank, world)
-        if world == 1 and not args.no_subconfigs:
+        if world == 1 and args.full and not args.no_subconfigs:
             res.update(subconfigs(args))
     elif args.workload == "c5":
         res = (bench_c5_host if args.c5_delivery == "host" else bench_c5)(args, dist, rank, world)

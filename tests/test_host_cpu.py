@@ -673,6 +673,66 @@ def test_bench_cpu_baselines_run():
     assert allcore["value"] > 0 and allcore["cores"] >= 1
 
 
+def test_bench_dump_outputs_files(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 kept, other dtypes written as float64, one
+    <name>.npy per array, nothing written without the option."""
+    import argparse
+
+    import bench
+
+    assert bench.dump_outputs(argparse.Namespace(dump_outputs=None), {"a": np.ones(3)}) is None
+    d = tmp_path / "out"
+    a64, a32, i32 = np.arange(12.0).reshape(3, 4), np.arange(5, dtype=np.float32), np.arange(4, dtype=np.int32)
+    wrote = bench.dump_outputs(argparse.Namespace(dump_outputs=str(d)), {"a": a64, "b": a32, "c": i32})
+    assert sorted(os.listdir(d)) == ["a.npy", "b.npy", "c.npy"] == sorted(wrote)
+    got = {k: np.load(d / f"{k}.npy") for k in "abc"}
+    assert got["a"].dtype == np.float64 and np.array_equal(got["a"], a64)
+    assert got["b"].dtype == np.float32 and np.array_equal(got["b"], a32)
+    assert got["c"].dtype == np.float64 and np.array_equal(got["c"], i32)
+    assert not any(w["sampled"] for w in wrote.values())
+
+
+def test_bench_dump_outputs_cap(tmp_path, monkeypatch):
+    """Past the cap in all, every array is cut to the same seeded sample on every run, in order, and
+    the files together stay under the cap."""
+    import argparse
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    big = np.random.default_rng(0).random((17, 100))  # 13,600 B
+    small = np.arange(200, dtype=np.float32)  # 800 B
+    runs = []
+    for name in ("r1", "r2"):
+        d = tmp_path / name
+        wrote = bench.dump_outputs(argparse.Namespace(dump_outputs=str(d)), {"big": big, "small": small})
+        assert all(w["sampled"] for w in wrote.values())
+        runs.append({k: np.load(d / f"{k}.npy") for k in ("big", "small")})
+    for k in ("big", "small"):
+        assert np.array_equal(runs[0][k], runs[1][k])
+    assert sum(a.nbytes for a in runs[0].values()) <= 4096
+    flat = big.ravel()
+    pos = np.searchsorted(np.sort(flat), runs[0]["big"])  # every sampled entry is an entry of the array
+    assert np.array_equal(np.sort(flat)[pos], runs[0]["big"])
+    assert 1 < runs[0]["big"].size < big.size
+
+
+def test_bench_dump_marginals_in_sorted_variable_order():
+    """The dumped marginals do not depend on the plan's (set-iteration) variable order."""
+    import types
+
+    import bench
+
+    rows = {"b": np.full((2, 4), 2.0), "a": np.full((3, 4), 1.0), "c": np.full((1, 4), 3.0)}
+    outs = []
+    for order in (["b", "a", "c"], ["c", "b", "a"]):
+        cards = [rows[v].shape[0] for v in order]
+        plan = types.SimpleNamespace(variables=order, cards=cards, acc_off=list(np.cumsum([0] + cards[:-1])))
+        outs.append(bench.sorted_marginals(plan, np.concatenate([rows[v] for v in order])))
+    assert np.array_equal(outs[0], outs[1])
+    assert outs[0][:, 0].tolist() == [1.0, 1.0, 1.0, 2.0, 2.0, 3.0]
+
+
 def test_c4_junction_tree_is_the_golden_tree():
     """bench.py's C4 line builds its tree with junction_tree_from_model (min-fill decomposition); the
     pathfinder BP fixture (tests/golden/pathfinder_bp.json) holds the reference's beliefs on a tree the

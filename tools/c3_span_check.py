@@ -13,7 +13,8 @@ dispatch's HSA start / end ticks and its queue.  From them alone this script rec
 and checks it against the line within 5 %.  It also splits the span the way the ring comparison needs:
 per-dispatch durations, how many dispatches are in flight over the span (time-weighted), the ramp
 (window start to the first moment four dispatches run) and the tail (last moment four run to the end),
-and the steady part's time per step.
+and the steady part's time per step.  The ring comparison (span_over_ring) needs a line printed by
+`bench.py --full`, which carries roofline.single_launch_ring; a plain line gives everything else.
 """
 import json
 import sys
