@@ -114,6 +114,35 @@ int pgm_contract_workspace(const pgm_contract_desc *d, size_t *bytes);
 int pgm_contract(const pgm_contract_desc *d, const double *A, const double *B, double *C,
                  void *workspace, size_t workspace_bytes, void *stream);
 
+/* Which kernel pgm_contract would launch for this descriptor and these operand addresses, and with which
+ * plan.  Host-only (no HIP call, no device needed; A and C are only compared for 16-B alignment, which
+ * decides PGM_CK_ROWS_TAB2; NULL counts as aligned).  The launcher takes its choice from the
+ * same function, so what is reported is what runs.  For tests and inspection. */
+enum pgm_contract_kernel {
+  PGM_CK_FLAT = 0,     /* k_contract: G = 2^g_log2 lanes per output, grid (blocks, n_split)          */
+  PGM_CK_ROWS = 1,     /* k_contract_rows: innermost kept dim across lanes, grid (x, outer, n_split) */
+  PGM_CK_ROWS_TAB = 2, /* k_contract_rows_tab: <= 512 reduction offsets from an LDS table, no split  */
+  PGM_CK_ROWS_TAB2 = 3 /* k_contract_rows_tab2: the same for COPY, two rows per lane (16-B accesses) */
+};
+typedef struct {
+  int32_t kernel;        /* enum pgm_contract_kernel */
+  int32_t g_log2;        /* flat: log2 of the lanes per output */
+  uint32_t n_split;      /* > 1: partial results in the workspace, then k_contract_final */
+  uint32_t red_chunk;    /* reduction-outer (flat: of n_ro, rows: of n_v) indices per split */
+  uint32_t ri_nb;        /* rows: chunks the innermost reduction dim is cut into */
+  uint32_t ri_chunk;     /* rows: innermost reduction entries per chunk */
+  uint32_t grid[3];      /* of the contraction kernel as launched */
+  uint32_t n_ro;         /* reduction-outer indices */
+  uint32_t n_v;          /* rows: n_ro * ri_nb (0 in flat mode) */
+  uint32_t n_out;        /* outputs */
+  uint32_t n_red;        /* reduction entries per output */
+  uint32_t ri_card;      /* innermost reduction extent after coalescing */
+  uint32_t nx;           /* innermost kept extent after coalescing (rows: the dim across the lanes) */
+  uint32_t unrolled;     /* rows without a reduction: 1 when the 4-wide loop is entered (NX > 3 * grid.x * 256) */
+  uint32_t empty_splits; /* splits whose range starts past the last reduction-outer index (they write the identity) */
+} pgm_contract_info_t;
+int pgm_contract_info(const pgm_contract_desc *d, const double *A, const double *C, pgm_contract_info_t *info);
+
 /* ---------------------------------------------------------------- n-ary product
  * C[keep] = prod_i X_i[keep . keep_s[i]]  (up to PGM_PRODN_MAX_OPS broadcast operands).
  * factor_product's left fold of __mul__ (pgmpy/factors/base.py:20-66) in one pass, and the

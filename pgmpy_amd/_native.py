@@ -62,6 +62,31 @@ class ContractDesc(ctypes.Structure):
     ]
 
 
+CK_FLAT, CK_ROWS, CK_ROWS_TAB, CK_ROWS_TAB2 = 0, 1, 2, 3  # enum pgm_contract_kernel
+CK_NAMES = ("FLAT", "ROWS", "ROWS_TAB", "ROWS_TAB2")
+
+
+class ContractInfo(ctypes.Structure):
+    """pgm_contract_info_t: the kernel and plan pgm_contract would run (host-only query)."""
+    _fields_ = [
+        ("kernel", ctypes.c_int32),
+        ("g_log2", ctypes.c_int32),
+        ("n_split", ctypes.c_uint32),
+        ("red_chunk", ctypes.c_uint32),
+        ("ri_nb", ctypes.c_uint32),
+        ("ri_chunk", ctypes.c_uint32),
+        ("grid", ctypes.c_uint32 * 3),
+        ("n_ro", ctypes.c_uint32),
+        ("n_v", ctypes.c_uint32),
+        ("n_out", ctypes.c_uint32),
+        ("n_red", ctypes.c_uint32),
+        ("ri_card", ctypes.c_uint32),
+        ("nx", ctypes.c_uint32),
+        ("unrolled", ctypes.c_uint32),
+        ("empty_splits", ctypes.c_uint32),
+    ]
+
+
 PRODN_MAX_OPS = 8
 PM_MAX_OPS = 8  # operands of a fused product + marginal step (pgm_internal.h MOPS)
 
@@ -169,6 +194,7 @@ _SIGS = {
     "pgm_event_elapsed_ms": ([_P, _P, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
     "pgm_contract_workspace": ([ctypes.POINTER(ContractDesc), ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
     "pgm_contract": ([ctypes.POINTER(ContractDesc), _P, _P, _P, _P, ctypes.c_size_t, _P], ctypes.c_int),
+    "pgm_contract_info": ([ctypes.POINTER(ContractDesc), _P, _P, ctypes.POINTER(ContractInfo)], ctypes.c_int),
     "pgm_product_n": ([ctypes.POINTER(ProductNDesc), ctypes.POINTER(_P), _P, _P], ctypes.c_int),
     "pgm_product_n_marginal_ok": ([ctypes.POINTER(ProductNDesc), ctypes.POINTER(_P), _P,
                                    ctypes.POINTER(ctypes.c_int64), _P], ctypes.c_int),

@@ -35,7 +35,7 @@
 #include "pgmhip.h"
 #include "pgm_internal.h"
 
-#define PGM_ABI_VERSION 23  // 23: pgm_batch_add_contract_n (n-ary contraction jobs), pgm_dq_timer_dispatch_times, pgm_host_scan_* / pgm_host_lut_map_u8; 22: pgm_dq_bind_pm / pgm_dq_run_chain / pgm_dq_profiling; 21: pgm_batch_specialise; 20: pgm_batch_info and the grid-barrier levelled batch removed (levels: single-workgroup mode only); 19: pgm_stream_sync_spin; 18: pgm_batch_set_mode (single-workgroup levelled batch), pgm_batch_blocks; 17: pgm_rows_shard_run (rows sharded over several GPUs from host buffers); 16: pgm_rows_ring_start_ready; 15: pgm_batch_add_level / pgm_batch_info (levelled batch), pgm_memcpy_d2h_async; 14: pgm_rows_ring_* (resident ring of row batches); 13: pgm_dq_timer_dispatch_stats, pgm_rows_bound_kernel; 12: pgm_dq_launch_group, pgm_dq_timer_stop_ticks, PGM_ROWS_FLOOR; 11: pgm_product_n_marginal_bind / pgm_pm_bound_*; 10: pgm_dq_* direct AQL dispatch, pgm_codes_remap; 9: gemm lane_order, batch product_n / indicator
+#define PGM_ABI_VERSION 24  // 24: pgm_contract_info (host-only query of the planned contraction kernel; the launcher takes its choice from the same function); 23: pgm_batch_add_contract_n (n-ary contraction jobs), pgm_dq_timer_dispatch_times, pgm_host_scan_* / pgm_host_lut_map_u8; 22: pgm_dq_bind_pm / pgm_dq_run_chain / pgm_dq_profiling; 21: pgm_batch_specialise; 20: pgm_batch_info and the grid-barrier levelled batch removed (levels: single-workgroup mode only); 19: pgm_stream_sync_spin; 18: pgm_batch_set_mode (single-workgroup levelled batch), pgm_batch_blocks; 17: pgm_rows_shard_run (rows sharded over several GPUs from host buffers); 16: pgm_rows_ring_start_ready; 15: pgm_batch_add_level / pgm_batch_info (levelled batch), pgm_memcpy_d2h_async; 14: pgm_rows_ring_* (resident ring of row batches); 13: pgm_dq_timer_dispatch_stats, pgm_rows_bound_kernel; 12: pgm_dq_launch_group, pgm_dq_timer_stop_ticks, PGM_ROWS_FLOOR; 11: pgm_product_n_marginal_bind / pgm_pm_bound_*; 10: pgm_dq_* direct AQL dispatch, pgm_codes_remap; 9: gemm lane_order, batch product_n / indicator
 
 // ----------------------------------------------------------------------------- errors
 static thread_local std::string g_err;
@@ -736,22 +736,28 @@ static bool rows2_ok(const ContractK &k, const double *A, const double *C) {
   return k.nr == 0 || k.ri_sa % 2 == 0;
 }
 
+// the kernel a planned contraction runs (enum pgm_contract_kernel) and its grid: the one place that
+// decides it, for the launcher and for pgm_contract_info
+static int contract_kernel(const ContractLaunch &L, int combine, int reduce, const double *A, const double *C,
+                           dim3 &grid) {
+  grid = L.grid;
+  if (!L.k.row_mode) return PGM_CK_FLAT;
+  if (reduce == PGM_RED_NONE || L.k.n_split != 1 || L.k.ri_nb != 1 || L.k.n_red > RTAB_MAX) return PGM_CK_ROWS;
+  if (combine != PGM_COMBINE_COPY || !rows2_ok(L.k, A, C)) return PGM_CK_ROWS_TAB;
+  grid.x = (unsigned)std::max<uint64_t>(1, (grid.x + 1) / 2);
+  return PGM_CK_ROWS_TAB2;
+}
+
 template <int CMB, int RED>
 static void launch_contract_t(const ContractLaunch &L, const double *A, const double *B, double *C, double *ws,
                               hipStream_t s) {
-  if (L.k.row_mode && RED != PGM_RED_NONE && L.k.n_split == 1 && L.k.ri_nb == 1 && L.k.n_red <= RTAB_MAX) {
-    if (CMB == PGM_COMBINE_COPY && rows2_ok(L.k, A, C)) {
-      dim3 g = L.grid;
-      g.x = (unsigned)std::max<uint64_t>(1, (g.x + 1) / 2);
-      hipLaunchKernelGGL((k_contract_rows_tab2<RED>), g, dim3(256), 0, s, L.k, A, C);
-    } else {
-      hipLaunchKernelGGL((k_contract_rows_tab<CMB, RED>), L.grid, dim3(256), 0, s, L.k, A, B, C);
-    }
+  dim3 g;
+  switch (contract_kernel(L, CMB, RED, A, C, g)) {
+    case PGM_CK_ROWS_TAB2: hipLaunchKernelGGL((k_contract_rows_tab2<RED>), g, dim3(256), 0, s, L.k, A, C); break;
+    case PGM_CK_ROWS_TAB: hipLaunchKernelGGL((k_contract_rows_tab<CMB, RED>), g, dim3(256), 0, s, L.k, A, B, C); break;
+    case PGM_CK_ROWS: hipLaunchKernelGGL((k_contract_rows<CMB, RED>), g, dim3(256), 0, s, L.k, A, B, C, ws); break;
+    default: hipLaunchKernelGGL((k_contract<CMB, RED>), g, dim3(256), 0, s, L.k, A, B, C, ws); break;
   }
-  else if (L.k.row_mode)
-    hipLaunchKernelGGL((k_contract_rows<CMB, RED>), L.grid, dim3(256), 0, s, L.k, A, B, C, ws);
-  else
-    hipLaunchKernelGGL((k_contract<CMB, RED>), L.grid, dim3(256), 0, s, L.k, A, B, C, ws);
   if (L.k.n_split > 1) {
     uint64_t blocks = std::min<uint64_t>((L.k.n_out + 255) / 256, 65535);
     hipLaunchKernelGGL((k_contract_final<RED>), dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(256), 0, s,
@@ -3124,6 +3130,38 @@ int pgm_contract_workspace(const pgm_contract_desc *d, size_t *bytes) {
   int rc = plan_contract(d, L);
   if (rc) return rc;
   *bytes = L.ws_doubles * sizeof(double);
+  return PGM_OK;
+}
+
+int pgm_contract_info(const pgm_contract_desc *d, const double *A, const double *C, pgm_contract_info_t *info) {
+  if (!info) return fail(PGM_EINVAL, "null pointer");
+  ContractLaunch L;
+  int rc = plan_contract(d, L);
+  if (rc) return rc;
+  memset(info, 0, sizeof *info);
+  const ContractK &k = L.k;
+  dim3 g;
+  info->kernel = contract_kernel(L, d->combine, d->reduce, A, C, g);
+  info->g_log2 = k.g_log2;
+  info->n_split = (uint32_t)k.n_split;
+  info->red_chunk = k.red_chunk;
+  info->ri_nb = k.ri_nb;
+  info->ri_chunk = k.ri_chunk;
+  info->grid[0] = g.x;
+  info->grid[1] = g.y;
+  info->grid[2] = g.z;
+  info->n_ro = k.n_ro;
+  info->n_v = k.n_v;
+  info->n_out = k.n_out;
+  info->n_red = k.n_red;
+  info->ri_card = k.ri_card;
+  const uint64_t NX = k.nk > 0 ? k.kdiv[k.nk - 1].d : 1;
+  info->nx = (uint32_t)NX;
+  info->unrolled = info->kernel == PGM_CK_ROWS && d->reduce == PGM_RED_NONE && NX > 3ull * g.x * 256;
+  // split s covers reduction-outer indices [s * red_chunk, ...): empty once that start is past the end
+  const uint64_t units = k.row_mode ? k.n_v : k.n_ro;
+  const uint64_t used = k.red_chunk ? (units + k.red_chunk - 1) / k.red_chunk : 0;
+  info->empty_splits = (uint32_t)((uint64_t)k.n_split > used ? (uint64_t)k.n_split - used : 0);
   return PGM_OK;
 }
 

@@ -278,24 +278,30 @@ def scalar(x):
     return to_device(np.array(x, dtype=np.float64))
 
 
-def prepare_contract(A, la, B, lb, out_labels, reduce=None, combine="mul", out=None):
-    """Build (descriptor, out, workspace, ws_bytes) for C[out_labels] = REDUCE COMBINE(A, B).
+def c_order_strides(shape):
+    """Element strides of a C-order array of this shape."""
+    st, acc = [], 1
+    for c in reversed(list(shape)):
+        st.append(acc)
+        acc *= int(c)
+    return st[::-1]
 
-    A/B: device fp64 tensors (any strides), la/lb: one label per axis (B may be
-    None for combine="copy").  Labels absent from an operand broadcast (stride 0);
-    labels absent from out_labels are reduced."""
-    L = N.lib()
+
+def contract_desc(la, shape_a, stride_a, lb, shape_b, stride_b, out_labels, reduce=None, combine="mul",
+                  out_stride=None):
+    """(descriptor, output shape) of C[out_labels] = REDUCE COMBINE(A[la], B[lb]) from label lists, shapes
+    and element strides alone: no tensor, no allocation, no library call.  lb None: no second operand
+    (combine="copy").  out_stride None: a C-order output.  Labels absent from an operand broadcast
+    (stride 0); labels absent from out_labels are reduced."""
     la = list(la)
-    lb = list(lb) if B is not None else []
+    lb = list(lb) if lb is not None else []
     out_labels = list(out_labels)
-    if len(la) != A.dim() or (B is not None and len(lb) != B.dim()):
+    if len(la) != len(shape_a) or (lb and len(lb) != len(shape_b)):
         raise ValueError("label count does not match tensor rank")
     card = {}
-    for t, ls in ((A, la), (B, lb)):
-        if t is None:
-            continue
+    for shape, ls in ((shape_a, la), (shape_b, lb)):
         for d, l in enumerate(ls):
-            c = int(t.shape[d])
+            c = int(shape[d])
             if card.setdefault(l, c) != c:
                 raise ValueError(f"cardinality mismatch for {l!r}: {card[l]} vs {c}")
     for l in out_labels:
@@ -306,15 +312,16 @@ def prepare_contract(A, la, B, lb, out_labels, reduce=None, combine="mul", out=N
         raise ValueError(f"labels {red} would be reduced but reduce=None")
     if len(out_labels) > N.PGM_MAX_DIMS or len(red) > N.PGM_MAX_DIMS:
         raise ValueError(f"too many dimensions ({len(out_labels)} kept, {len(red)} reduced; limit {N.PGM_MAX_DIMS})")
-    if out is None:
-        out = empty([card[l] for l in out_labels])
-    elif tuple(out.shape) != tuple(card[l] for l in out_labels):
+    out_shape = [card[l] for l in out_labels]
+    if out_stride is None:
+        out_stride = c_order_strides(out_shape)
+    elif len(out_stride) != len(out_labels):
         raise ValueError("out has the wrong shape")
 
-    def st(t, ls, l):
-        if t is None or l not in ls:
+    def st(strides, ls, l):
+        if l not in ls:
             return 0
-        return int(t.stride(ls.index(l)))
+        return int(strides[ls.index(l)])
 
     d = N.ContractDesc()
     d.combine = _COMBINE[combine]
@@ -323,17 +330,57 @@ def prepare_contract(A, la, B, lb, out_labels, reduce=None, combine="mul", out=N
     d.n_red = len(red)
     for i, l in enumerate(out_labels):
         d.keep_card[i] = card[l]
-        d.keep_sa[i] = st(A, la, l)
-        d.keep_sb[i] = st(B, lb, l)
-        d.keep_sc[i] = int(out.stride(i))
+        d.keep_sa[i] = st(stride_a, la, l)
+        d.keep_sb[i] = st(stride_b, lb, l)
+        d.keep_sc[i] = int(out_stride[i])
     for i, l in enumerate(red):
         d.red_card[i] = card[l]
-        d.red_sa[i] = st(A, la, l)
-        d.red_sb[i] = st(B, lb, l)
+        d.red_sa[i] = st(stride_a, la, l)
+        d.red_sb[i] = st(stride_b, lb, l)
+    return d, out_shape
+
+
+def prepare_contract(A, la, B, lb, out_labels, reduce=None, combine="mul", out=None):
+    """Build (descriptor, out, workspace, ws_bytes) for C[out_labels] = REDUCE COMBINE(A, B).
+
+    A/B: device fp64 tensors (any strides), la/lb: one label per axis (B may be
+    None for combine="copy").  Labels absent from an operand broadcast (stride 0);
+    labels absent from out_labels are reduced."""
+    L = N.lib()
+    la = list(la)
+    if len(la) != A.dim() or (B is not None and len(lb) != B.dim()):
+        raise ValueError("label count does not match tensor rank")
+    d, out_shape = contract_desc(la, A.shape, A.stride(), lb if B is not None else None,
+                                 B.shape if B is not None else (), B.stride() if B is not None else (),
+                                 out_labels, reduce, combine, None if out is None else out.stride())
+    if out is None:
+        out = empty(out_shape)
+    elif tuple(out.shape) != tuple(out_shape):
+        raise ValueError("out has the wrong shape")
     ws_bytes = ctypes.c_size_t(0)
     N.check(L.pgm_contract_workspace(ctypes.byref(d), ctypes.byref(ws_bytes)), "contract")
     ws = empty([ws_bytes.value // 8]) if ws_bytes.value else None
     return d, out, ws, ws_bytes.value
+
+
+def contract_info(la, shape_a, stride_a, lb, shape_b, stride_b, out_labels, reduce=None, combine="mul",
+                  out_stride=None, a_ptr=0, c_ptr=0):
+    """The kernel and plan pgm_contract would run for this contraction (N.ContractInfo; pgm_contract_info:
+    no device needed).  a_ptr / c_ptr: the addresses of A and C, of which only the 16-B alignment matters."""
+    d, _ = contract_desc(la, shape_a, stride_a, lb, shape_b, stride_b, out_labels, reduce, combine, out_stride)
+    info = N.ContractInfo()
+    N.check(N.load_library().pgm_contract_info(ctypes.byref(d), ctypes.c_void_p(int(a_ptr)), ctypes.c_void_p(int(c_ptr)),
+                                               ctypes.byref(info)), "contract_info")
+    return info
+
+
+def contract_info_tensors(A, la, B, lb, out_labels, reduce=None, combine="mul", out=None):
+    """contract_info for the tensors a contract() call with the same arguments would run on (out None: the
+    C-order output the engine allocates, 16-B aligned like every fresh allocation)."""
+    return contract_info(la, A.shape, A.stride(), lb if B is not None else None,
+                         B.shape if B is not None else (), B.stride() if B is not None else (), out_labels, reduce,
+                         combine, None if out is None else out.stride(), A.data_ptr(),
+                         0 if out is None else out.data_ptr())
 
 
 def contract(A, la, B, lb, out_labels, reduce=None, combine="mul", out=None):
