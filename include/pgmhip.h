@@ -617,6 +617,12 @@ int pgm_dq_timer_dispatch_stats(void *dq, uint64_t *sum_ticks, uint64_t *count);
  * *count = how many were written.  The raw timestamps behind the C3 line's span-based frac. */
 int pgm_dq_timer_dispatch_times(void *dq, uint64_t *start, uint64_t *end, int32_t cap, int32_t *count);
 int pgm_dq_bound_destroy(void *dbound);
+/* introspection (tests): the kernel object a bound launch dispatches, the device address of its kernarg
+ * segment, and how many bound launches currently share its loaded code object.  Bound launches of one
+ * code object on one device — whatever their queue — share one loaded executable, so they report the
+ * same kernel object for the same kernel; kernarg segments are 256-byte slots of device allocations of
+ * at least 64 KiB, reused after pgm_dq_bound_destroy.  Any output pointer may be NULL. */
+int pgm_dq_bound_info(void *dbound, uint64_t *kernel_object, uint64_t *kernarg, int32_t *sharers);
 /* r05 (ABI 22): a compiled query's steps on the queue (VariableElimination.query through a captured
  * plain Program, pgmpy/inference/ExactInference.py:349-440, C1 / C2).  pgm_dq_bind_pm re-binds one
  * plan-specialised launch (pgm_pm_bound_* handle: a fused product step, a merged level or a specialised

@@ -29,7 +29,8 @@ def hipcc():
 
 def build(force=False, verbose=True, out=OUT, defines=()):
     """defines: extra -D macros (tools only, e.g. PGM_ROWS_TIMELINE into lib/libpgmhip_timeline.so)."""
-    deps = [SRC, SRC_DQ, SRC_PM, SRC_HOST, os.path.join(HERE, "csrc", "pgm_internal.h"), os.path.join(INC, "pgmhip.h")]
+    deps = [SRC, SRC_DQ, SRC_PM, SRC_HOST, os.path.join(HERE, "csrc", "pgm_internal.h"),
+            os.path.join(HERE, "csrc", "pgm_share.h"), os.path.join(INC, "pgmhip.h")]
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
         return out
     os.makedirs(os.path.dirname(out), exist_ok=True)

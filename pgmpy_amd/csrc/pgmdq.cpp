@@ -5,8 +5,9 @@
 // (~4.5 us of host time on the MI355X boxes, more than the 100k-row kernel itself).  Here the
 // launch is what CDNA executes natively: one 64-byte kernel-dispatch packet written into an HSA
 // user-mode queue of the GPU agent and a doorbell write.  The code object is the same hipRTC
-// output HIP loaded (pgmi_rows_bound_jit), loaded a second time into an HSA executable; the
-// argument segment lives in device memory, written once at bind time.
+// output HIP loaded (pgmi_rows_bound_jit), loaded a second time into an HSA executable — once per code
+// object and agent, shared by every bound launch that runs it (pgm_share.h); the argument segment is a
+// 256-byte slot of a device-memory slab, written once at bind time.
 //
 // Ordering contract (include/pgmhip.h, pgm_dq_*): pgm_dq_bind_rows drains the device (HIP work that
 // produced the inputs is complete); packets on the queue run in order (barrier bit set: each
@@ -30,12 +31,14 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "pgm_internal.h"
+#include "pgm_share.h"
 #include "pgmhip.h"
 
 namespace {
@@ -75,14 +78,60 @@ struct DirectQueue {
   bool profiling = true;
 };
 
-struct DirectBound {
-  DirectQueue *dq = nullptr;
+// a kernel of a loaded code object as a dispatch packet names it
+struct KernelInfo {
+  uint64_t kernel_object = 0;
+  uint32_t group_bytes = 0, private_bytes = 0, kernarg_bytes = 0;
+};
+
+// one code object loaded and frozen for one agent, shared by every bound launch that runs it (the 96
+// resident batches of a row plan are one kernel at one address, not 96 copies the instruction cache and
+// L2 see as different code); holds an hsa_init reference of its own, so the queue whose bind loaded it
+// may be destroyed first
+struct LoadedCode {
+  hsa_agent_t agent{};
   hsa_code_object_reader_t reader{};
   hsa_executable_t exec{};
+  bool hsa_up = false, have_reader = false, have_exec = false;
+  std::map<std::string, KernelInfo> kernels;  // symbol lookups made so far (registry mutex)
+};
+
+using CodeRegistry = pgmshare::CodeRegistry<LoadedCode>;
+
+CodeRegistry &code_registry() {
+  static CodeRegistry *r = new CodeRegistry;  // never destroyed: bounds may outlive static destructors
+  return *r;
+}
+
+void unload_code(CodeRegistry::Entry &e) {
+  LoadedCode &c = e.value;
+  if (c.have_exec) (void)hsa_executable_destroy(c.exec);
+  if (c.have_reader) (void)hsa_code_object_reader_destroy(c.reader);
+  if (c.hsa_up) (void)hsa_shut_down();
+  c = LoadedCode{};
+}
+
+// kernarg segments of every bound launch on a device: 256-byte slots of shared device allocations
+// instead of one allocation (one page, one translation) per launch
+struct DeviceSlab {
+  std::mutex mu;
+  std::map<int, pgmshare::KernargSlab> by_device;
+};
+
+DeviceSlab &kernarg_slabs() {
+  static DeviceSlab *s = new DeviceSlab;  // device memory is returned with the process
+  return *s;
+}
+
+struct DirectBound {
+  DirectQueue *dq = nullptr;
+  CodeRegistry::Entry *code = nullptr;
   uint64_t kernel_object = 0;
   uint32_t group_bytes = 0, private_bytes = 0;
   uint16_t rel_scope = HSA_FENCE_SCOPE_AGENT;
-  void *kernarg = nullptr;  // device memory
+  void *kernarg = nullptr;  // device memory: a segment of the device's slab
+  size_t kernarg_bytes = 0;
+  int device = -1;
   unsigned blocks = 0, wg = 0;
 };
 
@@ -362,8 +411,83 @@ int pgm_dq_destroy(void *handle) {
   return rc;
 }
 
-// load a launch's code object into an HSA executable of the queue's agent, find its kernel, and write
-// its explicit arguments into a device-memory kernarg segment (drains the device first: inputs HIP
+// the launch's code object loaded for the queue's agent (pgm_share.h: loaded on a miss only) with its
+// kernel's symbol, cached per entry
+static int acquire_code(DirectQueue *dq, const pgmi_jit_launch &L, const char *co, size_t co_n, const char *what,
+                        CodeRegistry::Entry **out, KernelInfo *ki) {
+  CodeRegistry &reg = code_registry();
+  const hsa_agent_t agent = dq->agent;
+  const hsa_profile_t profile = dq->profile;
+  int rc = reg.acquire(agent.handle, co, co_n, [&](CodeRegistry::Entry &e) {
+    LoadedCode &c = e.value;
+    c.agent = agent;
+    auto bail = [&](int rc2) {
+      unload_code(e);
+      return rc2;
+    };
+    if (hsa_init() != HSA_STATUS_SUCCESS) return bail(fail(PGM_EDEVICE, "%s: hsa_init failed", what));
+    c.hsa_up = true;
+    // the reader reads the entry's own copy of the blob, which lives as long as the executable
+    hsa_status_t st = hsa_code_object_reader_create_from_memory(e.blob.data(), e.blob.size(), &c.reader);
+    if (st != HSA_STATUS_SUCCESS) return bail(fail(PGM_EDEVICE, "%s: code object reader: %s", what, hsa_msg(st)));
+    c.have_reader = true;
+    st = hsa_executable_create_alt(profile, HSA_DEFAULT_FLOAT_ROUNDING_MODE_DEFAULT, nullptr, &c.exec);
+    if (st != HSA_STATUS_SUCCESS) return bail(fail(PGM_EDEVICE, "%s: executable: %s", what, hsa_msg(st)));
+    c.have_exec = true;
+    st = hsa_executable_load_agent_code_object(c.exec, agent, c.reader, nullptr, nullptr);
+    if (st == HSA_STATUS_SUCCESS) st = hsa_executable_freeze(c.exec, nullptr);
+    if (st != HSA_STATUS_SUCCESS) return bail(fail(PGM_EDEVICE, "%s: load code object: %s", what, hsa_msg(st)));
+    return (int)PGM_OK;
+  }, out);
+  if (rc != PGM_OK) return rc;
+  LoadedCode &c = (*out)->value;
+  std::lock_guard<std::mutex> lk(reg.mutex());
+  auto hit = c.kernels.find(L.kernel);
+  if (hit == c.kernels.end()) {
+    hsa_executable_symbol_t sym;
+    const std::string kd = std::string(L.kernel) + ".kd";
+    hsa_status_t st = hsa_executable_get_symbol_by_name(c.exec, kd.c_str(), &c.agent, &sym);
+    if (st != HSA_STATUS_SUCCESS) st = hsa_executable_get_symbol_by_name(c.exec, L.kernel, &c.agent, &sym);
+    if (st != HSA_STATUS_SUCCESS) return fail(PGM_EDEVICE, "%s: kernel %s not found: %s", what, L.kernel, hsa_msg(st));
+    KernelInfo k;
+    (void)hsa_executable_symbol_get_info(sym, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_OBJECT, &k.kernel_object);
+    (void)hsa_executable_symbol_get_info(sym, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_GROUP_SEGMENT_SIZE, &k.group_bytes);
+    (void)hsa_executable_symbol_get_info(sym, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_PRIVATE_SEGMENT_SIZE, &k.private_bytes);
+    (void)hsa_executable_symbol_get_info(sym, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_KERNARG_SEGMENT_SIZE, &k.kernarg_bytes);
+    hit = c.kernels.emplace(L.kernel, k).first;
+  }
+  *ki = hit->second;
+  return PGM_OK;
+}
+
+// a zero-filled kernarg segment of the device's slab (grown by whole chunks of device memory)
+static hipError_t take_kernarg(int device, size_t bytes, void **out) {
+  DeviceSlab &s = kernarg_slabs();
+  hipError_t e = hipSuccess;
+  {
+    std::lock_guard<std::mutex> lk(s.mu);
+    *out = s.by_device[device].take(bytes, [&](size_t n) -> void * {
+      int cur = -1;
+      void *p = nullptr;
+      e = hipGetDevice(&cur);
+      if (e == hipSuccess && cur != device) e = hipSetDevice(device);
+      if (e == hipSuccess) e = hipMalloc(&p, n);
+      if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
+      return e == hipSuccess ? p : nullptr;
+    });
+  }
+  if (!*out) return e != hipSuccess ? e : hipErrorOutOfMemory;
+  return hipMemset(*out, 0, bytes);
+}
+
+static void give_kernarg(int device, void *p, size_t bytes) {
+  DeviceSlab &s = kernarg_slabs();
+  std::lock_guard<std::mutex> lk(s.mu);
+  (void)s.by_device[device].give(p, bytes);
+}
+
+// find (or load) a launch's code object as an HSA executable of the queue's agent and its kernel, and
+// write its explicit arguments into a device-memory kernarg segment (drains the device first: inputs HIP
 // produced are complete)
 static int bind_launch(DirectQueue *dq, const pgmi_jit_launch &L, const char *what, void **out) {
   if (L.blocks == 0 || L.wg == 0) return fail(PGM_EINVAL, "%s: empty launch", what);
@@ -376,43 +500,30 @@ static int bind_launch(DirectQueue *dq, const pgmi_jit_launch &L, const char *wh
   DirectBound *db = new (std::nothrow) DirectBound;
   if (!db) return fail(PGM_ENOMEM, "%s: out of host memory", what);
   db->dq = dq;
+  db->device = dq->device;
   db->blocks = L.blocks;
   db->wg = L.wg;
   db->rel_scope = (uint16_t)(L.write_through ? HSA_FENCE_SCOPE_NONE : HSA_FENCE_SCOPE_AGENT);
-  bool reader = false, exec = false;
   auto bail = [&](int rc2) {
-    if (exec) (void)hsa_executable_destroy(db->exec);
-    if (reader) (void)hsa_code_object_reader_destroy(db->reader);
-    if (db->kernarg) (void)hipFree(db->kernarg);
+    if (db->kernarg) give_kernarg(db->device, db->kernarg, db->kernarg_bytes);
+    if (db->code) (void)code_registry().release(db->code, unload_code);
     delete db;
     return rc2;
   };
-  hsa_status_t st = hsa_code_object_reader_create_from_memory(co, co_n, &db->reader);
-  if (st != HSA_STATUS_SUCCESS) return bail(fail(PGM_EDEVICE, "%s: code object reader: %s", what, hsa_msg(st)));
-  reader = true;
-  st = hsa_executable_create_alt(dq->profile, HSA_DEFAULT_FLOAT_ROUNDING_MODE_DEFAULT, nullptr, &db->exec);
-  if (st != HSA_STATUS_SUCCESS) return bail(fail(PGM_EDEVICE, "%s: executable: %s", what, hsa_msg(st)));
-  exec = true;
-  st = hsa_executable_load_agent_code_object(db->exec, dq->agent, db->reader, nullptr, nullptr);
-  if (st == HSA_STATUS_SUCCESS) st = hsa_executable_freeze(db->exec, nullptr);
-  if (st != HSA_STATUS_SUCCESS) return bail(fail(PGM_EDEVICE, "%s: load code object: %s", what, hsa_msg(st)));
-  hsa_executable_symbol_t sym;
-  const std::string kd = std::string(L.kernel) + ".kd";
-  st = hsa_executable_get_symbol_by_name(db->exec, kd.c_str(), &dq->agent, &sym);
-  if (st != HSA_STATUS_SUCCESS) st = hsa_executable_get_symbol_by_name(db->exec, L.kernel, &dq->agent, &sym);
-  if (st != HSA_STATUS_SUCCESS) return bail(fail(PGM_EDEVICE, "%s: kernel %s not found: %s", what, L.kernel, hsa_msg(st)));
-  uint32_t ka_size = 0;
-  (void)hsa_executable_symbol_get_info(sym, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_OBJECT, &db->kernel_object);
-  (void)hsa_executable_symbol_get_info(sym, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_GROUP_SEGMENT_SIZE, &db->group_bytes);
-  (void)hsa_executable_symbol_get_info(sym, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_PRIVATE_SEGMENT_SIZE, &db->private_bytes);
-  (void)hsa_executable_symbol_get_info(sym, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_KERNARG_SEGMENT_SIZE, &ka_size);
+  KernelInfo ki;
+  const int rc = acquire_code(dq, L, co, co_n, what, &db->code, &ki);
+  if (rc != PGM_OK) return bail(rc);
+  db->kernel_object = ki.kernel_object;
+  db->group_bytes = ki.group_bytes;
+  db->private_bytes = ki.private_bytes;
+  const uint32_t ka_size = ki.kernarg_bytes;
   if (!db->kernel_object) return bail(fail(PGM_EDEVICE, "%s: null kernel object", what));
   if (ka_size > L.args_size + 64)  // the kernel reads implicit arguments this path does not provide
     return bail(fail(PGM_EDEVICE, "%s: kernarg segment %u B > %zu B of explicit arguments", what, ka_size,
                      L.args_size));
   const size_t bytes = std::max<size_t>(256, (std::max<size_t>(ka_size, L.args_size) + 63) & ~(size_t)63);
-  hipError_t e = hipMalloc(&db->kernarg, bytes);
-  if (e == hipSuccess) e = hipMemset(db->kernarg, 0, bytes);
+  db->kernarg_bytes = bytes;
+  hipError_t e = take_kernarg(db->device, bytes, &db->kernarg);
   if (e == hipSuccess) e = hipMemcpy(db->kernarg, L.args, L.args_size, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipDeviceSynchronize();  // inputs produced on HIP streams are complete
   if (e != hipSuccess) {
@@ -740,11 +851,19 @@ int pgm_dq_bound_destroy(void *dbound) {
   DirectBound *db = (DirectBound *)dbound;
   if (!db) return PGM_OK;
   const int rc = pgm_dq_sync(db->dq);  // no dispatch of this kernel may still be in flight
-  (void)hsa_executable_destroy(db->exec);
-  (void)hsa_code_object_reader_destroy(db->reader);
-  if (db->kernarg) (void)hipFree(db->kernarg);
+  if (db->kernarg) give_kernarg(db->device, db->kernarg, db->kernarg_bytes);
+  (void)code_registry().release(db->code, unload_code);  // the last sharer unloads the code object
   delete db;
   return rc;
+}
+
+int pgm_dq_bound_info(void *dbound, uint64_t *kernel_object, uint64_t *kernarg, int32_t *sharers) {
+  const DirectBound *db = (const DirectBound *)dbound;
+  if (!db) return fail(PGM_EINVAL, "dq_bound_info: null handle");
+  if (kernel_object) *kernel_object = db->kernel_object;
+  if (kernarg) *kernarg = (uint64_t)(uintptr_t)db->kernarg;
+  if (sharers) *sharers = (int32_t)code_registry().refs(db->code);
+  return PGM_OK;
 }
 
 }  // extern "C"

@@ -1090,6 +1090,16 @@ class DirectGroup:
         self.queue.sync()
 
 
+def bound_info(handle):
+    """(kernel object, kernarg device address, sharers of the loaded code object) of a pgm_dq_bind_*
+    handle (pgm_dq_bound_info)."""
+    import ctypes
+
+    ko, ka, n = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int32()
+    N.check(N.lib().pgm_dq_bound_info(handle, ctypes.byref(ko), ctypes.byref(ka), ctypes.byref(n)), "dq_bound_info")
+    return ko.value, ka.value, n.value
+
+
 class DirectRows:
     """A bound row-plan launch re-bound to a DirectQueue (pgm_dq_bind_rows / pgm_dq_launch)."""
 
@@ -1118,6 +1128,11 @@ class DirectRows:
 
     def sync(self):
         self.queue.sync()
+
+    def info(self):
+        """(kernel object, kernarg device address, bound launches sharing the loaded code object)
+        (pgm_dq_bound_info)."""
+        return bound_info(self._h)
 
     def __del__(self):
         h = getattr(self, "_h", None)
