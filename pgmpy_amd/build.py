@@ -11,10 +11,16 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "csrc", "pgmhip.hip")
-SRC_DQ = os.path.join(HERE, "csrc", "pgmdq.cpp")  # direct AQL dispatch (host code, HSA runtime)
-SRC_PM = os.path.join(HERE, "csrc", "pgmpm.cpp")  # plan-specialised batched-BP steps (host code, hipRTC)
-SRC_HOST = os.path.join(HERE, "csrc", "pgmhost.cpp")  # DataFrame ingestion helpers (host threads only)
+CSRC = os.path.join(HERE, "csrc")
+# one hipcc command: the .hip units carry the kernels, the .cpp units are host code
+SOURCES = [os.path.join(CSRC, f) for f in (
+    "pgmhip.hip",        # primitive factor kernels + their C-ABI, the error string
+    "pgmrows.hip",       # fused row plan: kernels + C-ABI
+    "pgmrows_plan.cpp",  # fused row plan: plan compiler + generator of the specialised source (host only)
+    "pgmdq.cpp",         # direct AQL dispatch (host code, HSA runtime)
+    "pgmpm.cpp",         # plan-specialised batched-BP steps (host code, hipRTC)
+    "pgmhost.cpp",       # DataFrame ingestion helpers (host threads only)
+)]
 INC = os.path.join(ROOT, "include")
 OUT = os.path.join(HERE, "lib", "libpgmhip.so")
 ARCH = "gfx950"
@@ -29,14 +35,14 @@ def hipcc():
 
 def build(force=False, verbose=True, out=OUT, defines=()):
     """defines: extra -D macros (tools only, e.g. PGM_ROWS_TIMELINE into lib/libpgmhip_timeline.so)."""
-    deps = [SRC, SRC_DQ, SRC_PM, SRC_HOST, os.path.join(HERE, "csrc", "pgm_internal.h"),
-            os.path.join(HERE, "csrc", "pgm_share.h"), os.path.join(INC, "pgmhip.h")]
+    # every file of csrc/ (sources and private headers) and the public header
+    deps = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [os.path.join(INC, "pgmhip.h")]
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
         return out
     os.makedirs(os.path.dirname(out), exist_ok=True)
     tmp = out + ".tmp"
     cmd = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared",
-           "-Wno-unused-result", "-I", INC] + [f"-D{d}" for d in defines] + ["-o", tmp, SRC, SRC_DQ, SRC_PM, SRC_HOST, "-lhiprtc", "-lhsa-runtime64"]
+           "-Wno-unused-result", "-I", INC] + [f"-D{d}" for d in defines] + ["-o", tmp] + SOURCES + ["-lhiprtc", "-lhsa-runtime64"]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)

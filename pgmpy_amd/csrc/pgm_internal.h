@@ -1,4 +1,4 @@
-// pgm_internal.h — private interface between pgmhip.hip (kernels, C-ABI), pgmdq.cpp (direct AQL
+// pgm_internal.h — private interface between pgmhip.hip / pgmrows.hip (kernels, C-ABI), pgmdq.cpp (direct AQL
 // dispatch) and pgmpm.cpp (plan-specialised batched-BP steps).  Not part of the C-ABI of
 // include/pgmhip.h.
 #pragma once

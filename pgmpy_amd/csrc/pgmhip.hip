@@ -1,39 +1,32 @@
-// pgmhip.hip — gfx950 (MI355X / CDNA4) kernels + C-ABI of the discrete-factor engine.
+// pgmhip.hip — gfx950 (MI355X / CDNA4) primitive factor kernels + their C-ABI.
 //
 // Built for gfx950 only:  hipcc --offload-arch=gfx950 -O3 -fPIC -shared
 // (pgmpy_amd/build.py).  Declarations and the reference call site each entry
 // point replaces: include/pgmhip.h.  Design, data layout and the roofline of
-// every kernel: DESIGN.md.
+// every kernel: DESIGN.md.  The fused row plan (k_rows, pgm_rows_*) is pgmrows.hip.
 //
 // Kernels
 //   k_contract / k_contract_final  generic strided broadcast-combine + axis reduce (HBM-bound)
 //   k_gather                       batched evidence reduce (gather by per-row state codes)
 //   k_indicator                    0/1 evidence indicators (BP findings)
 //   k_argmax                       first-index argmax per row
-//   k_rows                         fused per-row plan: reduce -> sum-product -> normalize ->
-//                                  marginals / joint / MAP, one lane per evidence row
+// also: n-ary product (+ marginal), batched small jobs, the dense pairwise step (gemm), evidence
+// ingestion (codes_*), and the library's one error string (pgm_last_error, pgmi_fail / pgmi_failf)
 #include <hip/hip_runtime.h>
-#include <hip/hiprtc.h>
 
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
-
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include "pgmhip.h"
 #include "pgm_internal.h"
+#include "pgm_hip_common.h"
 
 #define PGM_ABI_VERSION 24  // 24: pgm_contract_info (host-only query of the planned contraction kernel; the launcher takes its choice from the same function); 23: pgm_batch_add_contract_n (n-ary contraction jobs), pgm_dq_timer_dispatch_times, pgm_host_scan_* / pgm_host_lut_map_u8; 22: pgm_dq_bind_pm / pgm_dq_run_chain / pgm_dq_profiling; 21: pgm_batch_specialise; 20: pgm_batch_info and the grid-barrier levelled batch removed (levels: single-workgroup mode only); 19: pgm_stream_sync_spin; 18: pgm_batch_set_mode (single-workgroup levelled batch), pgm_batch_blocks; 17: pgm_rows_shard_run (rows sharded over several GPUs from host buffers); 16: pgm_rows_ring_start_ready; 15: pgm_batch_add_level / pgm_batch_info (levelled batch), pgm_memcpy_d2h_async; 14: pgm_rows_ring_* (resident ring of row batches); 13: pgm_dq_timer_dispatch_stats, pgm_rows_bound_kernel; 12: pgm_dq_launch_group, pgm_dq_timer_stop_ticks, PGM_ROWS_FLOOR; 11: pgm_product_n_marginal_bind / pgm_pm_bound_*; 10: pgm_dq_* direct AQL dispatch, pgm_codes_remap; 9: gemm lane_order, batch product_n / indicator
 
@@ -50,16 +43,6 @@ static int fail(int code, const char *fmt, ...) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                                    \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) {                                                              \
-      (void)hipGetLastError();                                                           \
-      return fail(e_ == hipErrorOutOfMemory ? PGM_ENOMEM : PGM_EDEVICE, "%s: %s", #expr, \
-                  hipGetErrorString(e_));                                                \
-    }                                                                                    \
-  } while (0)
-
 // debugging aid (PGM_STALE_PROBE=1): report a pending HIP error left by an earlier call when a C-ABI
 // entry point starts, so a launch check is not blamed for someone else's error
 void pgmi_stale_probe(const char *fn) {
@@ -68,8 +51,6 @@ void pgmi_stale_probe(const char *fn) {
   const hipError_t e = hipPeekAtLastError();
   if (e != hipSuccess) fprintf(stderr, "pgmhip: pending HIP error at entry of %s: %s\n", fn, hipGetErrorString(e));
 }
-
-static inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ----------------------------------------------------------------------------- fast division
 // n / d for n < 2^31 with one mul-hi and one shift (Granlund-Montgomery round-up method).
@@ -580,8 +561,6 @@ static void coalesce(Dims &d, int nops) {
   d = o;
 }
 
-static constexpr bool g_no_rows2 = false;  // (r01's 8-B-only row paths: 0.54-0.70x the 16-B rate)
-
 static const uint64_t kTargetThreads = 256ull * 2048;  // 256 CUs x 32 waves x 64 lanes
 
 struct ContractLaunch {
@@ -723,9 +702,10 @@ static int plan_contract(const pgm_contract_desc *d, ContractLaunch &L) {
   return PGM_OK;
 }
 
-// two-rows-per-lane eligibility of a row-mode COPY contraction (A read, C written)
+// two-rows-per-lane eligibility of a row-mode COPY contraction (A read, C written); r01's 8-B-only row
+// paths ran at 0.54-0.70x the 16-B rate
 static bool rows2_ok(const ContractK &k, const double *A, const double *C) {
-  if (g_no_rows2 || !k.row_mode || k.nk < 1) return false;
+  if (!k.row_mode || k.nk < 1) return false;
   const int kx = k.nk - 1;
   if (k.kdiv[kx].d % 2 || k.ksa[kx] != 1 || k.ksc[kx] != 1) return false;
   if (((uintptr_t)A & 15) || ((uintptr_t)C & 15)) return false;
@@ -1132,7 +1112,7 @@ int pgmi_plan_product_marg(const pgm_productn_desc *d, const double *const *ops,
   if (!d || !ops || !marg_s || !M) return fail(PGM_EINVAL, "product_n_marginal: null argument");
   if (d->n_ops < 1 || d->n_ops > PMAX || d->n_keep < 1 || d->n_keep > PGM_MAX_DIMS)
     return fail(PGM_EINVAL, "product_n_marginal: n_ops %d / n_keep %d out of range", d->n_ops, d->n_keep);
-  if (g_no_rows2 || d->n_ops > MOPS || d->n_keep < 2) return 0;
+  if (d->n_ops > MOPS || d->n_keep < 2) return 0;
   memset(&k, 0, sizeof k);
   const int last = d->n_keep - 1;
   const int64_t NX = d->keep_card[last];
@@ -1905,1074 +1885,6 @@ __global__ __launch_bounds__(256) void k_sample_joint(const double *__restrict__
   out[r] = (int32_t)(idx < P ? idx : P - 1);
 }
 
-// ----------------------------------------------------------------------------- fused row plan
-// One workgroup owns 64 evidence rows (one per lane) for RG consecutive row groups; its waves split
-// the plan's independent components (wave w takes components w, w+W, ...), so every descriptor
-// read, loop bound and branch is wave-uniform (scalar) and a row's work is spread over W
-// wavefronts.  A wave loads only its components' evidence codes (all in flight at once) and
-// stages only their CPT values into LDS.  Components meet once per row group through LDS: masses
-// (impossible evidence makes every marginal NaN), MAP index digits and MAP gaps.
-//
-// Descriptors live in device memory as packed structs (one s_load_dwordx16 per component, one
-// s_load_dwordx4 per evidence term).  Table-driven components: for every entry e of a component's
-// (query x hidden) index space the host precomputes each factor's offset (tab[off_base + e*nf + j]),
-// the marginal rows each query dim accumulates into (tab[marg_base + qi*nq + i]) and the entry's MAP
-// index digit (tab[map_base + qi]).  Affine components (one query dim, no hidden dim) need no
-// table: factor j sits at base_j + s * fstride[j] for query state s.
-struct RowsComp {
-  int32_t nf, nt, P, H;
-  int32_t simple, mstride, q_lo, q_hi;
-  int32_t off_base, marg_base, map_base, ev_lo;  // ev_lo: first evidence term (n_ev when none)
-  int32_t val_lo, val_hi, marg0, nq;              // marg0: marginal row of the (affine) query dim
-  int32_t fbase[PGM_ROWS_MAX_FAC];
-  int32_t fstride[PGM_ROWS_MAX_FAC];
-  // affine fast kernel: evidence terms folded into per-slot strides (term j adds code_j * aS[j][k]
-  // to factor slot k), padded to 8 terms (stride 0, card 256, a real column)
-  int32_t a_S[8][4];
-  int32_t a_col[8], a_card[8];
-};
-struct RowsTerm {
-  int32_t col, stride, card, slot;  // evidence column, stride in its factor, cardinality, factor slot
-};
-struct RowsK {
-  int32_t n_values, n_marg, n_joint, n_comp;  // n_values includes the trailing 1.0 (index one_idx)
-  int32_t n_waves, terms_off, tab_off, one_idx;  // offsets (in int32) into the descriptor buffer
-  int32_t q_marg_off[PGM_ROWS_MAX_LOOP], q_card[PGM_ROWS_MAX_LOOP];
-};
-
-struct RowsHandle {
-  RowsK k;
-  int max_nf, max_nt;
-  bool any_table, all_affine;
-  double *d_values;
-  int32_t *d_desc;
-  // plan-specialised kernel (hipRTC): generated at create for all-affine plans, compiled on first use
-  std::string jit_src;
-  std::mutex jit_mu;
-  int jit_state = 0;  // 0 not compiled, 1 ready, -1 unavailable (the AOT kernels run instead)
-  hipModule_t jit_mod = nullptr;
-  hipFunction_t jit_fn = nullptr;
-  hipFunction_t jit_fn2 = nullptr;  // two rows per thread
-  hipFunction_t jit_fn_floor = nullptr;  // PGM_ROWS_FLOOR: the same dispatch's loads + stores only
-  hipFunction_t jit_fn_floor2 = nullptr;  // ... of the two-rows-per-thread dispatch
-  hipFunction_t jit_fn_ring = nullptr;    // the resident ring kernel (pgm_rows_ring_*)
-  std::vector<char> jit_code;         // the compiled code object (the direct AQL path loads it again)
-  bool jit_write_through = false;     // its output stores are write-through (jit_store() == 2)
-  int device = 0;                     // the HIP device current at create (its buffers / module live there)
-  int n_cols = 0;                     // 1 + the largest evidence column the plan reads (0: none)
-  std::vector<int> cols;              // the evidence columns the plan reads, ascending
-  // pgm_rows_shard_run's resources on this handle's device, created on first use and kept until the
-  // handle is destroyed: two streams, each with its own grow-only device chunk buffer (codes of the
-  // columns the plan reads, outputs, error flag) and a pinned error word, so consecutive chunks
-  // alternate between them (chunk c + 1's copy-in and pass overlap chunk c's copy-out)
-  struct ShardSide {
-    hipStream_t s = nullptr;
-    char *buf = nullptr;
-    size_t cap = 0;
-    int32_t *h_err = nullptr;
-  };
-  ShardSide shard[2];
-  std::mutex shard_mu;  // one pgm_rows_shard_run shard at a time per handle
-};
-
-template <bool VL, bool AL, int MAXFC, int MAXT>
-__global__ __launch_bounds__(64 * PGM_ROWS_MAX_COMP) void k_rows(
-    const RowsK p, const double *__restrict__ gvals, const int32_t *__restrict__ desc,
-    const uint8_t *__restrict__ codes, int64_t ld_codes, int64_t row0, int64_t n_rows, int32_t mode, int32_t RG,
-    double *__restrict__ marg, double *__restrict__ joint, int64_t ld_out, int32_t *__restrict__ map,
-    double *__restrict__ gap, int32_t *__restrict__ err) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  const int lane = threadIdx.x & 63;
-  const int c = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // this wave's component
-  const int NC = p.n_comp;
-  const RowsComp &cd = ((const RowsComp *)desc)[c];
-  const RowsTerm *__restrict__ tt = (const RowsTerm *)(desc + p.terms_off) + cd.ev_lo;
-  const int32_t *__restrict__ tab = desc + p.tab_off;
-  double *svals = lds;
-  double *xmass = lds + (VL ? ((p.n_values + 1) & ~1) : 0);  // [NC][64]
-  double *xgap = xmass + NC * 64;                              // [NC][64]
-  int32_t *xmap = (int32_t *)(xgap + NC * 64);                 // [NC][64]
-  double *sacc = (double *)(xmap + NC * 64);                   // [n_marg][64]
-  const bool do_marg = (mode & PGM_ROWS_MARGINALS) != 0;
-  const bool do_joint = (mode & PGM_ROWS_JOINT) != 0;
-  const bool do_map = (mode & (PGM_ROWS_MAP | PGM_ROWS_MAPGAP)) != 0;
-  const int nf = cd.nf, nq = cd.nq, nt = cd.nt;
-  const uint32_t P = cd.P, H = cd.H;
-  auto val = [&](int32_t i) -> double {
-    if constexpr (VL) return svals[i];
-    else return gvals[i];
-  };
-  // stage this component's CPT values once per workgroup (no other wave reads them: no barrier)
-  if constexpr (VL) {
-    if (lane == 0) svals[p.one_idx] = 1.0;
-    for (int i = cd.val_lo + lane; i < cd.val_hi; i += 64) svals[i] = gvals[i];
-  }
-  // evidence codes of row group g (MAXT <= 8: padded terms, static descriptor offsets)
-  constexpr int NT = MAXT <= 8 ? MAXT : 1;
-  auto load_codes = [&](int g, uint32_t (&code)[NT]) {
-    const int64_t r = ((int64_t)blockIdx.x * RG + g) * 64 + lane;
-    const uint8_t *crow = codes + row0 + (r < n_rows ? r : 0);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) code[j] = crow[(int64_t)tt[j].col * ld_codes];
-  };
-  uint32_t nxt[NT];
-  if (MAXT <= 8 && nt > 0) load_codes(0, nxt);
-  for (int g = 0; g < RG; ++g) {
-    const int64_t r = ((int64_t)blockIdx.x * RG + g) * 64 + lane;
-    const bool live = r < n_rows;
-    auto acc = [&](int32_t t) -> double & {
-      if constexpr (AL) return sacc[t * 64 + lane];
-      else return marg[(int64_t)t * ld_out + r];
-    };
-    int32_t cb[MAXFC];  // slots >= nf point at the constant 1.0 (fbase = one_idx, fstride = 0)
-#pragma unroll
-    for (int j = 0; j < MAXFC; ++j) cb[j] = cd.fbase[j];
-    bool bad = false;
-    if (nt == 0) {
-      // no evidence in this component: nothing to load (codes may have no columns at all)
-    } else if constexpr (MAXT <= 8) {
-      uint32_t code[NT];
-#pragma unroll
-      for (int j = 0; j < NT; ++j) code[j] = nxt[j];
-      if (g + 1 < RG) load_codes(g + 1, nxt);  // next row group's codes in flight during this one
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const RowsTerm &t = tt[j];
-        const bool oob = code[j] >= (uint32_t)t.card;
-        bad |= oob;
-        const int32_t w = oob ? 0 : (int32_t)code[j] * t.stride;
-#pragma unroll
-        for (int k = 0; k < MAXFC; ++k) cb[k] += (k == t.slot) ? w : 0;
-      }
-    } else {
-      const uint8_t *crow = codes + row0 + (live ? r : 0);
-      for (int j = 0; j < nt; ++j) {
-        const RowsTerm &t = tt[j];
-        uint32_t cv = crow[(int64_t)t.col * ld_codes];
-        if (cv >= (uint32_t)t.card) {
-          bad = true;
-          cv = 0;
-        }
-        const int32_t w = (int32_t)cv * t.stride;
-#pragma unroll
-        for (int k = 0; k < MAXFC; ++k) cb[k] += (k == t.slot) ? w : 0;
-      }
-    }
-    if (bad && live && err) atomicOr(err, 1);
-    double mass = 0.0, best = -1.0, second = -1.0;
-    int32_t best_map = 0;
-    if (cd.simple) {
-      // affine: states [0, RC) stay in registers (branch-free clamped loads, all LDS reads of
-      // the pass in flight at once); states >= RC are recomputed in the write pass
-      const int32_t ms = cd.mstride;
-      constexpr int RC = 8;
-      double pc[RC];
-      const int32_t plast = (int32_t)P - 1;
-#pragma unroll
-      for (int qs = 0; qs < RC; ++qs) {
-        const int32_t q = qs < plast ? qs : plast;
-        double prod = val(cb[0] + q * cd.fstride[0]);
-#pragma unroll
-        for (int j = 1; j < MAXFC; ++j) prod *= val(cb[j] + q * cd.fstride[j]);
-        pc[qs] = prod;
-      }
-      auto visit = [&](uint32_t qs, double prod) {
-        mass += prod;
-        if (do_joint && live) joint[(int64_t)qs * ms * ld_out + r] = prod;
-        if (do_map) {
-          if (prod > best) {
-            second = best;
-            best = prod;
-            best_map = (int32_t)qs * ms;
-          } else if (prod > second) {
-            second = prod;
-          }
-        }
-      };
-#pragma unroll
-      for (int qs = 0; qs < RC; ++qs)
-        if ((uint32_t)qs < P) visit(qs, pc[qs]);
-      for (uint32_t qs = RC; qs < P; ++qs) {
-        double prod = val(cb[0] + (int32_t)qs * cd.fstride[0]);
-#pragma unroll
-        for (int j = 1; j < MAXFC; ++j) prod *= val(cb[j] + (int32_t)qs * cd.fstride[j]);
-        visit(qs, prod);
-      }
-      if (do_marg && nq && live) {  // normalised marginal streamed straight to HBM
-        const double inv = 1.0 / mass;
-        double *out = marg + (int64_t)cd.marg0 * ld_out + r;
-#pragma unroll
-        for (int qs = 0; qs < RC; ++qs)
-          if ((uint32_t)qs < P) __builtin_nontemporal_store(pc[qs] * inv, out + (int64_t)qs * ld_out);
-        for (uint32_t qs = RC; qs < P; ++qs) {
-          double prod = val(cb[0] + (int32_t)qs * cd.fstride[0]);
-#pragma unroll
-          for (int j = 1; j < MAXFC; ++j) prod *= val(cb[j] + (int32_t)qs * cd.fstride[j]);
-          __builtin_nontemporal_store(prod * inv, out + (int64_t)qs * ld_out);
-        }
-      }
-    } else if (live) {
-      const int32_t *toff = tab + cd.off_base;
-      const int32_t *tmarg = tab + cd.marg_base;
-      const int32_t *tmap = tab + cd.map_base;
-      if (do_marg && nq > 1) {
-        for (int q = cd.q_lo; q < cd.q_hi; ++q)
-          for (int s = 0; s < p.q_card[q]; ++s) acc(p.q_marg_off[q] + s) = 0.0;
-      }
-      uint32_t e = 0;
-#pragma unroll 2
-      for (uint32_t qi = 0; qi < P; ++qi) {
-        double v = 0.0;
-        if (H == 1) {  // no hidden dims: one product per query entry
-          const int32_t *o = toff + qi * nf;
-          double prod = 1.0;
-#pragma unroll
-          for (int j = 0; j < MAXFC; ++j)
-            if (j < nf) prod *= val(cb[j] + o[j]);
-          v = prod;
-        } else {
-          for (uint32_t hi = 0; hi < H; ++hi, ++e) {
-            const int32_t *o = toff + e * nf;
-            double prod = 1.0;
-#pragma unroll
-            for (int j = 0; j < MAXFC; ++j)
-              if (j < nf) prod *= val(cb[j] + o[j]);
-            v += prod;
-          }
-        }
-        mass += v;
-        if (do_marg) {
-          if (nq == 1) {
-            acc(tmarg[qi]) = v;  // each marginal row is hit exactly once
-          } else {
-            for (int i = 0; i < nq; ++i) acc(tmarg[qi * nq + i]) += v;
-          }
-        }
-        if (do_joint) joint[(int64_t)tmap[qi] * ld_out + r] = v;
-        if (do_map) {
-          if (v > best) {
-            second = best;
-            best = v;
-            best_map = tmap[qi];
-          } else if (v > second) {
-            second = v;
-          }
-        }
-      }
-      if (do_marg && nq > 0) {  // component marginals normalised by the component mass
-        const double inv = 1.0 / mass;
-        for (int q = cd.q_lo; q < cd.q_hi; ++q)
-          for (int s = 0; s < p.q_card[q]; ++s) {
-            const int a = p.q_marg_off[q] + s;
-            if constexpr (AL) marg[(int64_t)a * ld_out + r] = acc(a) * inv;
-            else acc(a) *= inv;
-          }
-      }
-    }
-    if (NC > 1 || do_map) {
-      xmass[c * 64 + lane] = mass;
-      if (do_map) {
-        xmap[c * 64 + lane] = best_map;
-        xgap[c * 64 + lane] = (P > 1) ? (best > 0.0 ? (best - (second < 0.0 ? 0.0 : second)) / best : 0.0) : 1.0;
-      }
-    }
-    if (NC > 1) __syncthreads();
-    if (live) {
-      double z = mass;
-      if (NC > 1) {
-        z = 1.0;
-        for (int c2 = 0; c2 < NC; ++c2) z *= xmass[c2 * 64 + lane];
-      }
-      // impossible evidence (zero total mass): every marginal is 0/0 = NaN and np.argmax gives 0
-      const bool dead = !(z > 0.0);
-      if (do_marg && dead) {
-        const double nan = __builtin_nan("");
-        for (int q = cd.q_lo; q < cd.q_hi; ++q)
-          for (int s = 0; s < p.q_card[q]; ++s) marg[(int64_t)(p.q_marg_off[q] + s) * ld_out + r] = nan;
-      }
-      if (do_joint && c == 0) {  // single-component plans only
-        const double inv = 1.0 / z;
-        for (int q = 0; q < p.n_joint; ++q) {
-          double *j = joint + (int64_t)q * ld_out + r;
-          *j = dead ? __builtin_nan("") : *j * inv;
-        }
-      }
-      if (do_map && c == 0) {
-        int32_t m = 0;
-        double mg = 1.0;
-        for (int c2 = 0; c2 < NC; ++c2) {
-          m += xmap[c2 * 64 + lane];
-          mg = fmin(mg, xgap[c2 * 64 + lane]);
-        }
-        if (map) map[r] = dead ? 0 : m;
-        if (gap && (mode & PGM_ROWS_MAPGAP)) gap[r] = dead ? 0.0 : mg;
-      }
-    }
-    if (NC > 1 && g + 1 < RG) __syncthreads();  // the exchange slots are reused by the next row group
-  }
-}
-
-// workgroup barrier for LDS-only exchanges: waits for this wave's LDS traffic, not for its global
-// loads/stores (__syncthreads' release fence would wait for every outstanding store to be acked)
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// All-affine plans (every component one query dim, no hidden dim, <= 4 factors, <= 8 evidence
-// terms: the common batched-predict shape, e.g. munin C3).  Same work split as k_rows, but each
-// wave loads its component's descriptor into registers once, folds evidence with multiply-adds
-// against host-precomputed per-slot strides, and carries the MAP bookkeeping only when asked.
-// Latency shape (one row group per wave at 100k rows): descriptor -> {codes, CPT staging} in
-// flight together (staging issues every load before any LDS write) -> products -> LDS-only
-// exchange of component masses -> stores.  PGM_ROWS_TIMELINE builds add per-wave s_memrealtime
-// stamps (tools/rows_timeline.py).
-template <bool VL, int NF, int NT, bool MAP>
-__global__ __launch_bounds__(64 * PGM_ROWS_MAX_COMP) void k_rows_affine(
-    const RowsK p, const double *__restrict__ gvals, const int32_t *__restrict__ desc,
-    const uint8_t *__restrict__ codes, int64_t ld_codes, int64_t row0, int64_t n_rows, int32_t mode, int32_t RG,
-    double *__restrict__ marg, int64_t ld_out, int32_t *__restrict__ map, double *__restrict__ gap,
-    int32_t *__restrict__ err) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-#ifdef PGM_ROWS_TIMELINE
-  const uint64_t t_entry = __builtin_amdgcn_s_memrealtime();
-#endif
-  const int lane = threadIdx.x & 63;
-  const int c = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // this wave's component
-  const int NC = p.n_comp;
-  const RowsComp &cd = ((const RowsComp *)desc)[c];
-  double *svals = lds;
-  double *xmass = lds + (VL ? ((p.n_values + 1) & ~1) : 0);  // [NC][64]
-  double *xgap = xmass + NC * 64;                              // [NC][64] (MAP only)
-  int32_t *xmap = (int32_t *)(xgap + NC * 64);                 // [NC][64] (MAP only)
-  const bool do_marg = (mode & PGM_ROWS_MARGINALS) != 0;
-  // descriptor -> registers (wave-uniform)
-  int32_t fb[NF], fs[NF], S[NT][NF];
-  uint32_t card[NT];
-  int64_t cofs[NT];
-#pragma unroll
-  for (int k = 0; k < NF; ++k) {
-    fb[k] = cd.fbase[k];
-    fs[k] = cd.fstride[k];
-  }
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    card[j] = (uint32_t)cd.a_card[j];
-    cofs[j] = (int64_t)cd.a_col[j] * ld_codes + row0;
-#pragma unroll
-    for (int k = 0; k < NF; ++k) S[j][k] = cd.a_S[j][k];
-  }
-  const int nt = cd.nt;
-  const uint32_t P = (uint32_t)cd.P;
-  const int32_t ms = cd.mstride;
-  double *mrow = marg + (int64_t)cd.marg0 * ld_out;
-  auto val = [&](int32_t i) -> double {
-    if constexpr (VL) return svals[i];
-    else return gvals[i];
-  };
-  auto load_codes = [&](int g, uint32_t (&code)[NT]) {
-    const int64_t r = ((int64_t)blockIdx.x * RG + g) * 64 + lane;
-    const uint8_t *crow = codes + (r < n_rows ? r : 0);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) code[j] = crow[cofs[j]];
-  };
-  // this wave's first 256 CPT values, then the first row group's codes, all in flight before the
-  // LDS writes (vmcnt is in order: the writes wait only for the value loads); larger components
-  // stage the rest in further 256-value batches
-  uint32_t nx[NT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j) nx[j] = 0;
-  const int vlo = cd.val_lo, vhi = cd.val_hi;
-  double t[4];
-  if constexpr (VL) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = vlo + u * 64 + lane;
-      t[u] = gvals[i < vhi ? i : vhi - 1];
-    }
-  }
-  if (nt > 0) load_codes(0, nx);
-  if constexpr (VL) {
-    if (lane == 0) svals[p.one_idx] = 1.0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {  // clamped lanes rewrite the last value with itself: no branches
-      const int i = vlo + u * 64 + lane;
-      svals[i < vhi ? i : vhi - 1] = t[u];
-    }
-    for (int base = vlo + 256; base < vhi; base += 256) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int i = base + u * 64 + lane;
-        t[u] = gvals[i < vhi ? i : vhi - 1];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int i = base + u * 64 + lane;
-        if (i < vhi) svals[i] = t[u];
-      }
-    }
-  }
-#ifdef PGM_ROWS_TIMELINE
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  const uint64_t t_ready = __builtin_amdgcn_s_memrealtime();
-#endif
-  for (int g = 0; g < RG; ++g) {
-    const int64_t r = ((int64_t)blockIdx.x * RG + g) * 64 + lane;
-    const bool live = r < n_rows;
-    uint32_t code[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) code[j] = nx[j];
-    if (nt > 0 && g + 1 < RG) load_codes(g + 1, nx);  // next group's codes in flight during this one
-    int32_t cb[NF];
-#pragma unroll
-    for (int k = 0; k < NF; ++k) cb[k] = fb[k];
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const bool oob = code[j] >= card[j];
-      bad |= oob;
-      const int32_t cj = oob ? 0 : (int32_t)code[j];
-#pragma unroll
-      for (int k = 0; k < NF; ++k) cb[k] += cj * S[j][k];
-    }
-    if (bad && live && err) atomicOr(err, 1);
-    constexpr int RC = 8;
-    double pc[RC];
-    const int32_t plast = (int32_t)P - 1;
-#pragma unroll
-    for (int qs = 0; qs < RC; ++qs) {
-      const int32_t q = qs < plast ? qs : plast;
-      double prod = val(cb[0] + q * fs[0]);
-#pragma unroll
-      for (int k = 1; k < NF; ++k) prod *= val(cb[k] + q * fs[k]);
-      pc[qs] = prod;
-    }
-    double mass = 0.0, best = -1.0, second = -1.0;
-    int32_t best_s = 0;
-    auto visit = [&](uint32_t qs, double prod) {
-      mass += prod;
-      if constexpr (MAP) {
-        if (prod > best) {
-          second = best;
-          best = prod;
-          best_s = (int32_t)qs;
-        } else if (prod > second) {
-          second = prod;
-        }
-      }
-    };
-#pragma unroll
-    for (int qs = 0; qs < RC; ++qs)
-      if ((uint32_t)qs < P) visit(qs, pc[qs]);
-    for (uint32_t qs = RC; qs < P; ++qs) {
-      double prod = val(cb[0] + (int32_t)qs * fs[0]);
-#pragma unroll
-      for (int k = 1; k < NF; ++k) prod *= val(cb[k] + (int32_t)qs * fs[k]);
-      visit(qs, prod);
-    }
-    // the component waves of a row group meet BEFORE any store, through an LDS-only barrier
-    // (no wait for global stores to be acknowledged, as __syncthreads' release fence would)
-    double z = mass;
-    if (NC > 1) {
-      xmass[c * 64 + lane] = mass;
-      if constexpr (MAP) {
-        xmap[c * 64 + lane] = best_s * ms;
-        xgap[c * 64 + lane] = (P > 1) ? (best > 0.0 ? (best - (second < 0.0 ? 0.0 : second)) / best : 0.0) : 1.0;
-      }
-      lds_barrier();
-      z = 1.0;
-      for (int c2 = 0; c2 < NC; ++c2) z *= xmass[c2 * 64 + lane];
-    }
-    // impossible evidence (zero total mass): every marginal is 0/0 = NaN and np.argmax gives 0
-    const bool dead = !(z > 0.0);
-    if (do_marg && live) {  // normalised marginal streamed straight to HBM
-      const double inv = dead ? __builtin_nan("") : 1.0 / mass;
-      double *out = mrow + r;
-#pragma unroll
-      for (int qs = 0; qs < RC; ++qs)
-        if ((uint32_t)qs < P) out[(int64_t)qs * ld_out] = pc[qs] * inv;
-      for (uint32_t qs = RC; qs < P; ++qs) {
-        double prod = val(cb[0] + (int32_t)qs * fs[0]);
-#pragma unroll
-        for (int k = 1; k < NF; ++k) prod *= val(cb[k] + (int32_t)qs * fs[k]);
-        out[(int64_t)qs * ld_out] = prod * inv;
-      }
-    }
-    if constexpr (MAP) {
-      if (live && c == 0) {
-        int32_t m = best_s * ms;
-        double mg = (P > 1) ? (best > 0.0 ? (best - (second < 0.0 ? 0.0 : second)) / best : 0.0) : 1.0;
-        if (NC > 1) {
-          m = 0;
-          mg = 1.0;
-          for (int c2 = 0; c2 < NC; ++c2) {
-            m += xmap[c2 * 64 + lane];
-            mg = fmin(mg, xgap[c2 * 64 + lane]);
-          }
-        }
-        if (map) map[r] = dead ? 0 : m;
-        if (gap && (mode & PGM_ROWS_MAPGAP)) gap[r] = dead ? 0.0 : mg;
-      }
-    }
-    if (NC > 1 && g + 1 < RG) lds_barrier();  // the exchange slots are reused by the next row group
-  }
-#ifdef PGM_ROWS_TIMELINE
-  {  // [entry, ready, stores issued, stores acked, HW_ID, XCC_ID] per wave into `gap`
-    const uint64_t t_issued = __builtin_amdgcn_s_memrealtime();
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const uint64_t t_done = __builtin_amdgcn_s_memrealtime();
-    if (gap && !(mode & PGM_ROWS_MAPGAP) && lane == 0) {
-      double *tl = gap + ((int64_t)blockIdx.x * (blockDim.x >> 6) + c) * 6;
-      tl[0] = (double)t_entry;
-      tl[1] = (double)t_ready;
-      tl[2] = (double)t_issued;
-      tl[3] = (double)t_done;
-      tl[4] = (double)__builtin_amdgcn_s_getreg(4 | (31 << 11));
-      tl[5] = (double)__builtin_amdgcn_s_getreg(20 | (15 << 11));
-    }
-  }
-#endif
-}
-
-template <bool VL, int NF, int NT>
-static void launch_affine_m(bool do_map, dim3 g, dim3 b, size_t lds, hipStream_t s, const RowsK &k,
-                            const double *v, const int32_t *t, const uint8_t *codes, int64_t ldc, int64_t row0,
-                            int64_t n, int32_t mode, int32_t RG, double *marg, int64_t ldo, int32_t *map,
-                            double *gap, int32_t *err) {
-  if (do_map)
-    hipLaunchKernelGGL((k_rows_affine<VL, NF, NT, true>), g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, ldo, map, gap, err);
-  else
-    hipLaunchKernelGGL((k_rows_affine<VL, NF, NT, false>), g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, ldo, map, gap, err);
-}
-
-template <bool VL>
-static void launch_affine(int max_nf, int max_nt, bool do_map, dim3 g, dim3 b, size_t lds, hipStream_t s,
-                          const RowsK &k, const double *v, const int32_t *t, const uint8_t *codes, int64_t ldc,
-                          int64_t row0, int64_t n, int32_t mode, int32_t RG, double *marg, int64_t ldo,
-                          int32_t *map, double *gap, int32_t *err) {
-#define PGM_AFF(NF, NT) launch_affine_m<VL, NF, NT>(do_map, g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, ldo, map, gap, err)
-  if (max_nt <= 4) {
-    if (max_nf <= 1) PGM_AFF(1, 4);
-    else if (max_nf <= 2) PGM_AFF(2, 4);
-    else PGM_AFF(4, 4);
-  } else {
-    if (max_nf <= 1) PGM_AFF(1, 8);
-    else if (max_nf <= 2) PGM_AFF(2, 8);
-    else PGM_AFF(4, 8);
-  }
-#undef PGM_AFF
-}
-
-template <bool VL, bool AL, int MAXT>
-static void launch_rows_t(int max_nf, dim3 g, dim3 b, size_t lds, hipStream_t s, const RowsK &k, const double *v,
-                          const int32_t *t, const uint8_t *codes, int64_t ldc, int64_t row0, int64_t n, int32_t mode,
-                          int32_t RG, double *marg, double *joint, int64_t ldo, int32_t *map, double *gap, int32_t *err) {
-  if (max_nf <= 2)
-    hipLaunchKernelGGL((k_rows<VL, AL, 2, MAXT>), g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
-  else if (max_nf <= 4)
-    hipLaunchKernelGGL((k_rows<VL, AL, 4, MAXT>), g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
-  else if (max_nf <= 8)
-    hipLaunchKernelGGL((k_rows<VL, AL, 8, MAXT>), g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
-  else
-    hipLaunchKernelGGL((k_rows<VL, AL, PGM_ROWS_MAX_FAC, MAXT>), g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
-}
-
-template <bool VL, bool AL>
-static void launch_rows_f(int max_nt, int max_nf, dim3 g, dim3 b, size_t lds, hipStream_t s, const RowsK &k,
-                          const double *v, const int32_t *t, const uint8_t *codes, int64_t ldc, int64_t row0, int64_t n,
-                          int32_t mode, int32_t RG, double *marg, double *joint, int64_t ldo, int32_t *map, double *gap,
-                          int32_t *err) {
-  if (max_nt <= 4)
-    launch_rows_t<VL, AL, 4>(max_nf, g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
-  else if (max_nt <= 8)
-    launch_rows_t<VL, AL, 8>(max_nf, g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
-  else
-    launch_rows_t<VL, AL, PGM_ROWS_MAX_EV>(max_nf, g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
-}
-
-// ----------------------------------------------------------------------------- plan-specialised row kernel
-// For plans whose components each have one query variable and no hidden variable (the batched
-// predict shape, munin C3), pgm_rows_plan_create also writes a kernel source with every column,
-// stride, base offset and cardinality as a literal; hipRTC compiles it for gfx950 on first use.
-// One thread per evidence row, 256-row workgroups: the CPT values are staged in LDS with every
-// load issued before any LDS write, all evidence codes are loaded once per distinct column, and
-// each component's products stay in registers between the mass and the stores.  No descriptor
-// loads, no inter-wave exchange, a few hundred bytes of code.  Arithmetic order is exactly the
-// generic kernels' (factor products left to right, masses summed in state order, components'
-// masses multiplied in order), so results are bit-identical to k_rows_affine / k_rows.
-void pgmi_appendf(std::string &o, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  o += buf;
-}
-
-// workgroup size of the specialised row kernels (tuning knob PGM_ROWS_JIT_WG: a multiple of 64, <= 1024).
-// 512 (r02br, MI355X, C3 = 100k-row launches on 4 queues, two rows per thread): 98 blocks of 1,024
-// rows per launch — one CPT staging per 1,024 rows and a quarter of the workgroup dispatches of
-// 256 x one row — 26.4 -> 29.1-31.1 G rows/s at 20 steps, 36.2 -> 47.1 G at 400; one queue and
-// 1M-row launches unchanged (profiles/r02bq_c3_wg_rowform_sweep.txt, r02br_c3_wg_rowform_confirm.txt)
-// r04 (96 resident batches, the HBM regime: profiles/r04e, r04f): 320 — 157 blocks of 640 rows per
-// 100 k-row launch keep more CUs streaming than 98 x 1,024 once the outputs go to HBM instead of the
-// Infinity Cache; three interleaved repeats, 20 steps: 26.6 / 26.7 / 27.9 G rows/s against 27.3 / 25.1 /
-// 25.3 G at 512 (192: 27.0 / 26.7 / 26.0; 128: 25.7 / 25.6 / 26.6; 1,024: 25.5 / 24.7 / 25.5)
-// r06 (one 157-block launch never covers the 256 CUs): 192 — 261 blocks of 384 rows per
-// 100 k-row launch, every CU a block from each launch; three interleaved repeats at the driver's 20 steps
-// (profiles/r06b/): 26.29 / 26.82 / 26.04 G rows/s, frac 0.607 / 0.613 / 0.612, against 25.20 / 26.20 /
-// 25.74 G, frac 0.572 / 0.606 / 0.588 at 320; the 400-batch ring is unchanged (0.70-0.71).  A/B knob
-// PGM_ROWS_JIT_WG (a multiple of 64 in [64, 1024]), read once.
-static int jit_wg() {
-  static const int wg = [] {
-    const char *e = getenv("PGM_ROWS_JIT_WG");
-    const int v = e ? atoi(e) : 0;
-    return (v >= 64 && v <= 1024 && v % 64 == 0) ? v : 192;
-  }();
-  return wg;
-}
-
-// output store form of the specialised kernels: write-through — 8-B relaxed agent-scope atomic stores /
-// 16-B buffer stores with the sc1 bit — so every output line goes past the XCD's L2 in the dispatch that
-// writes it (no dirty output left for an end-of-dispatch release to write back; measured MI355X, 100k
-// rows: HIP launch 4.7 -> 3.8 us, direct queue 6.2 -> 4.0 us with the per-dispatch release dropped,
-// WRITE_SIZE 13.28 MB per launch either way; r02 also measured plain (write-back) and nontemporal forms)
-static constexpr int jit_store() { return 2; }
-
-// workgroup size of the ring kernel: 256 = one wave per
-// SIMD per workgroup; the loop around the two-row body takes ~147 VGPRs (3 waves per SIMD), so three
-// workgroups are resident per CU (a 1,024-thread bound caps it at 128 VGPRs and spills to scratch;
-// 512 threads fit one workgroup per CU)
-static constexpr int ring_wg() { return 256; }
-
-// the ring's waiting waves back off: the workgroup's token wave reads the chip-wide poll token before
-// trying to take it, and sleeps longer the longer it has waited (4 -> 12 -> 32 x 64 clocks).  768 token
-// waves retrying one atomic every ~0.1 us while the ring idles saturate that address and delay the one
-// wave that reads the host counter (r03: ring-ready 20 steps 17.1 -> 29.5-30.8 G rows/s)
-static constexpr bool ring_backoff() { return true; }
-
-static std::vector<int> rows_cols(const pgm_rows_plan *pl);
-static void emit_rows_code_loads(std::string &o, const std::vector<int> &cols, int R, bool coherent = false);
-static void emit_rows_compute(std::string &o, const pgm_rows_plan *pl, int R, const std::vector<int> &cols,
-                              const char *leave);
-
-// R rows per thread (1, or 2 with 16-B marginal stores / 2-byte code loads); names carry the row's suffix
-static void emit_rows_kernel(std::string &o, const pgm_rows_plan *pl, int R) {
-  const int NV = pl->n_values + 1;  // + trailing 1.0
-  // CPT values staged in LDS when they fit (else gathered straight from global memory through L1/L2)
-  const bool lds = NV * 8 <= 48 * 1024;
-  const int WG = jit_wg();
-  pgmi_appendf(o, "extern \"C\" __global__ void __launch_bounds__(%d) pgm_rows_jit%s(const double *__restrict__ V, "
-             "const unsigned char *__restrict__ C, long long ldc, long long row0, long long n, "
-             "double *__restrict__ M, long long ldo, int *__restrict__ MP, double *__restrict__ G, "
-             "int *__restrict__ E, int mode) {\n", WG, R == 2 ? "2" : "");
-  o += "  const int t = threadIdx.x;\n";
-  pgmi_appendf(o, "  const long long r = ((long long)blockIdx.x * %d + t) * %d;\n", WG, R);
-  pgmi_appendf(o, "  const long long rc = r < n ? r : n - %d;\n", R);
-  if (R == 2 && jit_store() == 2)
-    o += "  const __amdgpu_buffer_rsrc_t rsM = __builtin_amdgcn_make_buffer_rsrc(M, 0, 0x7fffffff, 0x00020000);\n"
-         "  const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc(G, 0, 0x7fffffff, 0x00020000);\n";
-  const int K = (NV + WG - 1) / WG;
-  if (lds) {
-    pgmi_appendf(o, "  __shared__ double S[%d];\n", K * WG);
-    for (int i = 0; i < K; ++i) pgmi_appendf(o, "  const double s%d = V[t + %d < %d ? t + %d : %d];\n", i, WG * i, NV, WG * i, NV - 1);
-  }
-  const std::vector<int> cols = rows_cols(pl);
-  emit_rows_code_loads(o, cols, R);
-  if (lds) {
-    for (int i = 0; i < K; ++i) pgmi_appendf(o, "  S[t + %d < %d ? t + %d : %d] = s%d;\n", WG * i, NV, WG * i, NV - 1, i);
-    o += "  __syncthreads();\n#define VAL(i) S[i]\n";
-  } else {
-    o += "#define VAL(i) V[i]\n";
-  }
-  emit_rows_compute(o, pl, R, cols, "return");
-  o += "}\n#undef VAL\n";
-}
-
-// the distinct evidence columns of a plan, each loaded once per row
-static std::vector<int> rows_cols(const pgm_rows_plan *pl) {
-  std::vector<int> cols;
-  for (int j = 0; j < pl->n_ev; ++j)
-    if (std::find(cols.begin(), cols.end(), pl->ev_col[j]) == cols.end()) cols.push_back(pl->ev_col[j]);
-  return cols;
-}
-
-// the row's evidence codes (row rc of the columns at C + row0, leading dimension ldc): e<i>_<u>
-// coherent: system-scope relaxed loads (past every non-coherent cache, no invalidation needed) — the
-// ring kernel's codes, which may be written after the launch started
-static void emit_rows_code_loads(std::string &o, const std::vector<int> &cols, int R, bool coherent) {
-  if (!cols.empty()) o += "  const unsigned char *cr = C + row0 + rc;\n";
-  for (size_t i = 0; i < cols.size(); ++i) {
-    if (R == 1) {
-      pgmi_appendf(o, "  const unsigned e%zu_0 = cr[%dLL * ldc];\n", i, cols[i]);
-    } else if (coherent) {
-      pgmi_appendf(o, "  const unsigned w%zu = __hip_atomic_load((__attribute__((address_space(1))) unsigned short *)(cr + %dLL * ldc), __ATOMIC_RELAXED, "
-                   "__HIP_MEMORY_SCOPE_SYSTEM);\n", i, cols[i]);
-      pgmi_appendf(o, "  const unsigned e%zu_0 = w%zu & 255u, e%zu_1 = w%zu >> 8;\n", i, i, i, i);
-    } else {
-      pgmi_appendf(o, "  const unsigned w%zu = *(const unsigned short *)(cr + %dLL * ldc);\n", i, cols[i]);
-      pgmi_appendf(o, "  const unsigned e%zu_0 = w%zu & 255u, e%zu_1 = w%zu >> 8;\n", i, i, i, i);
-    }
-  }
-}
-
-// the row's sum-product, normalisation and stores (r, rc, n, M, ldo, MP, G, E, mode, rsM / rsG and the
-// loaded codes in scope; VAL(i) = CPT value i); rows past n leave through `leave` ("return" in a grid
-// kernel, "break" inside the ring kernel's do-while)
-static void emit_rows_compute(std::string &o, const pgm_rows_plan *pl, int R, const std::vector<int> &cols,
-                              const char *leave) {
-  o += "  unsigned bad = 0u;\n";
-  const int NC = pl->n_comp;
-  for (int u = 0; u < R; ++u) {
-    for (int c = 0; c < NC; ++c) {
-      const int lb = pl->comp_loop_begin[c], nq = pl->comp_n_query[c];
-      const int fb = pl->comp_fac_begin[c], fe = pl->comp_fac_end[c];
-      const int P = nq == 1 ? pl->loop_card[lb] : 1;
-      for (int f = fb; f < fe; ++f) {
-        pgmi_appendf(o, "  int o%d_%d_%d = %d;\n", c, f - fb, u, pl->fac_base[f]);
-        for (int j = pl->fac_ev_begin[f]; j < pl->fac_ev_end[f]; ++j) {
-          const int ci = (int)(std::find(cols.begin(), cols.end(), pl->ev_col[j]) - cols.begin());
-          const unsigned cd = (unsigned)pl->ev_card[j];
-          pgmi_appendf(o, "  { const unsigned x = e%d_%d; bad |= (unsigned)(x >= %uu); o%d_%d_%d += (x >= %uu ? 0 : (int)x) * %d; }\n",
-                  ci, u, cd, c, f - fb, u, cd, pl->ev_stride[j]);
-        }
-      }
-      for (int q = 0; q < P; ++q) {
-        pgmi_appendf(o, "  const double p%d_%d_%d = ", c, q, u);
-        if (fe == fb) o += "1.0";
-        for (int f = fb; f < fe; ++f) {
-          const int qs = nq == 1 ? pl->fac_stride[f][lb] : 0;
-          pgmi_appendf(o, "%sVAL(o%d_%d_%d + %d)", f > fb ? " * " : "", c, f - fb, u, q * qs);
-        }
-        o += ";\n";
-      }
-      pgmi_appendf(o, "  const double m%d_%d = p%d_0_%d", c, u, c, u);
-      for (int q = 1; q < P; ++q) pgmi_appendf(o, " + p%d_%d_%d", c, q, u);
-      o += ";\n";
-    }
-    pgmi_appendf(o, "  const double z_%d = ", u);
-    if (NC == 1) pgmi_appendf(o, "m0_%d", u);
-    else {
-      o += "1.0";
-      for (int c = 0; c < NC; ++c) pgmi_appendf(o, " * m%d_%d", c, u);
-    }
-    pgmi_appendf(o, ";\n  const bool dead_%d = !(z_%d > 0.0);\n", u, u);
-  }
-  pgmi_appendf(o, "  if (bad && r < n && E) atomicOr(E, 1);\n  if (r >= n) %s;\n", leave);
-  o += "  if (mode & 1) {\n";
-  for (int c = 0; c < NC; ++c) {
-    const int lb = pl->comp_loop_begin[c], nq = pl->comp_n_query[c];
-    if (nq != 1) continue;
-    o += "    {";
-    for (int u = 0; u < R; ++u)
-      pgmi_appendf(o, " const double iv_%d = dead_%d ? __builtin_nan(\"\") : 1.0 / m%d_%d;", u, u, c, u);
-    o += "\n";
-    for (int q = 0; q < pl->loop_card[lb]; ++q) {
-      const int mo = pl->loop_marg_off[lb] + q;
-      if (R == 1 && jit_store() == 1)
-        pgmi_appendf(o, "      __builtin_nontemporal_store(p%d_%d_0 * iv_0, &M[%dLL * ldo + r]);\n", c, q, mo);
-      else if (R == 1 && jit_store() == 2)
-        pgmi_appendf(o, "      PGM_WT8(double, &M[%dLL * ldo + r], p%d_%d_0 * iv_0);\n", mo, c, q);
-      else if (R == 1)
-        pgmi_appendf(o, "      M[%dLL * ldo + r] = p%d_%d_0 * iv_0;\n", mo, c, q);
-      else if (jit_store() == 2)
-        pgmi_appendf(o, "      PGM_WT16(rsM, %dLL * ldo + r, p%d_%d_0 * iv_0, p%d_%d_1 * iv_1);\n", mo, c, q, c, q);
-      else
-        pgmi_appendf(o, "      *(double2 *)(M + %dLL * ldo + r) = make_double2(p%d_%d_0 * iv_0, p%d_%d_1 * iv_1);\n",
-                mo, c, q, c, q);
-    }
-    o += "    }\n";
-  }
-  o += "  }\n  if (mode & 12) {\n";
-  for (int u = 0; u < R; ++u) {
-    pgmi_appendf(o, "    int m_%d = 0;\n    double mg_%d = 1.0;\n", u, u);
-    for (int c = 0; c < NC; ++c) {
-      const int lb = pl->comp_loop_begin[c], nq = pl->comp_n_query[c];
-      const int P = nq == 1 ? pl->loop_card[lb] : 1;
-      const int ms = nq == 1 ? pl->loop_map_stride[lb] : 0;
-      o += "    { double b = -1.0, s = -1.0; int bs = 0;\n";
-      for (int q = 0; q < P; ++q)
-        pgmi_appendf(o, "      if (p%d_%d_%d > b) { s = b; b = p%d_%d_%d; bs = %d; } else if (p%d_%d_%d > s) { s = p%d_%d_%d; }\n",
-                c, q, u, c, q, u, q, c, q, u, c, q, u);
-      pgmi_appendf(o, "      m_%d += bs * %d;\n", u, ms);
-      if (P > 1)
-        o += "      const double g = b > 0.0 ? (b - (s < 0.0 ? 0.0 : s)) / b : 0.0;\n";
-      else
-        o += "      const double g = 1.0;\n";
-      pgmi_appendf(o, NC == 1 ? "      mg_%d = g; }\n" : "      mg_%d = fmin(mg_%d, g); }\n", u, u);
-    }
-  }
-  const bool wt = jit_store() == 2;
-  if (R == 1 && wt) {
-    o += "    if (MP) PGM_WT4(int, &MP[r], dead_0 ? 0 : m_0);\n"
-         "    if ((mode & 8) && G) PGM_WT8(double, &G[r], dead_0 ? 0.0 : mg_0);\n  }\n";
-  } else if (R == 1) {
-    o += "    if (MP) MP[r] = dead_0 ? 0 : m_0;\n    if ((mode & 8) && G) G[r] = dead_0 ? 0.0 : mg_0;\n  }\n";
-  } else if (wt) {
-    o += "    if (MP) PGM_WT8(unsigned long long, (unsigned long long *)(MP + r), "
-         "((unsigned long long)(unsigned)(dead_1 ? 0 : m_1) << 32) | (unsigned)(dead_0 ? 0 : m_0));\n";
-    o += "    if ((mode & 8) && G) PGM_WT16(rsG, r, dead_0 ? 0.0 : mg_0, dead_1 ? 0.0 : mg_1);\n  }\n";
-  } else {
-    o += "    if (MP) *(int2 *)(MP + r) = make_int2(dead_0 ? 0 : m_0, dead_1 ? 0 : m_1);\n";
-    o += "    if ((mode & 8) && G) *(double2 *)(G + r) = make_double2(dead_0 ? 0.0 : mg_0, dead_1 ? 0.0 : mg_1);\n  }\n";
-  }
-}
-
-// ---------------------------------------------------------------------------------------- ring kernel
-// pgm_rows_ring: the plan-specialised two-rows-per-thread body run by a RESIDENT grid over a stream of
-// row batches (pgm_rows_ring_*).  One launch consumes n_batches batches of n rows; batch b reads and
-// writes the buffers of slot b % n_slots (descriptor table D in device memory).  The host publishes
-// batches by raising a counter in pinned host memory (ctl[0] = batches posted); the launch may start
-// before the first post.  Work item = 128 rows (one wave, two rows per lane) of one batch; item j
-// goes to wave j mod W (W = resident waves), so consecutive batches overlap across the chip instead of
-// each paying a dispatch.
-// Learning that a batch is posted, three levels deep so the host counter sees ONE reader at a time
-// (reads of host memory from the GPU are serialised: 768 concurrent first polls cost ~150 us, r03a):
-//   1. the count the wave's workgroup last saw (LDS seen_s);
-//   2. one wave per workgroup (LDS token) reads the device-memory mirror g[0];
-//   3. one wave on the chip (token g[1], agent scope) reads ctl[0] with a system-scope acquire and
-//      raises the mirror.
-// No acquire fences (an L2 invalidation per workgroup serialises per XCD: ~100 us per launch, r03b):
-// the counters are read with relaxed system/agent-scope atomics, and the evidence codes with
-// system-scope loads, which go past every non-coherent cache — so codes written (by DMA) after the
-// launch started but before their batch was posted are read fresh.  Exit conditions every wave reaches:
-// all items done; ctl[1] (cancel) set by the host; or `timeout` ticks of the constant 100 MHz wall
-// clock without the needed batch (ctl[2] |= 2); either of the last two raises g[2] (stop) for all.
-// The CPT values are staged in LDS once per workgroup for the whole stream.
-static void emit_rows_ring(std::string &o, const pgm_rows_plan *pl) {
-  const int NV = pl->n_values + 1;
-  const int WG = ring_wg();
-  const int K = (NV + WG - 1) / WG;
-  pgmi_appendf(o, "#define BACKOFF %d\n", ring_backoff() ? 1 : 0);
-  o += "struct pgm_ring_slot { const unsigned char *C; long long ldc, row0; double *M; long long ldo; int *MP; "
-       "double *G; long long pad; };\n";
-  pgmi_appendf(o, "extern \"C\" __global__ void __launch_bounds__(%d) pgm_rows_ring(const double *__restrict__ V, "
-             "const pgm_ring_slot *__restrict__ D, unsigned n_slots, unsigned *ctl, unsigned *g, unsigned n_batches, "
-             "unsigned base, long long n, int *__restrict__ E, int mode, unsigned long long timeout, int signal) {\n", WG);
-  o += "  const int t = threadIdx.x;\n";
-  pgmi_appendf(o, "  __shared__ double S[%d];\n  __shared__ unsigned seen_s, token_s, stop_s;\n", K * WG);
-  for (int i = 0; i < K; ++i) pgmi_appendf(o, "  const double s%d = V[t + %d < %d ? t + %d : %d];\n", i, WG * i, NV, WG * i, NV - 1);
-  for (int i = 0; i < K; ++i) pgmi_appendf(o, "  S[t + %d < %d ? t + %d : %d] = s%d;\n", WG * i, NV, WG * i, NV - 1, i);
-  o += "  if (t == 0) { seen_s = base; token_s = 0u; stop_s = 0u; }\n  __syncthreads();\n#define VAL(i) S[i]\n";
-  // readiness (pgm_rows_ring_wait_ready): every workgroup counts itself in g[4..5] (64-bit, never reset:
-  // each launch adds exactly gridDim.x) once its CPT copy is staged; the last one raises ctl[3] for the host
-  o += "  if (signal && t == 0) {\n"
-       "    const unsigned long long s = atomicAdd((unsigned long long *)(g + 4), 1ull) + 1ull;\n"
-       "    if (s % gridDim.x == 0ull) __hip_atomic_store(&ctl[3], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);\n"
-       "  }\n";
-  pgmi_appendf(o, "  const unsigned long long W = (unsigned long long)gridDim.x * %d;\n", WG / 64);
-  pgmi_appendf(o, "  const unsigned long long wv0 = (unsigned long long)blockIdx.x * %d + (t >> 6);\n", WG / 64);
-  o += "  const unsigned long long chunks = (unsigned long long)(n + 127) / 128;\n"
-       "  const unsigned long long items = chunks * n_batches;\n"
-       "  const unsigned long long t0 = wall_clock64();\n"
-       "  const bool lead = (t & 63) == 0;\n"
-       "  unsigned seen = base;  /* counts are absolute over the ring's lifetime */\n"
-       "  for (unsigned long long j = wv0; j < items; j += W) {\n"
-       "    const unsigned bt = (unsigned)(j / chunks);\n"
-       "    const unsigned ab = base + bt;  /* the batch's absolute number: posted once ctl[0] > ab */\n"
-       "    bool stop = false;\n"
-       "    while (ab >= seen) {\n"
-       "      const unsigned sl = __hip_atomic_load(&seen_s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);\n"
-       "      if (sl > seen) { seen = sl; continue; }\n"
-       "      if (__hip_atomic_load(&stop_s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) { stop = true; break; }\n"
-       "      unsigned mine = 0u;\n"
-       "      if (lead) mine = atomicCAS(&token_s, 0u, 1u) == 0u ? 1u : 0u;\n"
-       "      mine = __builtin_amdgcn_readfirstlane(mine);\n"
-       "      if (!mine) {\n"
-       "        if (wall_clock64() - t0 > timeout) { stop = true; break; }\n"
-       "        __builtin_amdgcn_s_sleep(2);\n"
-       "        continue;\n"
-       "      }\n"
-       "      unsigned nap = 0u;\n"
-       "      for (;;) {  /* this wave speaks for its workgroup */\n"
-       "        unsigned m = __hip_atomic_load(&g[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-       "        if (m <= ab) {\n"
-       "          if (__hip_atomic_load(&g[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { stop = true; break; }\n"
-       "          unsigned poll = 0u;\n"
-       "          if (lead && (!BACKOFF || __hip_atomic_load(&g[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u))\n"
-       "            poll = atomicCAS(&g[1], 0u, 1u) == 0u ? 1u : 0u;\n"
-       "          poll = __builtin_amdgcn_readfirstlane(poll);\n"
-       "          if (poll) {  /* the one reader of the host counter */\n"
-       "            const unsigned p = __hip_atomic_load(&ctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);\n"
-       "            if (p > m && lead) __hip_atomic_fetch_max(&g[0], p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-       "            if (p > m) m = p;\n"
-       "            if (m <= ab) {\n"
-       "              const bool cancel = __hip_atomic_load(&ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u;\n"
-       "              const bool late = wall_clock64() - t0 > timeout;\n"
-       "              if ((cancel || late) && lead) {\n"
-       "                if (late) __hip_atomic_fetch_or(&ctl[2], 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);\n"
-       "                __hip_atomic_store(&g[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-       "              }\n"
-       "              stop = cancel || late;\n"
-       "            }\n"
-       "            if (lead) __hip_atomic_store(&g[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-       "            if (stop) break;\n"
-       "          } else if (wall_clock64() - t0 > timeout) {\n"
-       "            stop = true;\n"
-       "            break;\n"
-       "          }\n"
-       "        }\n"
-       "        if (m > ab) {\n"
-       "          seen = m;\n"
-       "          if (lead) atomicMax(&seen_s, m);\n"
-       "          break;\n"
-       "        }\n"
-       "        if (!BACKOFF || ++nap <= 2u) __builtin_amdgcn_s_sleep(4);\n"
-       "        else if (nap <= 8u) __builtin_amdgcn_s_sleep(12);\n"
-       "        else __builtin_amdgcn_s_sleep(32);\n"
-       "      }\n"
-       "      if (stop && lead) atomicExch(&stop_s, 1u);\n"
-       "      if (lead) atomicExch(&token_s, 0u);\n"
-       "      if (stop) break;\n"
-       "    }\n"
-       "    if (stop) break;\n"
-       "    const pgm_ring_slot d = D[bt % n_slots];\n"
-       "    const unsigned char *__restrict__ C = d.C;\n"
-       "    const long long ldc = d.ldc, row0 = d.row0, ldo = d.ldo;\n"
-       "    double *__restrict__ M = d.M;\n"
-       "    int *__restrict__ MP = d.MP;\n"
-       "    double *__restrict__ G = d.G;\n"
-       "    const long long r = (long long)(j - (unsigned long long)bt * chunks) * 128 + (t & 63) * 2;\n"
-       "    const long long rc = r < n ? r : n - 2;\n";
-  if (jit_store() == 2)
-    o += "    const __amdgpu_buffer_rsrc_t rsM = __builtin_amdgcn_make_buffer_rsrc(M, 0, 0x7fffffff, 0x00020000);\n"
-         "    const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc(G, 0, 0x7fffffff, 0x00020000);\n";
-  o += "    do {\n";
-  const std::vector<int> cols = rows_cols(pl);
-  emit_rows_code_loads(o, cols, 2, true);
-  emit_rows_compute(o, pl, 2, cols, "break");
-  o += "    } while (0);\n  }\n}\n#undef VAL\n";
-}
-
-// the dispatch floor of a plan (PGM_ROWS_FLOOR, measurement only): the row kernel's grid (R rows per
-// thread, as pgm_rows_jit / pgm_rows_jit2), its evidence-column loads and its output stores (same
-// addresses, same widths, same cache policy), with the CPT staging, gathers and arithmetic replaced by
-// one conversion of the loaded codes
-static void emit_rows_floor(std::string &o, const pgm_rows_plan *pl, int R) {
-  const int WG = jit_wg();
-  const bool wt = jit_store() == 2;
-  pgmi_appendf(o, "extern \"C\" __global__ void __launch_bounds__(%d) pgm_rows_floor%s(const double *__restrict__ V, "
-             "const unsigned char *__restrict__ C, long long ldc, long long row0, long long n, "
-             "double *__restrict__ M, long long ldo, int *__restrict__ MP, double *__restrict__ G, "
-             "int *__restrict__ E, int mode) {\n", WG, R == 2 ? "2" : "");
-  pgmi_appendf(o, "  const long long r = ((long long)blockIdx.x * %d + threadIdx.x) * %d;\n  if (r >= n) return;\n", WG, R);
-  if (R == 2 && wt)
-    o += "  const __amdgpu_buffer_rsrc_t rsM = __builtin_amdgcn_make_buffer_rsrc(M, 0, 0x7fffffff, 0x00020000);\n"
-         "  const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc(G, 0, 0x7fffffff, 0x00020000);\n";
-  std::vector<int> cols;
-  for (int j = 0; j < pl->n_ev; ++j)
-    if (std::find(cols.begin(), cols.end(), pl->ev_col[j]) == cols.end()) cols.push_back(pl->ev_col[j]);
-  o += "  unsigned x = 0u;\n";
-  if (!cols.empty()) o += "  const unsigned char *cr = C + row0 + r;\n";
-  for (size_t i = 0; i < cols.size(); ++i) {
-    if (R == 1) pgmi_appendf(o, "  x += cr[%dLL * ldc];\n", cols[i]);
-    else pgmi_appendf(o, "  x += *(const unsigned short *)(cr + %dLL * ldc);\n", cols[i]);
-  }
-  o += "  const double v = (double)x;\n  if (mode & 1) {\n";
-  for (int c = 0; c < pl->n_comp; ++c) {
-    const int lb = pl->comp_loop_begin[c];
-    if (pl->comp_n_query[c] != 1) continue;
-    for (int q = 0; q < pl->loop_card[lb]; ++q) {
-      const int mo = pl->loop_marg_off[lb] + q;
-      if (R == 2 && wt) pgmi_appendf(o, "    PGM_WT16(rsM, %dLL * ldo + r, v, v);\n", mo);
-      else if (R == 2) pgmi_appendf(o, "    *(double2 *)(M + %dLL * ldo + r) = make_double2(v, v);\n", mo);
-      else if (wt) pgmi_appendf(o, "    PGM_WT8(double, &M[%dLL * ldo + r], v);\n", mo);
-      else pgmi_appendf(o, "    M[%dLL * ldo + r] = v;\n", mo);
-    }
-  }
-  o += "  }\n  if (mode & 12) {\n";
-  if (R == 2 && wt)
-    o += "    if (MP) PGM_WT8(unsigned long long, (unsigned long long *)(MP + r), (unsigned long long)x);\n"
-         "    if ((mode & 8) && G) PGM_WT16(rsG, r, v, v);\n  }\n}\n";
-  else if (R == 2)
-    o += "    if (MP) *(int2 *)(MP + r) = make_int2((int)x, (int)x);\n"
-         "    if ((mode & 8) && G) *(double2 *)(G + r) = make_double2(v, v);\n  }\n}\n";
-  else if (wt)
-    o += "    if (MP) PGM_WT4(int, &MP[r], (int)x);\n    if ((mode & 8) && G) PGM_WT8(double, &G[r], v);\n  }\n}\n";
-  else
-    o += "    if (MP) MP[r] = (int)x;\n    if ((mode & 8) && G) G[r] = v;\n  }\n}\n";
-}
-
-static std::string rows_jit_source(const pgm_rows_plan *pl) {
-  // write-through stores: 4/8 B as relaxed agent-scope atomic stores (global_store ... sc1), 16 B as
-  // a buffer store with the sc1 cache bit (element offset into the resource's base, bytes < 2 GiB)
-  std::string o =
-      "typedef unsigned int pgm_u32x4 __attribute__((ext_vector_type(4)));\n"
-      "#define PGM_WT4(T, p, v) __hip_atomic_store((__attribute__((address_space(1))) T *)(p), (v), "
-      "__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)\n"
-      "#define PGM_WT8(T, p, v) PGM_WT4(T, p, v)\n"
-      "#define PGM_WT16(rs, off, a, b) do { const double2 v_ = make_double2((a), (b)); pgm_u32x4 w_; "
-      "__builtin_memcpy(&w_, &v_, 16); __builtin_amdgcn_raw_buffer_store_b128(w_, rs, (int)((off) * 8), 0, 16); } "
-      "while (0)\n";
-  emit_rows_kernel(o, pl, 1);
-  o += "\n";
-  emit_rows_kernel(o, pl, 2);
-  o += "\n";
-  emit_rows_floor(o, pl, 1);
-  o += "\n";
-  emit_rows_floor(o, pl, 2);
-  o += "\n";
-  emit_rows_ring(o, pl);
-  return o;
-}
-
-static bool rows2_aligned(int32_t mode, const uint8_t *codes, int64_t ld_codes, int64_t row0, int64_t n_rows,
-                          const double *marg, int64_t ld_out, const int32_t *map, const double *gap, int n_marg);
-
-// whether a launch runs the two-rows-per-thread kernel: big enough, and its alignment contract holds
-// (else the one-row kernel runs)
-static bool rows_jit2_ok(int32_t mode, const uint8_t *codes, int64_t ld_codes, int64_t row0, int64_t n_rows,
-                         const double *marg, int64_t ld_out, const int32_t *map, const double *gap, int n_marg) {
-  // measured (MI355X): two rows with 16-B stores once the launch is HBM-bound (4M rows: 110 vs 126 us)
-  // and, since the 512-thread workgroups and concurrent queues, at 100k rows too (one queue: equal,
-  // 3.9 us; four queues: 2.7 -> 2.1 us per launch of GPU span, r02br); one row below 50k rows
-  static constexpr int64_t min_rows = 50000;
-  if (n_rows < min_rows) return false;
-  return rows2_aligned(mode, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, n_marg);
-}
-
-// the alignment / addressing contract of the two-rows-per-lane body (pgm_rows_jit2, pgm_rows_ring)
-static bool rows2_aligned(int32_t mode, const uint8_t *codes, int64_t ld_codes, int64_t row0, int64_t n_rows,
-                          const double *marg, int64_t ld_out, const int32_t *map, const double *gap, int n_marg) {
-  if (n_rows % 2 || ld_codes % 2 || row0 % 2 || ((uintptr_t)codes & 1)) return false;
-  if ((mode & PGM_ROWS_MARGINALS) && (((uintptr_t)marg & 15) || ld_out % 2)) return false;
-  if (map && ((uintptr_t)map & 7)) return false;
-  if ((mode & PGM_ROWS_MAPGAP) && gap && ((uintptr_t)gap & 15)) return false;
-  // the write-through 16-B stores address outputs as 32-bit byte offsets below 2 GiB
-  if (jit_store() == 2 && (mode & PGM_ROWS_MARGINALS) && (uint64_t)(n_marg + 1) * (uint64_t)ld_out * 8 >= (1ull << 31))
-    return false;
-  if (jit_store() == 2 && (uint64_t)n_rows * 8 >= (1ull << 31)) return false;
-  return true;
-}
-
-
-// compile + load the handle's specialised kernel once; false when unavailable (AOT kernels run)
-static bool rows_jit_ready(RowsHandle *h) {
-  if (h->jit_src.empty()) return false;
-  std::lock_guard<std::mutex> lk(h->jit_mu);
-  if (h->jit_state != 0) return h->jit_state > 0;
-  h->jit_state = -1;
-  static const bool disabled = getenv("PGM_NO_JIT") != nullptr;  // testing: AOT kernels only
-  if (disabled) return false;
-  std::vector<char> code;
-  if (!pgmi_rtc_code(h->jit_src, "specialised row kernel", code)) return false;
-  h->jit_code = code;
-  if (hipModuleLoadData(&h->jit_mod, code.data()) != hipSuccess) {
-    (void)hipGetLastError();
-    h->jit_mod = nullptr;
-    return false;
-  }
-  if (hipModuleGetFunction(&h->jit_fn, h->jit_mod, "pgm_rows_jit") != hipSuccess ||
-      hipModuleGetFunction(&h->jit_fn2, h->jit_mod, "pgm_rows_jit2") != hipSuccess ||
-      hipModuleGetFunction(&h->jit_fn_floor, h->jit_mod, "pgm_rows_floor") != hipSuccess ||
-      hipModuleGetFunction(&h->jit_fn_floor2, h->jit_mod, "pgm_rows_floor2") != hipSuccess ||
-      hipModuleGetFunction(&h->jit_fn_ring, h->jit_mod, "pgm_rows_ring") != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  h->jit_state = 1;
-  return true;
-}
-
 // ============================================================================= C-ABI
 extern "C" {
 
@@ -3265,7 +2177,7 @@ int pgm_product_n(const pgm_productn_desc *d, const double *const *ops, double *
   const uint64_t NX = n > 0 ? (uint64_t)k.kdiv[n - 1].d : 1;
   const int64_t *sc = k.ksc;
   // two rows per lane when every access is 16-B aligned (batched BP: rows innermost, even count)
-  bool rows2 = k.row_mode && (NX % 2 == 0) && sc[n - 1] == 1 && ((uintptr_t)C & 15) == 0 && !g_no_rows2;
+  bool rows2 = k.row_mode && (NX % 2 == 0) && sc[n - 1] == 1 && ((uintptr_t)C & 15) == 0;
   for (int i = 0; rows2 && i < n - 1; ++i) rows2 = (sc[i] % 2) == 0;
   for (int t = 0; rows2 && t < d->n_ops; ++t) {
     const int64_t sx = k.ks[t][n - 1];
@@ -3548,7 +2460,7 @@ int pgm_batch_add_contract(void *handle, const pgm_contract_desc *d, const doubl
   // along the innermost kept dim is aligned and unit-stride (or broadcast)
   const int kx = k.nk - 1;
   const bool use_b = d->combine != PGM_COMBINE_COPY;
-  bool pairs = g == 0 && kx >= 0 && !g_no_rows2 && k.kdiv[kx].d % 2 == 0 && k.ksc[kx] == 1 && ((uintptr_t)C & 15) == 0;
+  bool pairs = g == 0 && kx >= 0 && k.kdiv[kx].d % 2 == 0 && k.ksc[kx] == 1 && ((uintptr_t)C & 15) == 0;
   const bool va = pairs && k.ksa[kx] != 0, vb = pairs && use_b && k.ksb[kx] != 0;
   pairs = pairs && (k.ksa[kx] == 0 || k.ksa[kx] == 1) && (!use_b || k.ksb[kx] == 0 || k.ksb[kx] == 1);
   for (int i = 0; pairs && i < kx; ++i) pairs = k.ksc[i] % 2 == 0 && (!va || k.ksa[i] % 2 == 0) && (!vb || k.ksb[i] % 2 == 0);
@@ -3594,7 +2506,7 @@ int pgm_batch_add_product_n(void *handle, const pgm_productn_desc *d, const doub
   // pairs: 16-B accesses when every access along the innermost dim is aligned and unit/zero stride
   ProdNK &k = J.pn;
   const int kx = k.nk - 1;
-  bool pairs = kx >= 0 && k.kdiv[kx].d % 2 == 0 && k.ksc[kx] == 1 && ((uintptr_t)C & 15) == 0 && !g_no_rows2;
+  bool pairs = kx >= 0 && k.kdiv[kx].d % 2 == 0 && k.ksc[kx] == 1 && ((uintptr_t)C & 15) == 0;
   for (int i = 0; pairs && i < kx; ++i) pairs = k.ksc[i] % 2 == 0;
   for (int t = 0; pairs && t < k.n_ops; ++t) {
     const int64_t sx = k.ks[t][kx];
@@ -4035,868 +2947,6 @@ int pgm_sample_joint(const double *joint, int64_t ld, int64_t P, const int32_t *
   if (bx > 0x7fffffffull) return fail(PGM_EINVAL, "sample_joint: too many rows");
   hipLaunchKernelGGL(k_sample_joint, dim3((unsigned)bx), dim3(256), 0, S(stream), joint, ld, P, group, u, n, out_idx);
   HIP_TRY(hipGetLastError());
-  return PGM_OK;
-}
-
-int pgm_rows_plan_create(const pgm_rows_plan *pl, const double *host_values, void **handle) {
-  STALE_PROBE();
-  if (!pl || !handle || (!host_values && pl->n_values > 0)) return fail(PGM_EINVAL, "rows_plan_create: null argument");
-  *handle = nullptr;
-  if (pl->n_loop < 0 || pl->n_loop > PGM_ROWS_MAX_LOOP || pl->n_query < 0 || pl->n_query > pl->n_loop ||
-      pl->n_fac < 0 || pl->n_fac > PGM_ROWS_MAX_FAC || pl->n_ev < 0 || pl->n_ev > PGM_ROWS_MAX_EV ||
-      pl->n_values < 0 || pl->n_comp < 1 || pl->n_comp > PGM_ROWS_MAX_COMP || pl->n_marg < 0 ||
-      pl->n_marg > PGM_ROWS_MAX_MARG)
-    return fail(PGM_EINVAL, "rows_plan_create: plan out of range (loop %d query %d fac %d ev %d comp %d marg %d)",
-                pl->n_loop, pl->n_query, pl->n_fac, pl->n_ev, pl->n_comp, pl->n_marg);
-  RowsK k;
-  memset(&k, 0, sizeof k);
-  k.one_idx = pl->n_values;  // a trailing 1.0 multiplies into the products of unused factor slots
-  k.n_values = pl->n_values + 1;
-  k.n_marg = pl->n_marg;
-  k.n_joint = pl->n_joint;
-  k.n_comp = pl->n_comp;
-  // factors: value ranges and evidence ownership
-  std::vector<int64_t> fac_hi(pl->n_fac);
-  for (int f = 0; f < pl->n_fac; ++f) {
-    if (pl->fac_ev_begin[f] < 0 || pl->fac_ev_end[f] > pl->n_ev || pl->fac_ev_begin[f] > pl->fac_ev_end[f])
-      return fail(PGM_EINVAL, "rows_plan_create: factor %d evidence range", f);
-    int64_t mx = pl->fac_base[f];
-    for (int kk = 0; kk < pl->n_loop; ++kk) mx += (int64_t)(pl->loop_card[kk] - 1) * pl->fac_stride[f][kk];
-    for (int j = pl->fac_ev_begin[f]; j < pl->fac_ev_end[f]; ++j) mx += (int64_t)(pl->ev_card[j] - 1) * pl->ev_stride[j];
-    if (mx >= pl->n_values || pl->fac_base[f] < 0)
-      return fail(PGM_EINVAL, "rows_plan_create: factor %d reads past values", f);
-    fac_hi[f] = mx + 1;
-  }
-  std::vector<int> ev_owner(pl->n_ev, -1);
-  for (int f = 0; f < pl->n_fac; ++f)
-    for (int j = pl->fac_ev_begin[f]; j < pl->fac_ev_end[f]; ++j) {
-      if (ev_owner[j] != -1) return fail(PGM_EINVAL, "rows_plan_create: evidence term %d feeds two factors", j);
-      ev_owner[j] = f;
-    }
-  std::vector<RowsComp> comps(pl->n_comp);
-  std::vector<int32_t> tab;
-  int covered_loop = 0, covered_fac = 0, nq_total = 0, max_nf = 1, max_nt = 0;
-  bool any_table = false;
-  for (int c = 0; c < pl->n_comp; ++c) {
-    const int lb = pl->comp_loop_begin[c], nq = pl->comp_n_query[c], le = pl->comp_loop_end[c];
-    const int fb = pl->comp_fac_begin[c], fe = pl->comp_fac_end[c];
-    if (lb != covered_loop || nq < 0 || lb + nq > le || le > pl->n_loop || fb != covered_fac || fe < fb ||
-        fe > pl->n_fac)
-      return fail(PGM_EINVAL, "rows_plan_create: component %d ranges (loops [%d,%d,%d) factors [%d,%d))", c, lb,
-                  lb + nq, le, fb, fe);
-    covered_loop = le;
-    covered_fac = fe;
-    uint64_t P = 1, H = 1;
-    for (int kk = lb; kk < le; ++kk) {
-      if (pl->loop_card[kk] <= 0) return fail(PGM_EINVAL, "rows_plan_create: loop_card[%d] <= 0", kk);
-      (kk < lb + nq ? P : H) *= (uint64_t)pl->loop_card[kk];
-      if (kk < lb + nq && (pl->loop_marg_off[kk] < 0 || pl->loop_marg_off[kk] + pl->loop_card[kk] > pl->n_marg))
-        return fail(PGM_EINVAL, "rows_plan_create: loop %d marginal rows out of range", kk);
-    }
-    const int nf = fe - fb;
-    if (P * H * (uint64_t)std::max(nf, 1) + tab.size() >= (1ull << 26))
-      return fail(PGM_EINVAL, "rows_plan_create: component %d index space too large for the fused kernel", c);
-    for (int f = fb; f < fe; ++f)
-      for (int kk = 0; kk < pl->n_loop; ++kk)
-        if ((kk < lb || kk >= le) && pl->fac_stride[f][kk] != 0)
-          return fail(PGM_EINVAL, "rows_plan_create: factor %d strides a loop dim outside its component", f);
-    max_nf = std::max(max_nf, nf);
-    RowsComp &cd = comps[c];
-    memset(&cd, 0, sizeof cd);
-    cd.nf = nf;
-    cd.nq = nq;
-    cd.P = (int32_t)P;
-    cd.H = (int32_t)H;
-    cd.q_lo = nq_total;
-    for (int kk = lb; kk < lb + nq; ++kk) {
-      k.q_marg_off[nq_total] = pl->loop_marg_off[kk];
-      k.q_card[nq_total] = pl->loop_card[kk];
-      ++nq_total;
-    }
-    cd.q_hi = nq_total;
-    cd.marg0 = nq >= 1 ? pl->loop_marg_off[lb] : 0;
-    cd.simple = (nq <= 1 && H == 1) ? 1 : 0;
-    any_table |= !cd.simple;
-    cd.mstride = nq == 1 ? pl->loop_map_stride[lb] : 0;
-    int64_t vlo = pl->n_values, vhi = 0;
-    for (int j = 0; j < PGM_ROWS_MAX_FAC; ++j) cd.fbase[j] = k.one_idx;
-    for (int f = fb; f < fe; ++f) {
-      cd.fbase[f - fb] = pl->fac_base[f];
-      cd.fstride[f - fb] = nq == 1 ? pl->fac_stride[f][lb] : 0;
-      vlo = std::min<int64_t>(vlo, pl->fac_base[f]);
-      vhi = std::max<int64_t>(vhi, fac_hi[f]);
-    }
-    cd.val_lo = vlo < vhi ? (int32_t)vlo : 0;
-    cd.val_hi = vlo < vhi ? (int32_t)vhi : 0;
-    // evidence terms: one contiguous run per component
-    int lo = pl->n_ev, hi = 0;
-    for (int f = fb; f < fe; ++f)
-      if (pl->fac_ev_end[f] > pl->fac_ev_begin[f]) {
-        lo = std::min(lo, pl->fac_ev_begin[f]);
-        hi = std::max(hi, pl->fac_ev_end[f]);
-      }
-    if (lo >= hi) lo = hi = pl->n_ev;
-    for (int j = lo; j < hi; ++j)
-      if (ev_owner[j] < fb || ev_owner[j] >= fe)
-        return fail(PGM_EINVAL, "rows_plan_create: component %d evidence terms are not contiguous", c);
-    cd.ev_lo = lo;
-    cd.nt = hi - lo;
-    max_nt = std::max(max_nt, hi - lo);
-    for (int j = 0; j < 8; ++j) {
-      cd.a_col[j] = hi > lo ? pl->ev_col[lo] : 0;
-      cd.a_card[j] = 256;
-    }
-    if (hi - lo <= 8)
-      for (int j = lo; j < hi; ++j) {
-        cd.a_col[j - lo] = pl->ev_col[j];
-        cd.a_card[j - lo] = pl->ev_card[j];
-        if (ev_owner[j] - fb < 4) cd.a_S[j - lo][ev_owner[j] - fb] = pl->ev_stride[j];
-      }
-    if (cd.simple) continue;
-    // per-entry tables, entries in C-order over [query dims..., hidden dims...] (last fastest)
-    const int nl = le - lb;
-    std::vector<int32_t> dig(nl, 0);
-    cd.off_base = (int32_t)tab.size();
-    for (uint64_t e = 0; e < P * H; ++e) {
-      uint64_t t = e;
-      for (int d = nl - 1; d >= 0; --d) {
-        dig[d] = (int32_t)(t % (uint64_t)pl->loop_card[lb + d]);
-        t /= (uint64_t)pl->loop_card[lb + d];
-      }
-      for (int f = fb; f < fe; ++f) {
-        int64_t o = 0;
-        for (int d = 0; d < nl; ++d) o += (int64_t)dig[d] * pl->fac_stride[f][lb + d];
-        tab.push_back((int32_t)o);
-      }
-    }
-    cd.marg_base = (int32_t)tab.size();
-    for (uint64_t qi = 0; qi < P; ++qi) {
-      uint64_t t = qi;
-      for (int d = nq - 1; d >= 0; --d) {
-        dig[d] = (int32_t)(t % (uint64_t)pl->loop_card[lb + d]);
-        t /= (uint64_t)pl->loop_card[lb + d];
-      }
-      for (int d = 0; d < nq; ++d) tab.push_back(pl->loop_marg_off[lb + d] + dig[d]);
-    }
-    cd.map_base = (int32_t)tab.size();
-    for (uint64_t qi = 0; qi < P; ++qi) {
-      uint64_t t = qi;
-      int64_t m = 0;
-      for (int d = nq - 1; d >= 0; --d) {
-        m += (int64_t)(t % (uint64_t)pl->loop_card[lb + d]) * pl->loop_map_stride[lb + d];
-        t /= (uint64_t)pl->loop_card[lb + d];
-      }
-      tab.push_back((int32_t)m);
-    }
-  }
-  if (covered_loop != pl->n_loop || covered_fac != pl->n_fac || nq_total != pl->n_query)
-    return fail(PGM_EINVAL, "rows_plan_create: components do not cover the loop dims / factors");
-  // descriptor buffer: [RowsComp x n_comp][RowsTerm blocks][tables].  Each component's terms are
-  // padded with no-op terms to the kernel's static term count (4 or 8) when they fit it.
-  const int padt = max_nt <= 4 ? 4 : max_nt <= 8 ? 8 : 0;
-  std::vector<RowsTerm> terms;
-  for (int c = 0; c < pl->n_comp; ++c) {
-    RowsComp &cd = comps[c];
-    const int lo = cd.ev_lo, nt = cd.nt, fb = pl->comp_fac_begin[c];
-    cd.ev_lo = (int32_t)terms.size();
-    for (int j = lo; j < lo + nt; ++j)
-      terms.push_back(RowsTerm{pl->ev_col[j], pl->ev_stride[j], pl->ev_card[j], ev_owner[j] - fb});
-    if (nt > 0)
-      for (int j = nt; j < padt; ++j) terms.push_back(RowsTerm{pl->ev_col[lo], 0, 256, -1});
-  }
-  terms.push_back(RowsTerm{0, 0, 256, -1});
-  static_assert(sizeof(RowsComp) % 16 == 0 && sizeof(RowsTerm) == 16, "descriptor packing");
-  std::vector<int32_t> buf(comps.size() * (sizeof(RowsComp) / 4));
-  if (!comps.empty()) memcpy(buf.data(), comps.data(), comps.size() * sizeof(RowsComp));
-  k.terms_off = (int32_t)buf.size();
-  buf.resize(buf.size() + terms.size() * 4);
-  memcpy(buf.data() + k.terms_off, terms.data(), terms.size() * sizeof(RowsTerm));
-  k.tab_off = (int32_t)buf.size();
-  buf.insert(buf.end(), tab.begin(), tab.end());
-  buf.push_back(0);
-  RowsHandle *h = new (std::nothrow) RowsHandle;
-  if (!h) return fail(PGM_ENOMEM, "rows_plan_create: host allocation");
-  h->k = k;
-  h->max_nf = max_nf;
-  h->max_nt = max_nt;
-  h->any_table = any_table;
-  h->all_affine = !any_table && max_nf <= 4 && max_nt <= 8;
-  h->d_values = nullptr;
-  h->d_desc = nullptr;
-  (void)hipGetDevice(&h->device);
-  for (int j = 0; j < pl->n_ev; ++j) h->n_cols = std::max(h->n_cols, pl->ev_col[j] + 1);
-  for (int j = 0; j < pl->n_ev; ++j) h->cols.push_back(pl->ev_col[j]);
-  std::sort(h->cols.begin(), h->cols.end());
-  h->cols.erase(std::unique(h->cols.begin(), h->cols.end()), h->cols.end());
-  if (!any_table) {
-    h->jit_src = rows_jit_source(pl);
-    h->jit_write_through = jit_store() == 2;
-  }
-  hipError_t e = hipSuccess;
-  e = hipMalloc((void **)&h->d_values, sizeof(double) * (pl->n_values + 1));
-  if (e == hipSuccess && pl->n_values > 0)
-    e = hipMemcpy(h->d_values, host_values, sizeof(double) * pl->n_values, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    const double one = 1.0;
-    e = hipMemcpy(h->d_values + pl->n_values, &one, sizeof(double), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess) e = hipMalloc((void **)&h->d_desc, sizeof(int32_t) * buf.size());
-  if (e == hipSuccess) e = hipMemcpy(h->d_desc, buf.data(), sizeof(int32_t) * buf.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (h->d_values) (void)hipFree(h->d_values);
-    if (h->d_desc) (void)hipFree(h->d_desc);
-    delete h;
-    return fail(e == hipErrorOutOfMemory ? PGM_ENOMEM : PGM_EDEVICE, "rows_plan_create: %s", hipGetErrorString(e));
-  }
-  *handle = h;
-  return PGM_OK;
-}
-
-int pgm_rows_plan_source(const pgm_rows_plan *pl, char *buf, size_t len, size_t *needed) {
-  STALE_PROBE();
-  if (!pl) return fail(PGM_EINVAL, "rows_plan_source: null plan");
-  if (pl->n_comp < 1 || pl->n_comp > PGM_ROWS_MAX_COMP || pl->n_fac < 0 || pl->n_fac > PGM_ROWS_MAX_FAC ||
-      pl->n_ev < 0 || pl->n_ev > PGM_ROWS_MAX_EV || pl->n_loop < 0 || pl->n_loop > PGM_ROWS_MAX_LOOP)
-    return fail(PGM_EINVAL, "rows_plan_source: plan out of range");
-  for (int c = 0; c < pl->n_comp; ++c)
-    if (pl->comp_n_query[c] > 1 || pl->comp_loop_end[c] - pl->comp_loop_begin[c] != pl->comp_n_query[c])
-      return fail(PGM_EINVAL, "rows_plan_source: component %d is not specialisable (query dims %d, loop dims %d)", c,
-                  pl->comp_n_query[c], pl->comp_loop_end[c] - pl->comp_loop_begin[c]);
-  const std::string src = rows_jit_source(pl);
-  if (needed) *needed = src.size() + 1;
-  if (buf && len > 0) {
-    const size_t n = std::min(len - 1, src.size());
-    memcpy(buf, src.data(), n);
-    buf[n] = 0;
-  }
-  return PGM_OK;
-}
-
-int pgm_rows_plan_destroy(void *handle) {
-  STALE_PROBE();
-  RowsHandle *h = (RowsHandle *)handle;
-  if (!h) return PGM_OK;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (h->shard[0].s || h->shard[1].s) (void)hipSetDevice(h->device);
-  for (auto &sd : h->shard) {
-    if (sd.s) (void)hipStreamSynchronize(sd.s);
-    if (sd.buf) (void)hipFree(sd.buf);
-    if (sd.h_err) (void)hipHostFree(sd.h_err);
-    if (sd.s) (void)hipStreamDestroy(sd.s);
-  }
-  (void)hipSetDevice(prev);
-  if (h->d_values) (void)hipFree(h->d_values);
-  if (h->d_desc) (void)hipFree(h->d_desc);
-  if (h->jit_mod) (void)hipModuleUnload(h->jit_mod);
-  delete h;
-  return PGM_OK;
-}
-
-}  // extern "C"
-
-// dry: validate and size the launch only (pgm_rows_plan_bind)
-static int rows_plan_run(void *handle, int32_t mode, const uint8_t *codes, int64_t ld_codes, int64_t row0,
-                         int64_t n_rows, double *marg, double *joint, int64_t ld_out, int32_t *map, double *gap,
-                         int32_t *err_flag, void *stream, bool dry) {
-  RowsHandle *h = (RowsHandle *)handle;
-  if (!h) return fail(PGM_EINVAL, "rows_plan_run: null handle");
-  if (n_rows <= 0) return PGM_OK;
-  if (h->max_nt > 0 && !codes) return fail(PGM_EINVAL, "rows_plan_run: null codes");
-  if ((mode & PGM_ROWS_MARGINALS) && !marg) return fail(PGM_EINVAL, "rows_plan_run: marginals requested, marg is null");
-  if ((mode & PGM_ROWS_JOINT) && !joint) return fail(PGM_EINVAL, "rows_plan_run: joint requested, joint is null");
-  if ((mode & PGM_ROWS_JOINT) && h->k.n_comp != 1)
-    return fail(PGM_EINVAL, "rows_plan_run: joint output needs a single-component plan");
-  if ((mode & PGM_ROWS_MAP) && !map) return fail(PGM_EINVAL, "rows_plan_run: MAP requested, map is null");
-  if ((mode & PGM_ROWS_MAPGAP) && !gap) return fail(PGM_EINVAL, "rows_plan_run: MAP gap requested, gap is null");
-  if ((mode & (PGM_ROWS_MARGINALS | PGM_ROWS_JOINT)) && ld_out < n_rows)
-    return fail(PGM_EINVAL, "rows_plan_run: ld_out %lld < n_rows %lld", (long long)ld_out, (long long)n_rows);
-  // one workgroup = 64 rows x RG row groups; W waves split the components
-  RowsK k = h->k;
-  k.n_waves = k.n_comp;  // one wave per component
-  const size_t kLds = 64 * 1024;
-  size_t vals_bytes = (size_t)((k.n_values + 1) & ~1) * sizeof(double);
-  const bool vals_lds = vals_bytes <= 40 * 1024 && !(mode & PGM_ROWS_VALUES_GLOBAL);
-  if (!vals_lds) vals_bytes = 0;
-  const size_t x_bytes = (size_t)k.n_comp * 64 * (2 * sizeof(double) + sizeof(int32_t));
-  const size_t acc_bytes = (size_t)k.n_marg * 64 * sizeof(double);
-  const bool acc_lds = (mode & PGM_ROWS_MARGINALS) && h->any_table && vals_bytes + x_bytes + acc_bytes <= kLds;
-  const size_t lds = vals_bytes + x_bytes + (acc_lds ? acc_bytes : 0);
-  const uint64_t groups = ((uint64_t)n_rows + 63) / 64;
-  // amortise the LDS staging of the CPT values over several row groups once the grid is large
-  int32_t RG = 1;
-  if (vals_lds && !(mode & PGM_ROWS_ONE_GROUP)) RG = (int32_t)std::max<uint64_t>(1, std::min<uint64_t>(8, groups / 4096));
-  hipStream_t s = S(stream);
-  const double *v = h->d_values;
-  const int32_t *t = h->d_desc;
-  if (!(mode & (PGM_ROWS_JOINT | PGM_ROWS_GENERIC | PGM_ROWS_NO_JIT | PGM_ROWS_VALUES_GLOBAL | PGM_ROWS_ONE_GROUP)) &&
-      rows_jit_ready(h)) {
-    const bool two = rows_jit2_ok(mode, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, h->k.n_marg);
-    const uint64_t rpb = (uint64_t)jit_wg() * (two ? 2 : 1);  // rows per block
-    const uint64_t jblocks = ((uint64_t)n_rows + rpb - 1) / rpb;
-    if (jblocks > 0x7fffffffull) return fail(PGM_EINVAL, "rows_plan_run: too many rows");
-    if (dry) return PGM_OK;
-    const uint8_t *cp = codes;
-    int64_t ldc = ld_codes, r0 = row0, nr = n_rows, ldo = ld_out;
-    double *mg = marg, *gp = gap;
-    int32_t *mp = map, *ef = err_flag;
-    int32_t md = mode;
-    void *args[] = {(void *)&v, (void *)&cp, &ldc, &r0, &nr, (void *)&mg, &ldo, (void *)&mp, (void *)&gp, (void *)&ef, &md};
-    HIP_TRY(hipModuleLaunchKernel(two ? h->jit_fn2 : h->jit_fn, (unsigned)jblocks, 1, 1, (unsigned)jit_wg(), 1, 1, 0, s,
-                                  args, nullptr));
-    return PGM_OK;
-  }
-  if (h->all_affine && !(mode & PGM_ROWS_JOINT) && !(mode & PGM_ROWS_GENERIC)) {
-    RG = 1;
-    if (vals_lds && !(mode & PGM_ROWS_ONE_GROUP))
-      RG = (int32_t)std::max<uint64_t>(1, std::min<uint64_t>(8, groups / 4096));
-    const uint64_t ablocks = (groups + RG - 1) / RG;
-    if (ablocks > 0x7fffffffull) return fail(PGM_EINVAL, "rows_plan_run: too many rows");
-    const bool do_map = (mode & (PGM_ROWS_MAP | PGM_ROWS_MAPGAP)) != 0;
-    // exchange slots: masses only, unless MAP digits / gaps are combined too
-    const size_t x_aff = k.n_comp > 1 ? (size_t)k.n_comp * 64 * (do_map ? 2 * sizeof(double) + sizeof(int32_t) : sizeof(double)) : 0;
-    const dim3 ag((unsigned)ablocks), ab(64 * k.n_comp);
-    if (dry) return PGM_OK;
-    if (vals_lds)
-      launch_affine<true>(h->max_nf, h->max_nt, do_map, ag, ab, vals_bytes + x_aff, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, ld_out, map, gap, err_flag);
-    else
-      launch_affine<false>(h->max_nf, h->max_nt, do_map, ag, ab, vals_bytes + x_aff, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, ld_out, map, gap, err_flag);
-    HIP_TRY(hipGetLastError());
-    return PGM_OK;
-  }
-  const uint64_t blocks = (groups + RG - 1) / RG;
-  if (blocks > 0x7fffffffull) return fail(PGM_EINVAL, "rows_plan_run: too many rows");
-  const dim3 g((unsigned)blocks), b(64 * k.n_waves);
-  if (dry) return PGM_OK;
-  if (vals_lds && acc_lds)
-    launch_rows_f<true, true>(h->max_nt, h->max_nf, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, joint, ld_out, map, gap, err_flag);
-  else if (vals_lds)
-    launch_rows_f<true, false>(h->max_nt, h->max_nf, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, joint, ld_out, map, gap, err_flag);
-  else if (acc_lds)
-    launch_rows_f<false, true>(h->max_nt, h->max_nf, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, joint, ld_out, map, gap, err_flag);
-  else
-    launch_rows_f<false, false>(h->max_nt, h->max_nf, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, joint, ld_out, map, gap, err_flag);
-  HIP_TRY(hipGetLastError());
-  return PGM_OK;
-}
-
-extern "C" {
-
-int pgm_rows_plan_run(void *handle, int32_t mode, const uint8_t *codes, int64_t ld_codes, int64_t row0, int64_t n_rows,
-                      double *marg, double *joint, int64_t ld_out, int32_t *map, double *gap, int32_t *err_flag,
-                      void *stream) {
-  STALE_PROBE();
-  return rows_plan_run(handle, mode, codes, ld_codes, row0, n_rows, marg, joint, ld_out, map, gap, err_flag, stream,
-                       false);
-}
-
-// A validated, fully bound pgm_rows_plan_run (a prepared launch): repeated batches over the same
-// buffers pay one argument-free call each instead of re-marshalling thirteen arguments.
-struct RowsJitArgs {  // pgm_rows_jit's parameters, packed as the kernel's argument segment
-  const double *V;
-  const uint8_t *C;
-  int64_t ldc, row0, n;
-  double *M;
-  int64_t ldo;
-  int32_t *MP;
-  double *G;
-  int32_t *E;
-  int32_t mode;
-  int32_t pad;
-};
-
-struct RowsBound {
-  // specialised kernel bound: the packed argument segment and launch shape, launched directly
-  hipFunction_t fn = nullptr;
-  RowsJitArgs args;
-  size_t args_size = sizeof(RowsJitArgs);
-  unsigned blocks = 0;
-  void *handle;
-  int32_t mode;
-  const uint8_t *codes;
-  int64_t ld_codes, row0, n_rows;
-  double *marg, *joint;
-  int64_t ld_out;
-  int32_t *map;
-  double *gap;
-  int32_t *err;
-  void *stream;
-};
-
-int pgm_rows_plan_bind(void *handle, int32_t mode, const uint8_t *codes, int64_t ld_codes, int64_t row0,
-                       int64_t n_rows, double *marg, double *joint, int64_t ld_out, int32_t *map, double *gap,
-                       int32_t *err_flag, void *stream, void **bound) {
-  STALE_PROBE();
-  if (!bound) return fail(PGM_EINVAL, "rows_plan_bind: null output pointer");
-  *bound = nullptr;
-  const bool floor = (mode & PGM_ROWS_FLOOR) != 0;
-  mode &= ~PGM_ROWS_FLOOR;
-  if (floor && (mode & (PGM_ROWS_JOINT | PGM_ROWS_GENERIC | PGM_ROWS_NO_JIT | PGM_ROWS_VALUES_GLOBAL | PGM_ROWS_ONE_GROUP)))
-    return fail(PGM_EINVAL, "rows_plan_bind: the floor kernel exists for the specialised kernel's modes only");
-  const int st = rows_plan_run(handle, mode, codes, ld_codes, row0, n_rows, marg, joint, ld_out, map, gap, err_flag,
-                               stream, true);
-  if (st != PGM_OK) return st;
-  RowsBound *b = new (std::nothrow) RowsBound;
-  if (!b) return fail(PGM_ENOMEM, "rows_plan_bind: out of host memory");
-  b->handle = handle;
-  b->mode = mode;
-  b->codes = codes;
-  b->ld_codes = ld_codes;
-  b->row0 = row0;
-  b->n_rows = n_rows;
-  b->marg = marg;
-  b->joint = joint;
-  b->ld_out = ld_out;
-  b->map = map;
-  b->gap = gap;
-  b->err = err_flag;
-  b->stream = stream;
-  RowsHandle *h = (RowsHandle *)handle;
-  // the same choice rows_plan_run makes (the dry run above compiled the kernel if it applies)
-  if (n_rows > 0 && h->jit_state > 0 &&
-      !(mode & (PGM_ROWS_JOINT | PGM_ROWS_GENERIC | PGM_ROWS_NO_JIT | PGM_ROWS_VALUES_GLOBAL | PGM_ROWS_ONE_GROUP))) {
-    const bool two = rows_jit2_ok(mode, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, h->k.n_marg);
-    b->fn = floor ? (two ? h->jit_fn_floor2 : h->jit_fn_floor) : two ? h->jit_fn2 : h->jit_fn;
-    b->args = RowsJitArgs{h->d_values, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, err_flag, mode, 0};
-    const uint64_t rpb = (uint64_t)jit_wg() * (two ? 2 : 1);
-    b->blocks = (unsigned)(((uint64_t)n_rows + rpb - 1) / rpb);
-  } else if (floor) {
-    delete b;
-    return fail(PGM_EINVAL, "rows_plan_bind: the floor kernel needs the plan-specialised (hipRTC) kernel");
-  }
-  *bound = b;
-  return PGM_OK;
-}
-
-int pgm_rows_bound_run(void *bound) {
-  STALE_PROBE();
-  RowsBound *b = (RowsBound *)bound;
-  if (!b) return fail(PGM_EINVAL, "rows_bound_run: null handle");
-  if (b->fn) {
-    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &b->args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &b->args_size,
-                     HIP_LAUNCH_PARAM_END};
-    HIP_TRY(hipModuleLaunchKernel(b->fn, b->blocks, 1, 1, (unsigned)jit_wg(), 1, 1, 0, S(b->stream), nullptr, extra));
-    return PGM_OK;
-  }
-  return rows_plan_run(b->handle, b->mode, b->codes, b->ld_codes, b->row0, b->n_rows, b->marg, b->joint, b->ld_out,
-                       b->map, b->gap, b->err, b->stream, false);
-}
-
-int pgm_rows_bound_kernel(void *bound, char *name, size_t cap, uint32_t *blocks, uint32_t *wg) {
-  RowsBound *b = (RowsBound *)bound;
-  if (!b || !name || cap == 0) return fail(PGM_EINVAL, "rows_bound_kernel: null argument");
-  RowsHandle *h = (RowsHandle *)b->handle;
-  const char *k = !b->fn ? "" : b->fn == h->jit_fn2 ? "pgm_rows_jit2" : b->fn == h->jit_fn_floor ? "pgm_rows_floor" : b->fn == h->jit_fn_floor2 ? "pgm_rows_floor2" : "pgm_rows_jit";
-  snprintf(name, cap, "%s", k);
-  if (blocks) *blocks = b->fn ? b->blocks : 0;
-  if (wg) *wg = b->fn ? (uint32_t)jit_wg() : 0;
-  return PGM_OK;
-}
-
-int pgm_rows_bound_destroy(void *bound) {
-  STALE_PROBE();
-  delete (RowsBound *)bound;
-  return PGM_OK;
-}
-
-// ---------------------------------------------------------------------------- rows sharded over GPUs
-// One shard of pgm_rows_shard_run on its plan's device, on its own host thread: its rows in chunks of
-// at most shard_chunk_rows(), chunk c on side c % 2 of the handle's kept resources (stream + device
-// buffer): the chunk's rows of the columns the plan reads in (one copy per run of adjacent columns),
-// the plan's pass, its outputs out to the caller's host arrays at the chunk's columns.  Each side's
-// stream orders its own chunks, so chunk c + 2 reuses the buffer only after chunk c's copy-out; with
-// pinned host arrays (pgm_host_alloc / hipHostRegister) the two sides' DMA and kernels overlap.
-static constexpr int64_t shard_chunk_rows() { return 262144; }  // 256 K rows: 36 MB of marginals per chunk
-
-static int shard_side_ready(RowsHandle::ShardSide &sd, size_t need) {
-  if (!sd.s) HIP_TRY(hipStreamCreateWithFlags(&sd.s, hipStreamNonBlocking));
-  if (!sd.h_err) HIP_TRY(hipHostMalloc((void **)&sd.h_err, 64, hipHostMallocDefault));
-  if (sd.cap < need) {
-    if (sd.buf) {
-      HIP_TRY(hipStreamSynchronize(sd.s));
-      (void)hipFree(sd.buf);
-      sd.buf = nullptr;
-      sd.cap = 0;
-    }
-    HIP_TRY(hipMalloc((void **)&sd.buf, need));
-    sd.cap = need;
-  }
-  return PGM_OK;
-}
-
-static int rows_shard_one(RowsHandle *h, int32_t mode, const uint8_t *host_codes, int64_t ld_codes, int64_t r0,
-                          int64_t nr, double *host_marg, int64_t ld_out, int32_t *host_map, int32_t *err_any) {
-  std::lock_guard<std::mutex> lk(h->shard_mu);
-  HIP_TRY(hipSetDevice(h->device));
-  const int64_t chunk = std::min<int64_t>(nr, shard_chunk_rows());
-  // device layout of a chunk: codes [h->n_cols][ldc] (only the plan's columns are written), marg
-  // [n_marg][ldc], map [ldc], err; ldc a multiple of 16 so the two-rows-per-lane kernel takes full chunks
-  const int64_t ldc = (chunk + 15) & ~(int64_t)15;
-  const bool want_m = (mode & PGM_ROWS_MARGINALS) != 0, want_p = (mode & PGM_ROWS_MAP) != 0;
-  const size_t b_codes = (size_t)std::max(h->n_cols, 1) * ldc;
-  const size_t o_marg = (b_codes + 255) & ~(size_t)255;
-  const size_t b_marg = want_m ? (size_t)h->k.n_marg * ldc * sizeof(double) : 0;
-  const size_t o_map = o_marg + ((b_marg + 255) & ~(size_t)255);
-  const size_t b_map = want_p ? (size_t)ldc * sizeof(int32_t) : 0;
-  const size_t o_err = o_map + ((b_map + 255) & ~(size_t)255);
-  const int n_sides = nr > chunk ? 2 : 1;
-  for (int i = 0; i < n_sides; ++i) {
-    const int st = shard_side_ready(h->shard[i], o_err + 256);
-    if (st != PGM_OK) return st;
-    h->shard[i].h_err[0] = 0;
-    HIP_TRY(hipMemsetAsync(h->shard[i].buf + o_err, 0, sizeof(int32_t), h->shard[i].s));
-  }
-  // runs of adjacent plan columns: one 2-D copy each
-  std::vector<std::pair<int, int>> runs;
-  for (int c : h->cols) {
-    if (!runs.empty() && runs.back().first + runs.back().second == c) ++runs.back().second;
-    else runs.push_back({c, 1});
-  }
-  int st = PGM_OK;
-  hipError_t e = hipSuccess;
-  int64_t c = 0;
-  for (int64_t a = r0; a < r0 + nr && st == PGM_OK && e == hipSuccess; a += chunk, ++c) {
-    RowsHandle::ShardSide &sd = h->shard[c % n_sides];
-    const int64_t m = std::min(chunk, r0 + nr - a);
-    uint8_t *d_codes = (uint8_t *)sd.buf;
-    double *d_marg = want_m ? (double *)(sd.buf + o_marg) : nullptr;
-    int32_t *d_map = want_p ? (int32_t *)(sd.buf + o_map) : nullptr;
-    int32_t *d_err = (int32_t *)(sd.buf + o_err);
-    for (size_t k = 0; k < runs.size() && e == hipSuccess; ++k)
-      e = hipMemcpy2DAsync(d_codes + (size_t)runs[k].first * ldc, (size_t)ldc,
-                           host_codes + (size_t)runs[k].first * ld_codes + a, (size_t)ld_codes, (size_t)m,
-                           (size_t)runs[k].second, hipMemcpyHostToDevice, sd.s);
-    if (e != hipSuccess) break;
-    st = rows_plan_run(h, mode, d_codes, ldc, 0, m, d_marg, nullptr, ldc, d_map, nullptr, d_err, sd.s, false);
-    if (st == PGM_OK && want_m)
-      e = hipMemcpy2DAsync(host_marg + a, (size_t)ld_out * sizeof(double), d_marg, (size_t)ldc * sizeof(double),
-                           (size_t)m * sizeof(double), (size_t)h->k.n_marg, hipMemcpyDeviceToHost, sd.s);
-    if (st == PGM_OK && e == hipSuccess && want_p)
-      e = hipMemcpyAsync(host_map + a, d_map, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, sd.s);
-  }
-  int32_t h_err = 0;
-  for (int i = 0; i < n_sides; ++i) {
-    RowsHandle::ShardSide &sd = h->shard[i];
-    if (e == hipSuccess && st == PGM_OK)
-      e = hipMemcpyAsync(sd.h_err, sd.buf + o_err, sizeof(int32_t), hipMemcpyDeviceToHost, sd.s);
-    const hipError_t es = hipStreamSynchronize(sd.s);
-    if (e == hipSuccess) e = es;
-    h_err |= sd.h_err[0];
-  }
-  if (st != PGM_OK) return st;
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(PGM_EDEVICE, "rows_shard_run: %s", hipGetErrorString(e));
-  }
-  if (h_err && err_any) __atomic_fetch_or(err_any, h_err, __ATOMIC_RELAXED);
-  return PGM_OK;
-}
-
-int pgm_rows_shard_run(void *const *handles, int32_t n_shards, int32_t mode, const uint8_t *host_codes,
-                       int64_t ld_codes, int64_t n_cols, int64_t n_rows, double *host_marg, int64_t ld_out,
-                       int32_t *host_map, int32_t *err_any) {
-  STALE_PROBE();
-  if (!handles || n_shards < 1) return fail(PGM_EINVAL, "rows_shard_run: no plan handles");
-  if (n_rows < 0 || ld_codes < n_rows || n_cols < 0) return fail(PGM_EINVAL, "rows_shard_run: bad shape");
-  if (mode & ~(PGM_ROWS_MARGINALS | PGM_ROWS_MAP))
-    return fail(PGM_EINVAL, "rows_shard_run: mode takes PGM_ROWS_MARGINALS | PGM_ROWS_MAP only");
-  if (!(mode & (PGM_ROWS_MARGINALS | PGM_ROWS_MAP))) return fail(PGM_EINVAL, "rows_shard_run: no output requested");
-  if ((mode & PGM_ROWS_MARGINALS) && (!host_marg || ld_out < n_rows))
-    return fail(PGM_EINVAL, "rows_shard_run: marginals need host_marg with ld_out >= n_rows");
-  if ((mode & PGM_ROWS_MAP) && !host_map) return fail(PGM_EINVAL, "rows_shard_run: MAP needs host_map");
-  int32_t n_marg = -1;
-  for (int32_t i = 0; i < n_shards; ++i) {
-    const RowsHandle *h = (const RowsHandle *)handles[i];
-    if (!h) return fail(PGM_EINVAL, "rows_shard_run: null handle %d", i);
-    if (h->n_cols > n_cols) return fail(PGM_EINVAL, "rows_shard_run: plan %d reads column %d of %lld", i, h->n_cols - 1,
-                                        (long long)n_cols);
-    if (n_marg >= 0 && h->k.n_marg != n_marg) return fail(PGM_EINVAL, "rows_shard_run: plans differ (marginal rows)");
-    n_marg = h->k.n_marg;
-  }
-  if (n_rows == 0) return PGM_OK;
-  if (n_cols > 0 && !host_codes) return fail(PGM_EINVAL, "rows_shard_run: null codes");
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  // contiguous shards (distributed.shard_bounds): shard i = rows [i n / S, (i + 1) n / S)
-  std::vector<int> st(n_shards, PGM_OK);
-  std::vector<std::string> msg(n_shards);
-  std::vector<std::thread> th;
-  th.reserve(n_shards);
-  for (int32_t i = 0; i < n_shards; ++i) {
-    const int64_t a = n_rows * i / n_shards, b = n_rows * (i + 1) / n_shards;
-    th.emplace_back([&, i, a, b] {
-      if (b > a) {
-        st[i] = rows_shard_one((RowsHandle *)handles[i], mode, host_codes, ld_codes, a, b - a, host_marg, ld_out,
-                               host_map, err_any);
-        if (st[i] != PGM_OK) msg[i] = g_err;  // the worker's thread-local message
-      }
-    });
-  }
-  for (auto &t : th) t.join();
-  (void)hipSetDevice(prev);
-  for (int32_t i = 0; i < n_shards; ++i)
-    if (st[i] != PGM_OK) return fail(st[i], "rows_shard_run: shard %d: %s", i, msg[i].c_str());
-  return PGM_OK;
-}
-
-// ---------------------------------------------------------------------------- resident ring of batches
-struct PgmRingSlot {  // pgm_ring_slot of the generated source (64 B)
-  const uint8_t *C;
-  int64_t ldc, row0;
-  double *M;
-  int64_t ldo;
-  int32_t *MP;
-  double *G;
-  int64_t pad;
-};
-static_assert(sizeof(PgmRingSlot) == 64, "ring slot layout");
-
-struct RowsRing {
-  RowsHandle *h = nullptr;
-  int32_t mode = 0;
-  int64_t n_rows = 0;
-  uint32_t n_slots = 0;
-  PgmRingSlot *d_slots = nullptr;  // device
-  unsigned *ctl = nullptr;         // pinned host: [0] batches posted, [1] cancel, [2] status (|2: timed out)
-  unsigned *ctl_dev = nullptr;     // its device address
-  unsigned *gctl = nullptr;        // device memory: [0] mirror of ctl[0], [1] host-poll token, [2] stop
-  int32_t *err = nullptr;
-  hipStream_t stream = nullptr;
-  unsigned blocks = 0;
-  bool running = false;
-  bool reset_gctl = true;   // the device counters need zeroing before the next launch (first / after a stop)
-  uint32_t n_batches = 0, posted = 0;  // this launch: batches to run, batches posted
-  uint32_t base = 0;        // absolute number of batches posted over the ring's lifetime before this launch
-  int wall_khz = 100000;    // the device's constant wall clock (timeout ticks)
-};
-
-int pgm_rows_ring_create(void *handle, int32_t mode, int32_t n_slots, const uint8_t *const *codes,
-                         const int64_t *ld_codes, const int64_t *row0, int64_t n_rows, double *const *marg,
-                         int64_t ld_out, int32_t *const *map, double *const *gap, int32_t *err_flag, void *stream,
-                         void **ring) {
-  STALE_PROBE();
-  if (!ring) return fail(PGM_EINVAL, "rows_ring_create: null output pointer");
-  *ring = nullptr;
-  RowsHandle *h = (RowsHandle *)handle;
-  if (!h) return fail(PGM_EINVAL, "rows_ring_create: null plan");
-  if (n_slots < 1 || !codes || !ld_codes || !row0) return fail(PGM_EINVAL, "rows_ring_create: no slots");
-  if (n_rows < 2) return fail(PGM_EINVAL, "rows_ring_create: n_rows %lld < 2", (long long)n_rows);
-  if (mode & ~(PGM_ROWS_MARGINALS | PGM_ROWS_MAP | PGM_ROWS_MAPGAP))
-    return fail(PGM_EINVAL, "rows_ring_create: the ring runs marginals / MAP / MAP-gap outputs only");
-  if (!(mode & (PGM_ROWS_MARGINALS | PGM_ROWS_MAP | PGM_ROWS_MAPGAP)))
-    return fail(PGM_EINVAL, "rows_ring_create: no output requested");
-  if (!rows_jit_ready(h)) return fail(PGM_EINVAL, "rows_ring_create: the ring needs the plan-specialised (hipRTC) kernel");
-  std::vector<PgmRingSlot> slots((size_t)n_slots);
-  for (int32_t i = 0; i < n_slots; ++i) {
-    double *m = (mode & PGM_ROWS_MARGINALS) ? (marg ? marg[i] : nullptr) : nullptr;
-    int32_t *mp = (mode & (PGM_ROWS_MAP | PGM_ROWS_MAPGAP)) && map ? map[i] : nullptr;
-    double *g = (mode & PGM_ROWS_MAPGAP) && gap ? gap[i] : nullptr;
-    if ((mode & PGM_ROWS_MARGINALS) && !m) return fail(PGM_EINVAL, "rows_ring_create: slot %d has no marginal buffer", i);
-    if ((mode & PGM_ROWS_MAP) && !mp) return fail(PGM_EINVAL, "rows_ring_create: slot %d has no MAP buffer", i);
-    if ((mode & PGM_ROWS_MAPGAP) && !g) return fail(PGM_EINVAL, "rows_ring_create: slot %d has no MAP-gap buffer", i);
-    if (h->max_nt > 0 && !codes[i]) return fail(PGM_EINVAL, "rows_ring_create: slot %d has no evidence codes", i);
-    if ((mode & PGM_ROWS_MARGINALS) && ld_out < n_rows)
-      return fail(PGM_EINVAL, "rows_ring_create: ld_out %lld < n_rows %lld", (long long)ld_out, (long long)n_rows);
-    if (!rows2_aligned(mode, codes[i], ld_codes[i], row0[i], n_rows, m, ld_out, mp, g, h->k.n_marg))
-      return fail(PGM_EINVAL, "rows_ring_create: slot %d breaks the two-rows-per-lane contract (even rows, row0 and "
-                  "leading dimensions, 16-B aligned outputs)", i);
-    slots[i] = PgmRingSlot{codes[i], ld_codes[i], row0[i], m, ld_out, mp, g, 0};
-  }
-  RowsRing *rg = new (std::nothrow) RowsRing;
-  if (!rg) return fail(PGM_ENOMEM, "rows_ring_create: out of host memory");
-  rg->h = h;
-  rg->mode = mode;
-  rg->n_rows = n_rows;
-  rg->n_slots = (uint32_t)n_slots;
-  rg->err = err_flag;
-  rg->stream = S(stream);
-  hipError_t e = hipMalloc((void **)&rg->d_slots, sizeof(PgmRingSlot) * slots.size());
-  if (e == hipSuccess)
-    e = hipMemcpy(rg->d_slots, slots.data(), sizeof(PgmRingSlot) * slots.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipHostMalloc((void **)&rg->ctl, 64, hipHostMallocCoherent | hipHostMallocMapped);
-  if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&rg->ctl_dev, rg->ctl, 0);
-  if (e == hipSuccess) e = hipMalloc((void **)&rg->gctl, 64);
-  int dev = 0, cus = 0, per_cu = 0;
-  if (e == hipSuccess) e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess)
-    e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit_fn_ring, ring_wg(), 0);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (rg->d_slots) (void)hipFree(rg->d_slots);
-    if (rg->gctl) (void)hipFree(rg->gctl);
-    if (rg->ctl) (void)hipHostFree(rg->ctl);
-    delete rg;
-    return fail(e == hipErrorOutOfMemory ? PGM_ENOMEM : PGM_EDEVICE, "rows_ring_create: %s", hipGetErrorString(e));
-  }
-  memset(rg->ctl, 0, 64);
-  int khz = 0;
-  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && khz > 0) rg->wall_khz = khz;
-  (void)hipGetLastError();
-  // every workgroup resident at once (one per CU at the default 1,024 threads)
-  rg->blocks = (unsigned)std::max(1, cus * std::max(1, per_cu));
-  *ring = rg;
-  return PGM_OK;
-}
-
-static int ring_start(RowsRing *rg, uint32_t n_batches, double timeout_s, int signal);
-
-int pgm_rows_ring_start(void *ring, uint32_t n_batches, double timeout_s) {
-  STALE_PROBE();
-  return ring_start((RowsRing *)ring, n_batches, timeout_s, 0);
-}
-
-int pgm_rows_ring_start_ready(void *ring, uint32_t n_batches, double timeout_s, double ready_timeout_s) {
-  STALE_PROBE();
-  RowsRing *rg = (RowsRing *)ring;
-  if (!(ready_timeout_s > 0.0) || ready_timeout_s > 600.0)
-    return fail(PGM_EINVAL, "rows_ring_start_ready: ready timeout must be in (0, 600] s");
-  if (rg) __atomic_store_n(&rg->ctl[3], 0u, __ATOMIC_SEQ_CST);
-  const int st = ring_start(rg, n_batches, timeout_s, 1);
-  if (st != PGM_OK || n_batches == 0) return st;
-  const auto t0 = std::chrono::steady_clock::now();
-  while (__atomic_load_n(&rg->ctl[3], __ATOMIC_ACQUIRE) == 0u) {
-    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > ready_timeout_s) {
-      (void)pgm_rows_ring_cancel(ring);
-      return fail(PGM_EDEVICE, "rows_ring_start_ready: the resident grid did not come up within %.3g s",
-                  ready_timeout_s);
-    }
-  }
-  return PGM_OK;
-}
-
-static int ring_start(RowsRing *rg, uint32_t n_batches, double timeout_s, int signal) {
-  if (!rg) return fail(PGM_EINVAL, "rows_ring_start: null ring");
-  if (rg->running) return fail(PGM_EINVAL, "rows_ring_start: the ring is running (finish or cancel it first)");
-  if (!(timeout_s > 0.0) || timeout_s > 600.0) return fail(PGM_EINVAL, "rows_ring_start: timeout must be in (0, 600] s");
-  unsigned long long ticks = (unsigned long long)(timeout_s * (double)rg->wall_khz * 1000.0);
-  // ctl[0] counts batches posted over the ring's lifetime (never reset: a launch's batch b is
-  // absolute batch base + b), so no device-side reset is needed between launches
-  __atomic_store_n(&rg->ctl[1], 0u, __ATOMIC_SEQ_CST);
-  __atomic_store_n(&rg->ctl[2], 0u, __ATOMIC_SEQ_CST);
-  rg->base = __atomic_load_n(&rg->ctl[0], __ATOMIC_SEQ_CST);
-  if (rg->base > 0xF0000000u) return fail(PGM_EINVAL, "rows_ring_start: batch counter exhausted (recreate the ring)");
-  rg->n_batches = n_batches;
-  rg->posted = 0;
-  if (n_batches == 0) return PGM_OK;
-  const double *v = rg->h->d_values;
-  const PgmRingSlot *d = rg->d_slots;
-  unsigned ns = rg->n_slots, nb = n_batches;
-  unsigned *ctl = rg->ctl_dev, *gc = rg->gctl;
-  unsigned base = rg->base;
-  long long n = rg->n_rows;
-  int32_t *ef = rg->err;
-  int32_t md = rg->mode;
-  int sg = signal;
-  void *args[] = {(void *)&v, (void *)&d, &ns, (void *)&ctl, (void *)&gc, &nb, &base, &n, (void *)&ef, &md, &ticks, &sg};
-  if (rg->reset_gctl) {  // mirror = base, token free, stop clear, readiness count 0
-    unsigned init[16] = {base, 0u, 0u};
-    HIP_TRY(hipMemcpyAsync(rg->gctl, init, sizeof init, hipMemcpyHostToDevice, rg->stream));
-    HIP_TRY(hipStreamSynchronize(rg->stream));
-    rg->reset_gctl = false;
-  }
-  HIP_TRY(hipModuleLaunchKernel(rg->h->jit_fn_ring, rg->blocks, 1, 1, (unsigned)ring_wg(), 1, 1, 0, rg->stream, args,
-                                nullptr));
-  rg->running = true;
-  return PGM_OK;
-}
-
-int pgm_rows_ring_post(void *ring, uint32_t n_posted) {
-  RowsRing *rg = (RowsRing *)ring;
-  if (!rg) return fail(PGM_EINVAL, "rows_ring_post: null ring");
-  if (!rg->running) return fail(PGM_EINVAL, "rows_ring_post: the ring is not running");
-  rg->posted = std::max(rg->posted, __atomic_load_n(&rg->ctl[0], __ATOMIC_SEQ_CST) - rg->base);  // direct stores
-  if (n_posted < rg->posted || n_posted > rg->n_batches)
-    return fail(PGM_EINVAL, "rows_ring_post: %u batches posted, %u started, asked for %u", rg->posted, rg->n_batches,
-                n_posted);
-  rg->posted = n_posted;
-  // a sequentially consistent store: drained from the store buffer before this call returns
-  __atomic_store_n(&rg->ctl[0], rg->base + n_posted, __ATOMIC_SEQ_CST);
-  return PGM_OK;
-}
-
-static int ring_wait(RowsRing *rg) {
-  HIP_TRY(hipStreamSynchronize(rg->stream));
-  rg->running = false;
-  return PGM_OK;
-}
-
-int pgm_rows_ring_finish(void *ring) {
-  STALE_PROBE();
-  RowsRing *rg = (RowsRing *)ring;
-  if (!rg) return fail(PGM_EINVAL, "rows_ring_finish: null ring");
-  if (!rg->running) return PGM_OK;
-  rg->posted = std::max(rg->posted, __atomic_load_n(&rg->ctl[0], __ATOMIC_SEQ_CST) - rg->base);  // direct stores
-  if (rg->posted < rg->n_batches)
-    return fail(PGM_EINVAL, "rows_ring_finish: only %u of %u batches posted (post them or cancel)", rg->posted,
-                rg->n_batches);
-  const int st = ring_wait(rg);
-  if (st != PGM_OK) return st;
-  if (__atomic_load_n(&rg->ctl[2], __ATOMIC_SEQ_CST) & 2u) {
-    rg->reset_gctl = true;
-    return fail(PGM_EDEVICE, "rows_ring_finish: the resident kernel timed out waiting for a batch");
-  }
-  return PGM_OK;
-}
-
-int pgm_rows_ring_cancel(void *ring) {
-  STALE_PROBE();
-  RowsRing *rg = (RowsRing *)ring;
-  if (!rg) return fail(PGM_EINVAL, "rows_ring_cancel: null ring");
-  if (!rg->running) return PGM_OK;
-  __atomic_store_n(&rg->ctl[1], 1u, __ATOMIC_SEQ_CST);
-  rg->reset_gctl = true;
-  return ring_wait(rg);
-}
-
-int pgm_rows_ring_counter(void *ring, uint32_t **counter, uint32_t *base) {
-  RowsRing *rg = (RowsRing *)ring;
-  if (!rg || !counter || !base) return fail(PGM_EINVAL, "rows_ring_counter: null argument");
-  *counter = rg->ctl;
-  *base = rg->base;
-  return PGM_OK;
-}
-
-int pgm_rows_ring_kernel(void *ring, char *name, size_t cap, uint32_t *blocks, uint32_t *wg) {
-  RowsRing *rg = (RowsRing *)ring;
-  if (!rg || !name || cap == 0) return fail(PGM_EINVAL, "rows_ring_kernel: null argument");
-  snprintf(name, cap, "%s", "pgm_rows_ring");
-  if (blocks) *blocks = rg->blocks;
-  if (wg) *wg = (uint32_t)ring_wg();
-  return PGM_OK;
-}
-
-int pgm_rows_ring_destroy(void *ring) {
-  STALE_PROBE();
-  RowsRing *rg = (RowsRing *)ring;
-  if (!rg) return PGM_OK;
-  int st = PGM_OK;
-  if (rg->running) st = pgm_rows_ring_cancel(rg);
-  if (rg->d_slots) (void)hipFree(rg->d_slots);
-  if (rg->gctl) (void)hipFree(rg->gctl);
-  if (rg->ctl) (void)hipHostFree(rg->ctl);
-  delete rg;
-  return st;
-}
-
-// internal (pgm_internal.h): what the direct AQL path (pgmdq.cpp) needs to dispatch a bound
-// specialised launch on its own queue; PGM_EINVAL when the bound launch is not the hipRTC kernel
-int pgmi_rows_bound_jit(void *bound, pgmi_jit_launch *out) {
-  RowsBound *b = (RowsBound *)bound;
-  if (!b || !out) return fail(PGM_EINVAL, "rows_bound_jit: null argument");
-  if (!b->fn) return fail(PGM_EINVAL, "direct launch needs the plan-specialised kernel (hipRTC), not an AOT kernel");
-  RowsHandle *h = (RowsHandle *)b->handle;
-  if (h->jit_code.empty()) return fail(PGM_EINVAL, "direct launch: no code object kept for this plan");
-  out->code = h->jit_code.data();
-  out->code_size = h->jit_code.size();
-  out->kernel = b->fn == h->jit_fn2 ? "pgm_rows_jit2" : b->fn == h->jit_fn_floor ? "pgm_rows_floor" : b->fn == h->jit_fn_floor2 ? "pgm_rows_floor2" : "pgm_rows_jit";
-  out->args = &b->args;
-  out->args_size = b->args_size;
-  out->blocks = b->blocks;
-  out->wg = (unsigned)jit_wg();
-  out->owner = h;
-  out->write_through = h->jit_write_through ? 1 : 0;
   return PGM_OK;
 }
 

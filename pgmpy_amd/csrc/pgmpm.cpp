@@ -2,7 +2,7 @@
 // gfx950 with hipRTC at run time): the fused product + marginal, n-ary products, separator marginals
 // and two-marginal passes of a batched calibration (pgmpy ExactInference.py:770-805), merged per
 // dependency level into one launch, plus the on-disk code-object cache shared with the specialised
-// row kernels of pgmhip.hip.  C-ABI: include/pgmhip.h (pgm_product_n_marginal_bind, pgm_pm_*).
+// row kernels of pgmrows_plan.cpp.  C-ABI: include/pgmhip.h (pgm_product_n_marginal_bind, pgm_pm_*).
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 #include <sys/stat.h>

@@ -160,7 +160,7 @@ class PatternPlan:
     def kernel_name(self):
         """The device kernel pgm_rows_plan_run launches for this plan's marginal/MAP outputs: the
         plan-specialised hipRTC kernel `pgm_rows_jit` when every component has one query variable and
-        no hidden variable (pgmhip.hip rows_jit_source; if hipRTC is unavailable the AOT
+        no hidden variable (pgmrows_plan.cpp rows_jit_source; if hipRTC is unavailable the AOT
         k_rows_affine / k_rows run instead), else the table-driven k_rows."""
         if self.kind != "fused":
             return None

@@ -354,6 +354,41 @@ def test_specialised_row_kernel_source_compiles_for_gfx950():
         assert r.returncode == 0, r.stderr
 
 
+def row_source_plans():
+    """name -> PatternPlan of the model plans in tests/golden/rows_jit_source.json: the munin C3 template
+    of the test above, alarm and asia plans with two or three unobserved variables (all specialisable)."""
+    import random
+
+    from pgmpy_amd.inference.plan import PatternPlan
+    from pgmpy_amd.utils import get_example_model
+
+    plans = {}
+    for name, net, seed, k in (("munin_c3", "munin", 0, 3), ("alarm_3", "alarm", 0, 3), ("alarm_2", "alarm", 1, 2),
+                               ("asia_2", "asia", 0, 2), ("asia_3", "asia", 1, 3)):
+        m = get_example_model(net)
+        missing = random.Random(seed).sample(sorted(m.nodes()), k)
+        obs = sorted(v for v in m.nodes() if v not in missing)
+        plans[name] = PatternPlan(m, missing, obs, {v: i for i, v in enumerate(obs)})
+    return plans
+
+
+def test_specialised_row_kernel_source_matches_golden():
+    """The generated source of the plan-specialised row kernels is, byte for byte, what the generator
+    emitted before it moved out of pgmhip.hip into pgmrows_plan.cpp: length and SHA-256 per plan, recorded
+    with the library built from the commit before the move (tests/golden/rows_jit_source.json)."""
+    import hashlib
+    import json
+
+    with open(os.path.join(os.path.dirname(__file__), "golden", "rows_jit_source.json")) as f:
+        golden = json.load(f)["plans"]
+    plans = row_source_plans()
+    assert len(plans) == 5
+    for name, plan in plans.items():
+        assert plan.kernel_name() == "pgm_rows_jit", name
+        src = plan.specialised_source().encode()
+        assert {"length": len(src), "sha256": hashlib.sha256(src).hexdigest()} == golden[name], name
+
+
 def test_program_dependency_levels():
     """Levelled Program (pgmpy_amd/program.py): RAW, WAR and WAW hazards order steps into levels;
     independent steps share a level; views of one buffer conflict.  No launches (host only)."""
