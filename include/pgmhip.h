@@ -480,6 +480,39 @@ int pgm_rows_plan_run(void *handle, int32_t mode, const uint8_t *codes, int64_t 
                       int64_t n_rows, double *marg, double *joint, int64_t ld_out, int32_t *map,
                       double *gap, int32_t *err_flag, void *stream);
 
+/* Which kernel pgm_rows_plan_run would launch for this plan and these launch arguments, and how.
+ * Host-only (no HIP call, no device, no handle): the plan is compiled, the arguments are checked as
+ * pgm_rows_plan_run checks them (same order, same messages), and the pointers are inspected for NULL
+ * and alignment only (the two-rows-per-thread contract of pgm_rows_jit2).  jit_available: whether the
+ * plan-specialised (hipRTC) kernel can be had; with 0 the ahead-of-time kernels are chosen, as when
+ * hipRTC fails.  pgm_rows_plan_run and pgm_rows_plan_bind take their choice from the same function.
+ * n_rows <= 0 launches nothing: kernel PGM_RK_NONE, blocks 0.  For tests and inspection. */
+enum pgm_rows_kernel {
+  PGM_RK_NONE = -1,
+  PGM_RK_JIT = 0,    /* pgm_rows_jit: plan-specialised, one row per thread                       */
+  PGM_RK_JIT2 = 1,   /* pgm_rows_jit2: plan-specialised, two rows per thread, 16-B stores        */
+  PGM_RK_AFFINE = 2, /* k_rows_affine<values_lds, nf, nt, map>: all-affine plans                 */
+  PGM_RK_TABLE = 3   /* k_rows<values_lds, acc_lds, maxfc, maxt>: table-driven components        */
+};
+typedef struct {
+  int32_t kernel;     /* enum pgm_rows_kernel */
+  int32_t values_lds; /* CPT values staged in LDS (else read from global memory) */
+  int32_t acc_lds;    /* TABLE: marginal accumulators in LDS (else none, or in marg itself) */
+  int32_t maxfc;      /* TABLE: factor slots of the instance (2, 4, 8, 16) */
+  int32_t maxt;       /* TABLE: evidence terms of the instance (4, 8, 48) */
+  int32_t nf;         /* AFFINE: factor slots of the instance (1, 2, 4) */
+  int32_t nt;         /* AFFINE: evidence terms of the instance (4, 8) */
+  int32_t map;        /* AFFINE: the instance that carries the MAP bookkeeping */
+  int32_t rg;         /* 64-row groups per workgroup (1 for the specialised kernels) */
+  uint32_t blocks;    /* workgroups */
+  uint32_t wg;        /* work-items per workgroup */
+  uint32_t lds_bytes; /* AOT: dynamic LDS of the launch; specialised: its static value array */
+} pgm_rows_launch_info_t;
+int pgm_rows_launch_info(const pgm_rows_plan *plan, int32_t mode, const uint8_t *codes, int64_t ld_codes,
+                         int64_t row0, int64_t n_rows, const double *marg, const double *joint, int64_t ld_out,
+                         const int32_t *map, const double *gap, int32_t jit_available,
+                         pgm_rows_launch_info_t *info);
+
 /* Prepared launch: validates the same arguments as pgm_rows_plan_run once and binds them; each
  * pgm_rows_bound_run then launches that pass (same result as the unbound call).  The buffers and the
  * plan handle must outlive the bound handle.  Replaces the per-batch Python call of predict()'s

@@ -6,3 +6,4 @@ predict_probability; every factor operation runs in hand-written HIP kernels
 (pgmpy_amd/csrc/pgmhip.hip, pgmrows.hip) reached through the C-ABI of include/pgmhip.h.
 """
 __version__ = "0.1.0"
+ABI_VERSION = 25  # pgm_version() of the library the ctypes mirrors in _native.py are written for

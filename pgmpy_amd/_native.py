@@ -172,6 +172,42 @@ class RowsPlan(ctypes.Structure):
 
 
 _P = ctypes.c_void_p
+RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
+RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
+
+
+class RowsLaunchInfo(ctypes.Structure):
+    """pgm_rows_launch_info_t: the kernel and launch pgm_rows_plan_run would make (host-only query)."""
+    _fields_ = [
+        ("kernel", ctypes.c_int32),
+        ("values_lds", ctypes.c_int32),
+        ("acc_lds", ctypes.c_int32),
+        ("maxfc", ctypes.c_int32),
+        ("maxt", ctypes.c_int32),
+        ("nf", ctypes.c_int32),
+        ("nt", ctypes.c_int32),
+        ("map", ctypes.c_int32),
+        ("rg", ctypes.c_int32),
+        ("blocks", ctypes.c_uint32),
+        ("wg", ctypes.c_uint32),
+        ("lds_bytes", ctypes.c_uint32),
+    ]
+
+
+def rows_launch_info(plan, mode, n_rows, row0=0, ld_codes=None, ld_out=None, codes=64, marg=64, joint=64, map_=64,
+                     gap=64, jit=True):
+    """RowsLaunchInfo of a pgm_rows_plan for a launch (pgm_rows_launch_info; no device).  The pointers
+    are addresses (ints or None): only NULL and alignment matter."""
+    info = RowsLaunchInfo()
+    ld_codes = row0 + n_rows if ld_codes is None else ld_codes
+    ld_out = n_rows if ld_out is None else ld_out
+    P = ctypes.c_void_p
+    check(load_library().pgm_rows_launch_info(ctypes.byref(plan), int(mode), P(codes), int(ld_codes), int(row0),
+                                              int(n_rows), P(marg), P(joint), int(ld_out), P(map_), P(gap),
+                                              1 if jit else 0, ctypes.byref(info)), "rows_launch_info")
+    return info
+
+
 _SIGS = {
     "pgm_version": ([], ctypes.c_int),
     "pgm_last_error": ([ctypes.c_char_p, ctypes.c_size_t], ctypes.c_int),
@@ -242,6 +278,9 @@ _SIGS = {
     "pgm_argmax": ([_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, _P, _P], ctypes.c_int),
     "pgm_rows_plan_create": ([ctypes.POINTER(RowsPlan), _P, ctypes.POINTER(_P)], ctypes.c_int),
     "pgm_rows_plan_destroy": ([_P], ctypes.c_int),
+    "pgm_rows_launch_info": ([ctypes.POINTER(RowsPlan), ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int64,
+                              ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P, ctypes.c_int32,
+                              ctypes.POINTER(RowsLaunchInfo)], ctypes.c_int),
     "pgm_rows_plan_run": ([_P, ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, _P,
                            ctypes.c_int64, _P, _P, _P, _P], ctypes.c_int),
     "pgm_rows_plan_bind": ([_P, ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, _P,

@@ -65,6 +65,24 @@ PGM_ROWS_LOCAL bool rows_jit2_ok(int32_t mode, const uint8_t *codes, int64_t ld_
                                  const double *marg, int64_t ld_out, const int32_t *map, const double *gap,
                                  int n_marg);
 
+// The launch of a compiled plan: pgm_rows_plan_run's argument checks (rows_launch_check, in its order,
+// with its messages), then which kernel runs, with which template arguments, grid and LDS
+// (rows_launch_choose).  rows_plan_run, pgm_rows_plan_bind and pgm_rows_launch_info all go through
+// these two, so what is reported is what runs.  jit: the plan-specialised kernel is compiled and loaded
+// (callers ask for it only when rows_jit_mode(mode) holds and the plan has a generated source).
+PGM_ROWS_LOCAL bool rows_jit_mode(int32_t mode);  // no mode bit rules the specialised kernel out
+PGM_ROWS_LOCAL int rows_launch_check(const RowsPlan &p, int32_t mode, const uint8_t *codes, int64_t n_rows,
+                                     const double *marg, const double *joint, int64_t ld_out, const int32_t *map,
+                                     const double *gap);
+PGM_ROWS_LOCAL int rows_launch_choose(const RowsPlan &p, int32_t mode, const uint8_t *codes, int64_t ld_codes,
+                                      int64_t row0, int64_t n_rows, const double *marg, int64_t ld_out,
+                                      const int32_t *map, const double *gap, bool jit, pgm_rows_launch_info_t *info);
+// pgm_rows_launch_info without STALE_PROBE: compile, check, choose
+PGM_ROWS_LOCAL int rows_launch_info(const pgm_rows_plan *pl, int32_t mode, const uint8_t *codes, int64_t ld_codes,
+                                    int64_t row0, int64_t n_rows, const double *marg, const double *joint,
+                                    int64_t ld_out, const int32_t *map, const double *gap, bool jit_available,
+                                    pgm_rows_launch_info_t *info);
+
 // launch geometry the generated source is written for (the launchers must use the same numbers)
 PGM_ROWS_LOCAL int jit_wg();  // workgroup size of pgm_rows_jit / jit2 / floor / floor2
 // workgroup size of the ring kernel: 256 = one wave per

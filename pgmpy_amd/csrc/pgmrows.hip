@@ -324,6 +324,7 @@ __global__ __launch_bounds__(64 * PGM_ROWS_MAX_COMP) void k_rows_affine(
     for (int k = 0; k < NF; ++k) S[j][k] = cd.a_S[j][k];
   }
   const int nt = cd.nt;
+  const bool has_q = cd.nq != 0;
   const uint32_t P = (uint32_t)cd.P;
   const int32_t ms = cd.mstride;
   double *mrow = marg + (int64_t)cd.marg0 * ld_out;
@@ -345,20 +346,25 @@ __global__ __launch_bounds__(64 * PGM_ROWS_MAX_COMP) void k_rows_affine(
   for (int j = 0; j < NT; ++j) nx[j] = 0;
   const int vlo = cd.val_lo, vhi = cd.val_hi;
   double t[4];
+  // (a component without factors has vlo == vhi == 0: nothing to stage, and vhi - 1 is no index)
   if constexpr (VL) {
+    if (vlo < vhi) {
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = vlo + u * 64 + lane;
-      t[u] = gvals[i < vhi ? i : vhi - 1];
+      for (int u = 0; u < 4; ++u) {
+        const int i = vlo + u * 64 + lane;
+        t[u] = gvals[i < vhi ? i : vhi - 1];
+      }
     }
   }
   if (nt > 0) load_codes(0, nx);
   if constexpr (VL) {
     if (lane == 0) svals[p.one_idx] = 1.0;
+    if (vlo < vhi) {
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {  // clamped lanes rewrite the last value with itself: no branches
-      const int i = vlo + u * 64 + lane;
-      svals[i < vhi ? i : vhi - 1] = t[u];
+      for (int u = 0; u < 4; ++u) {  // clamped lanes rewrite the last value with itself: no branches
+        const int i = vlo + u * 64 + lane;
+        svals[i < vhi ? i : vhi - 1] = t[u];
+      }
     }
     for (int base = vlo + 256; base < vhi; base += 256) {
 #pragma unroll
@@ -446,7 +452,8 @@ __global__ __launch_bounds__(64 * PGM_ROWS_MAX_COMP) void k_rows_affine(
     }
     // impossible evidence (zero total mass): every marginal is 0/0 = NaN and np.argmax gives 0
     const bool dead = !(z > 0.0);
-    if (do_marg && live) {  // normalised marginal streamed straight to HBM
+    // (a component without a query dim has P == 1 and no marginal row: nothing to store, as in k_rows)
+    if (do_marg && live && has_q) {  // normalised marginal streamed straight to HBM
       const double inv = dead ? __builtin_nan("") : 1.0 / mass;
       double *out = mrow + r;
 #pragma unroll
@@ -506,49 +513,50 @@ static void launch_affine_m(bool do_map, dim3 g, dim3 b, size_t lds, hipStream_t
     hipLaunchKernelGGL((k_rows_affine<VL, NF, NT, false>), g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, ldo, map, gap, err);
 }
 
+// the launchers take the template arguments rows_launch_choose picked (pgm_rows_launch_info_t)
 template <bool VL>
-static void launch_affine(int max_nf, int max_nt, bool do_map, dim3 g, dim3 b, size_t lds, hipStream_t s,
+static void launch_affine(int nf, int nt, bool do_map, dim3 g, dim3 b, size_t lds, hipStream_t s,
                           const RowsK &k, const double *v, const int32_t *t, const uint8_t *codes, int64_t ldc,
                           int64_t row0, int64_t n, int32_t mode, int32_t RG, double *marg, int64_t ldo,
                           int32_t *map, double *gap, int32_t *err) {
 #define PGM_AFF(NF, NT) launch_affine_m<VL, NF, NT>(do_map, g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, ldo, map, gap, err)
-  if (max_nt <= 4) {
-    if (max_nf <= 1) PGM_AFF(1, 4);
-    else if (max_nf <= 2) PGM_AFF(2, 4);
+  if (nt == 4) {
+    if (nf == 1) PGM_AFF(1, 4);
+    else if (nf == 2) PGM_AFF(2, 4);
     else PGM_AFF(4, 4);
   } else {
-    if (max_nf <= 1) PGM_AFF(1, 8);
-    else if (max_nf <= 2) PGM_AFF(2, 8);
+    if (nf == 1) PGM_AFF(1, 8);
+    else if (nf == 2) PGM_AFF(2, 8);
     else PGM_AFF(4, 8);
   }
 #undef PGM_AFF
 }
 
 template <bool VL, bool AL, int MAXT>
-static void launch_rows_t(int max_nf, dim3 g, dim3 b, size_t lds, hipStream_t s, const RowsK &k, const double *v,
+static void launch_rows_t(int maxfc, dim3 g, dim3 b, size_t lds, hipStream_t s, const RowsK &k, const double *v,
                           const int32_t *t, const uint8_t *codes, int64_t ldc, int64_t row0, int64_t n, int32_t mode,
                           int32_t RG, double *marg, double *joint, int64_t ldo, int32_t *map, double *gap, int32_t *err) {
-  if (max_nf <= 2)
+  if (maxfc == 2)
     hipLaunchKernelGGL((k_rows<VL, AL, 2, MAXT>), g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
-  else if (max_nf <= 4)
+  else if (maxfc == 4)
     hipLaunchKernelGGL((k_rows<VL, AL, 4, MAXT>), g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
-  else if (max_nf <= 8)
+  else if (maxfc == 8)
     hipLaunchKernelGGL((k_rows<VL, AL, 8, MAXT>), g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
   else
     hipLaunchKernelGGL((k_rows<VL, AL, PGM_ROWS_MAX_FAC, MAXT>), g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
 }
 
 template <bool VL, bool AL>
-static void launch_rows_f(int max_nt, int max_nf, dim3 g, dim3 b, size_t lds, hipStream_t s, const RowsK &k,
+static void launch_rows_f(int maxt, int maxfc, dim3 g, dim3 b, size_t lds, hipStream_t s, const RowsK &k,
                           const double *v, const int32_t *t, const uint8_t *codes, int64_t ldc, int64_t row0, int64_t n,
                           int32_t mode, int32_t RG, double *marg, double *joint, int64_t ldo, int32_t *map, double *gap,
                           int32_t *err) {
-  if (max_nt <= 4)
-    launch_rows_t<VL, AL, 4>(max_nf, g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
-  else if (max_nt <= 8)
-    launch_rows_t<VL, AL, 8>(max_nf, g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
+  if (maxt == 4)
+    launch_rows_t<VL, AL, 4>(maxfc, g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
+  else if (maxt == 8)
+    launch_rows_t<VL, AL, 8>(maxfc, g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
   else
-    launch_rows_t<VL, AL, PGM_ROWS_MAX_EV>(max_nf, g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
+    launch_rows_t<VL, AL, PGM_ROWS_MAX_EV>(maxfc, g, b, lds, s, k, v, t, codes, ldc, row0, n, mode, RG, marg, joint, ldo, map, gap, err);
 }
 
 // ----------------------------------------------------------------------------- plan handle
@@ -661,6 +669,14 @@ int pgm_rows_plan_source(const pgm_rows_plan *pl, char *buf, size_t len, size_t 
   return PGM_OK;
 }
 
+int pgm_rows_launch_info(const pgm_rows_plan *pl, int32_t mode, const uint8_t *codes, int64_t ld_codes, int64_t row0,
+                         int64_t n_rows, const double *marg, const double *joint, int64_t ld_out, const int32_t *map,
+                         const double *gap, int32_t jit_available, pgm_rows_launch_info_t *info) {
+  STALE_PROBE();
+  return rows_launch_info(pl, mode, codes, ld_codes, row0, n_rows, marg, joint, ld_out, map, gap, jit_available != 0,
+                          info);
+}
+
 int pgm_rows_plan_destroy(void *handle) {
   STALE_PROBE();
   RowsHandle *h = (RowsHandle *)handle;
@@ -691,80 +707,49 @@ static int rows_plan_run(void *handle, int32_t mode, const uint8_t *codes, int64
   RowsHandle *h = (RowsHandle *)handle;
   if (!h) return pgmi_failf(PGM_EINVAL, "rows_plan_run: null handle");
   if (n_rows <= 0) return PGM_OK;
-  if (h->max_nt > 0 && !codes) return pgmi_failf(PGM_EINVAL, "rows_plan_run: null codes");
-  if ((mode & PGM_ROWS_MARGINALS) && !marg) return pgmi_failf(PGM_EINVAL, "rows_plan_run: marginals requested, marg is null");
-  if ((mode & PGM_ROWS_JOINT) && !joint) return pgmi_failf(PGM_EINVAL, "rows_plan_run: joint requested, joint is null");
-  if ((mode & PGM_ROWS_JOINT) && h->k.n_comp != 1)
-    return pgmi_failf(PGM_EINVAL, "rows_plan_run: joint output needs a single-component plan");
-  if ((mode & PGM_ROWS_MAP) && !map) return pgmi_failf(PGM_EINVAL, "rows_plan_run: MAP requested, map is null");
-  if ((mode & PGM_ROWS_MAPGAP) && !gap) return pgmi_failf(PGM_EINVAL, "rows_plan_run: MAP gap requested, gap is null");
-  if ((mode & (PGM_ROWS_MARGINALS | PGM_ROWS_JOINT)) && ld_out < n_rows)
-    return pgmi_failf(PGM_EINVAL, "rows_plan_run: ld_out %lld < n_rows %lld", (long long)ld_out, (long long)n_rows);
-  // one workgroup = 64 rows x RG row groups; W waves split the components
+  int st = rows_launch_check(*h, mode, codes, n_rows, marg, joint, ld_out, map, gap);
+  if (st != PGM_OK) return st;
+  // which kernel, with which template arguments, grid and LDS: rows_launch_choose (pgmrows_plan.cpp)
+  const bool jit = rows_jit_mode(mode) && rows_jit_ready(h);
+  pgm_rows_launch_info_t li;
+  st = rows_launch_choose(*h, mode, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, jit, &li);
+  if (st != PGM_OK) return st;
+  if (dry) return PGM_OK;
   RowsK k = h->k;
   k.n_waves = k.n_comp;  // one wave per component
-  const size_t kLds = 64 * 1024;
-  size_t vals_bytes = (size_t)((k.n_values + 1) & ~1) * sizeof(double);
-  const bool vals_lds = vals_bytes <= 40 * 1024 && !(mode & PGM_ROWS_VALUES_GLOBAL);
-  if (!vals_lds) vals_bytes = 0;
-  const size_t x_bytes = (size_t)k.n_comp * 64 * (2 * sizeof(double) + sizeof(int32_t));
-  const size_t acc_bytes = (size_t)k.n_marg * 64 * sizeof(double);
-  const bool acc_lds = (mode & PGM_ROWS_MARGINALS) && h->any_table && vals_bytes + x_bytes + acc_bytes <= kLds;
-  const size_t lds = vals_bytes + x_bytes + (acc_lds ? acc_bytes : 0);
-  const uint64_t groups = ((uint64_t)n_rows + 63) / 64;
-  // amortise the LDS staging of the CPT values over several row groups once the grid is large
-  int32_t RG = 1;
-  if (vals_lds && !(mode & PGM_ROWS_ONE_GROUP)) RG = (int32_t)std::max<uint64_t>(1, std::min<uint64_t>(8, groups / 4096));
   hipStream_t s = S(stream);
   const double *v = h->d_values;
   const int32_t *t = h->d_desc;
-  if (!(mode & (PGM_ROWS_JOINT | PGM_ROWS_GENERIC | PGM_ROWS_NO_JIT | PGM_ROWS_VALUES_GLOBAL | PGM_ROWS_ONE_GROUP)) &&
-      rows_jit_ready(h)) {
-    const bool two = rows_jit2_ok(mode, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, h->k.n_marg);
-    const uint64_t rpb = (uint64_t)jit_wg() * (two ? 2 : 1);  // rows per block
-    const uint64_t jblocks = ((uint64_t)n_rows + rpb - 1) / rpb;
-    if (jblocks > 0x7fffffffull) return pgmi_failf(PGM_EINVAL, "rows_plan_run: too many rows");
-    if (dry) return PGM_OK;
+  if (li.kernel == PGM_RK_JIT || li.kernel == PGM_RK_JIT2) {
     const uint8_t *cp = codes;
     int64_t ldc = ld_codes, r0 = row0, nr = n_rows, ldo = ld_out;
     double *mg = marg, *gp = gap;
     int32_t *mp = map, *ef = err_flag;
     int32_t md = mode;
     void *args[] = {(void *)&v, (void *)&cp, &ldc, &r0, &nr, (void *)&mg, &ldo, (void *)&mp, (void *)&gp, (void *)&ef, &md};
-    HIP_TRY(hipModuleLaunchKernel(two ? h->jit_fn2 : h->jit_fn, (unsigned)jblocks, 1, 1, (unsigned)jit_wg(), 1, 1, 0, s,
+    HIP_TRY(hipModuleLaunchKernel(li.kernel == PGM_RK_JIT2 ? h->jit_fn2 : h->jit_fn, li.blocks, 1, 1, li.wg, 1, 1, 0, s,
                                   args, nullptr));
     return PGM_OK;
   }
-  if (h->all_affine && !(mode & PGM_ROWS_JOINT) && !(mode & PGM_ROWS_GENERIC)) {
-    RG = 1;
-    if (vals_lds && !(mode & PGM_ROWS_ONE_GROUP))
-      RG = (int32_t)std::max<uint64_t>(1, std::min<uint64_t>(8, groups / 4096));
-    const uint64_t ablocks = (groups + RG - 1) / RG;
-    if (ablocks > 0x7fffffffull) return pgmi_failf(PGM_EINVAL, "rows_plan_run: too many rows");
-    const bool do_map = (mode & (PGM_ROWS_MAP | PGM_ROWS_MAPGAP)) != 0;
-    // exchange slots: masses only, unless MAP digits / gaps are combined too
-    const size_t x_aff = k.n_comp > 1 ? (size_t)k.n_comp * 64 * (do_map ? 2 * sizeof(double) + sizeof(int32_t) : sizeof(double)) : 0;
-    const dim3 ag((unsigned)ablocks), ab(64 * k.n_comp);
-    if (dry) return PGM_OK;
-    if (vals_lds)
-      launch_affine<true>(h->max_nf, h->max_nt, do_map, ag, ab, vals_bytes + x_aff, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, ld_out, map, gap, err_flag);
+  const dim3 g(li.blocks), b(li.wg);
+  const size_t lds = li.lds_bytes;
+  const int32_t RG = li.rg;
+  if (li.kernel == PGM_RK_AFFINE) {
+    if (li.values_lds)
+      launch_affine<true>(li.nf, li.nt, li.map != 0, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, ld_out, map, gap, err_flag);
     else
-      launch_affine<false>(h->max_nf, h->max_nt, do_map, ag, ab, vals_bytes + x_aff, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, ld_out, map, gap, err_flag);
+      launch_affine<false>(li.nf, li.nt, li.map != 0, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, ld_out, map, gap, err_flag);
     HIP_TRY(hipGetLastError());
     return PGM_OK;
   }
-  const uint64_t blocks = (groups + RG - 1) / RG;
-  if (blocks > 0x7fffffffull) return pgmi_failf(PGM_EINVAL, "rows_plan_run: too many rows");
-  const dim3 g((unsigned)blocks), b(64 * k.n_waves);
-  if (dry) return PGM_OK;
-  if (vals_lds && acc_lds)
-    launch_rows_f<true, true>(h->max_nt, h->max_nf, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, joint, ld_out, map, gap, err_flag);
-  else if (vals_lds)
-    launch_rows_f<true, false>(h->max_nt, h->max_nf, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, joint, ld_out, map, gap, err_flag);
-  else if (acc_lds)
-    launch_rows_f<false, true>(h->max_nt, h->max_nf, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, joint, ld_out, map, gap, err_flag);
+  if (li.values_lds && li.acc_lds)
+    launch_rows_f<true, true>(li.maxt, li.maxfc, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, joint, ld_out, map, gap, err_flag);
+  else if (li.values_lds)
+    launch_rows_f<true, false>(li.maxt, li.maxfc, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, joint, ld_out, map, gap, err_flag);
+  else if (li.acc_lds)
+    launch_rows_f<false, true>(li.maxt, li.maxfc, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, joint, ld_out, map, gap, err_flag);
   else
-    launch_rows_f<false, false>(h->max_nt, h->max_nf, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, joint, ld_out, map, gap, err_flag);
+    launch_rows_f<false, false>(li.maxt, li.maxfc, g, b, lds, s, k, v, t, codes, ld_codes, row0, n_rows, mode, RG, marg, joint, ld_out, map, gap, err_flag);
   HIP_TRY(hipGetLastError());
   return PGM_OK;
 }
@@ -842,13 +827,13 @@ int pgm_rows_plan_bind(void *handle, int32_t mode, const uint8_t *codes, int64_t
   b->stream = stream;
   RowsHandle *h = (RowsHandle *)handle;
   // the same choice rows_plan_run makes (the dry run above compiled the kernel if it applies)
-  if (n_rows > 0 && h->jit_state > 0 &&
-      !(mode & (PGM_ROWS_JOINT | PGM_ROWS_GENERIC | PGM_ROWS_NO_JIT | PGM_ROWS_VALUES_GLOBAL | PGM_ROWS_ONE_GROUP))) {
-    const bool two = rows_jit2_ok(mode, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, h->k.n_marg);
+  pgm_rows_launch_info_t li;
+  if (n_rows > 0 && h->jit_state > 0 && rows_jit_mode(mode) &&
+      rows_launch_choose(*h, mode, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, true, &li) == PGM_OK) {
+    const bool two = li.kernel == PGM_RK_JIT2;
     b->fn = floor ? (two ? h->jit_fn_floor2 : h->jit_fn_floor) : two ? h->jit_fn2 : h->jit_fn;
     b->args = RowsJitArgs{h->d_values, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, err_flag, mode, 0};
-    const uint64_t rpb = (uint64_t)jit_wg() * (two ? 2 : 1);
-    b->blocks = (unsigned)(((uint64_t)n_rows + rpb - 1) / rpb);
+    b->blocks = li.blocks;
   } else if (floor) {
     delete b;
     return pgmi_failf(PGM_EINVAL, "rows_plan_bind: the floor kernel needs the plan-specialised (hipRTC) kernel");

@@ -181,11 +181,14 @@ static void emit_rows_compute(std::string &o, const pgm_rows_plan *pl, int R, co
   }
 }
 
+// whether pgm_rows_jit / jit2 stage the nv CPT values (trailing 1.0 included) in LDS
+static bool jit_values_lds(int nv) { return nv * 8 <= 48 * 1024; }
+
 // R rows per thread (1, or 2 with 16-B marginal stores / 2-byte code loads); names carry the row's suffix
 static void emit_rows_kernel(std::string &o, const pgm_rows_plan *pl, int R) {
   const int NV = pl->n_values + 1;  // + trailing 1.0
   // CPT values staged in LDS when they fit (else gathered straight from global memory through L1/L2)
-  const bool lds = NV * 8 <= 48 * 1024;
+  const bool lds = jit_values_lds(NV);
   const int WG = jit_wg();
   pgmi_appendf(o, "extern \"C\" __global__ void __launch_bounds__(%d) pgm_rows_jit%s(const double *__restrict__ V, "
              "const unsigned char *__restrict__ C, long long ldc, long long row0, long long n, "
@@ -427,6 +430,97 @@ bool rows_jit2_ok(int32_t mode, const uint8_t *codes, int64_t ld_codes, int64_t 
   static constexpr int64_t min_rows = 50000;
   if (n_rows < min_rows) return false;
   return rows2_aligned(mode, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, n_marg);
+}
+
+// ----------------------------------------------------------------------------- launch choice
+bool rows_jit_mode(int32_t mode) {
+  return !(mode & (PGM_ROWS_JOINT | PGM_ROWS_GENERIC | PGM_ROWS_NO_JIT | PGM_ROWS_VALUES_GLOBAL | PGM_ROWS_ONE_GROUP));
+}
+
+int rows_launch_check(const RowsPlan &p, int32_t mode, const uint8_t *codes, int64_t n_rows, const double *marg,
+                      const double *joint, int64_t ld_out, const int32_t *map, const double *gap) {
+  if (p.max_nt > 0 && !codes) return pgmi_failf(PGM_EINVAL, "rows_plan_run: null codes");
+  if ((mode & PGM_ROWS_MARGINALS) && !marg) return pgmi_failf(PGM_EINVAL, "rows_plan_run: marginals requested, marg is null");
+  if ((mode & PGM_ROWS_JOINT) && !joint) return pgmi_failf(PGM_EINVAL, "rows_plan_run: joint requested, joint is null");
+  if ((mode & PGM_ROWS_JOINT) && p.k.n_comp != 1)
+    return pgmi_failf(PGM_EINVAL, "rows_plan_run: joint output needs a single-component plan");
+  if ((mode & PGM_ROWS_MAP) && !map) return pgmi_failf(PGM_EINVAL, "rows_plan_run: MAP requested, map is null");
+  if ((mode & PGM_ROWS_MAPGAP) && !gap) return pgmi_failf(PGM_EINVAL, "rows_plan_run: MAP gap requested, gap is null");
+  if ((mode & (PGM_ROWS_MARGINALS | PGM_ROWS_JOINT)) && ld_out < n_rows)
+    return pgmi_failf(PGM_EINVAL, "rows_plan_run: ld_out %lld < n_rows %lld", (long long)ld_out, (long long)n_rows);
+  return PGM_OK;
+}
+
+int rows_launch_choose(const RowsPlan &p, int32_t mode, const uint8_t *codes, int64_t ld_codes, int64_t row0,
+                       int64_t n_rows, const double *marg, int64_t ld_out, const int32_t *map, const double *gap,
+                       bool jit, pgm_rows_launch_info_t *info) {
+  memset(info, 0, sizeof *info);
+  info->kernel = PGM_RK_NONE;
+  if (n_rows <= 0) return PGM_OK;
+  const RowsK &k = p.k;
+  info->rg = 1;
+  if (jit) {
+    const bool two = rows_jit2_ok(mode, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, k.n_marg);
+    const uint64_t rpb = (uint64_t)jit_wg() * (two ? 2 : 1);  // rows per block
+    const uint64_t jblocks = ((uint64_t)n_rows + rpb - 1) / rpb;
+    if (jblocks > 0x7fffffffull) return pgmi_failf(PGM_EINVAL, "rows_plan_run: too many rows");
+    info->kernel = two ? PGM_RK_JIT2 : PGM_RK_JIT;
+    info->values_lds = jit_values_lds(k.n_values);
+    info->blocks = (uint32_t)jblocks;
+    info->wg = (uint32_t)jit_wg();
+    info->lds_bytes = info->values_lds ? (uint32_t)((k.n_values + jit_wg() - 1) / jit_wg() * jit_wg() * 8) : 0;
+    return PGM_OK;
+  }
+  // one workgroup = 64 rows x RG row groups; one wave per component
+  const size_t kLds = 64 * 1024;
+  size_t vals_bytes = (size_t)((k.n_values + 1) & ~1) * sizeof(double);
+  const bool vals_lds = vals_bytes <= 40 * 1024 && !(mode & PGM_ROWS_VALUES_GLOBAL);
+  if (!vals_lds) vals_bytes = 0;
+  const uint64_t groups = ((uint64_t)n_rows + 63) / 64;
+  // amortise the LDS staging of the CPT values over several row groups once the grid is large
+  int32_t RG = 1;
+  if (vals_lds && !(mode & PGM_ROWS_ONE_GROUP)) RG = (int32_t)std::max<uint64_t>(1, std::min<uint64_t>(8, groups / 4096));
+  const uint64_t blocks = (groups + RG - 1) / RG;
+  if (blocks > 0x7fffffffull) return pgmi_failf(PGM_EINVAL, "rows_plan_run: too many rows");
+  info->values_lds = vals_lds;
+  info->rg = RG;
+  info->blocks = (uint32_t)blocks;
+  info->wg = (uint32_t)(64 * k.n_comp);
+  if (p.all_affine && !(mode & PGM_ROWS_JOINT) && !(mode & PGM_ROWS_GENERIC)) {
+    const bool do_map = (mode & (PGM_ROWS_MAP | PGM_ROWS_MAPGAP)) != 0;
+    // exchange slots: masses only, unless MAP digits / gaps are combined too
+    const size_t x_aff = k.n_comp > 1 ? (size_t)k.n_comp * 64 * (do_map ? 2 * sizeof(double) + sizeof(int32_t) : sizeof(double)) : 0;
+    info->kernel = PGM_RK_AFFINE;
+    info->nf = p.max_nf <= 1 ? 1 : p.max_nf <= 2 ? 2 : 4;
+    info->nt = p.max_nt <= 4 ? 4 : 8;
+    info->map = do_map;
+    info->lds_bytes = (uint32_t)(vals_bytes + x_aff);
+    return PGM_OK;
+  }
+  const size_t x_bytes = (size_t)k.n_comp * 64 * (2 * sizeof(double) + sizeof(int32_t));
+  const size_t acc_bytes = (size_t)k.n_marg * 64 * sizeof(double);
+  const bool acc_lds = (mode & PGM_ROWS_MARGINALS) && p.any_table && vals_bytes + x_bytes + acc_bytes <= kLds;
+  info->kernel = PGM_RK_TABLE;
+  info->acc_lds = acc_lds;
+  info->maxfc = p.max_nf <= 2 ? 2 : p.max_nf <= 4 ? 4 : p.max_nf <= 8 ? 8 : PGM_ROWS_MAX_FAC;
+  info->maxt = p.max_nt <= 4 ? 4 : p.max_nt <= 8 ? 8 : PGM_ROWS_MAX_EV;
+  info->lds_bytes = (uint32_t)(vals_bytes + x_bytes + (acc_lds ? acc_bytes : 0));
+  return PGM_OK;
+}
+
+int rows_launch_info(const pgm_rows_plan *pl, int32_t mode, const uint8_t *codes, int64_t ld_codes, int64_t row0,
+                     int64_t n_rows, const double *marg, const double *joint, int64_t ld_out, const int32_t *map,
+                     const double *gap, bool jit_available, pgm_rows_launch_info_t *info) {
+  if (!pl || !info) return pgmi_failf(PGM_EINVAL, "rows_launch_info: null argument");
+  RowsPlan plan;
+  int st = rows_plan_compile(pl, plan);
+  if (st != PGM_OK) return st;
+  if (n_rows > 0) {
+    st = rows_launch_check(plan, mode, codes, n_rows, marg, joint, ld_out, map, gap);
+    if (st != PGM_OK) return st;
+  }
+  const bool jit = jit_available && !plan.jit_src.empty() && rows_jit_mode(mode);
+  return rows_launch_choose(plan, mode, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, jit, info);
 }
 
 int rows_plan_source(const pgm_rows_plan *pl, std::string &src) {

@@ -169,6 +169,17 @@ class PatternPlan:
                 return "k_rows"
         return "pgm_rows_jit"
 
+    def launch_info(self, n_rows, marginals=True, map_=False, gap=False, jit=True, **window):
+        """N.RowsLaunchInfo of run() on n_rows rows with these outputs (pgm_rows_launch_info: kernel
+        family, template arguments, row groups, grid, LDS); host-only.  window: row0, ld_codes, ld_out
+        and buffer addresses, as N.rows_launch_info takes them."""
+        if self.kind != "fused":
+            return None
+        pl, _, _ = self._rows_plan_struct(split=True)
+        mode = self.extra_mode | (N.ROWS_MARGINALS if marginals else 0) | (N.ROWS_MAP if map_ else 0) | (
+            N.ROWS_MAPGAP if gap else 0)
+        return N.rows_launch_info(pl, mode, n_rows, jit=jit, **window)
+
     def _rows_plan_struct(self, split):
         """(pgm_rows_plan, packed CPT values, component count): host-only."""
         comps = self.components() if split else [(list(self.variables), list(self.hidden),

@@ -1,5 +1,5 @@
 // rows_plan_selftest.cpp — the host side of the fused row plan (pgmpy_amd/csrc/pgmrows_plan.cpp: plan
-// compiler, generator of the plan-specialised kernel source, two-rows-per-thread predicates) on the
+// compiler, generator of the plan-specialised kernel source, two-rows-per-thread predicates, launch choice) on the
 // CPU, against hand-built pgm_rows_plan structs.  Links that unit alone; meant for a sanitizer build:
 //   c++ -std=c++17 -g -fsanitize=address,undefined -I include -I pgmpy_amd/csrc
 //       tools/rows_plan_selftest.cpp pgmpy_amd/csrc/pgmrows_plan.cpp -o rows_plan_selftest
@@ -590,6 +590,98 @@ static int test_rows2_aligned() {
   return 0;
 }
 
+// ---------------------------------------------------------------------------- launch choice
+// rows_launch_info (what pgm_rows_launch_info returns and rows_plan_run launches) at its boundaries
+static int test_launch_info() {
+  const int32_t M = PGM_ROWS_MARGINALS, P = PGM_ROWS_MAP, G = PGM_ROWS_MAPGAP, all = M | P | G;
+  const uint8_t *codes = (const uint8_t *)0x10000;
+  const double *marg = (const double *)0x20000, *gap = (const double *)0x30000, *joint = (const double *)0x50000;
+  const int32_t *map = (const int32_t *)0x40000;
+  pgm_rows_launch_info_t li;
+  auto info = [&](const pgm_rows_plan &p, int32_t mode, int64_t n, bool jit) {
+    return rows_launch_info(&p, mode, codes, n, 0, n, marg, joint, n, map, gap, jit, &li);
+  };
+  // values in LDS up to 5,120 doubles with the trailing 1.0 (40 KiB), ahead-of-time kernels
+  pgm_rows_plan p = plan_affine_nq1();
+  p.n_values = 5119;
+  CHECK(info(p, all, 197, false) == PGM_OK);
+  CHECK(li.kernel == PGM_RK_AFFINE && li.values_lds == 1 && li.nf == 1 && li.nt == 4 && li.map == 1 && li.rg == 1);
+  CHECK(li.blocks == 4 && li.wg == 64 && li.lds_bytes == 5120 * 8);  // one component: no exchange slots
+  p.n_values = 5120;
+  CHECK(info(p, all, 197, false) == PGM_OK);
+  CHECK(li.kernel == PGM_RK_AFFINE && li.values_lds == 0 && li.lds_bytes == 0);
+  CHECK(info(p, all | PGM_ROWS_GENERIC, 197, false) == PGM_OK);
+  CHECK(li.kernel == PGM_RK_TABLE && li.values_lds == 0 && li.acc_lds == 0 && li.maxfc == 2 && li.maxt == 4);
+  CHECK(li.lds_bytes == 64 * 20);
+  // the specialised kernels stage up to 6,144 doubles (48 KiB)
+  p.n_values = 6143;
+  CHECK(info(p, all, 197, true) == PGM_OK);
+  CHECK(li.kernel == PGM_RK_JIT && li.values_lds == 1 && li.wg == (uint32_t)jit_wg() && li.rg == 1);
+  CHECK(li.blocks == (197 + li.wg - 1) / li.wg && li.lds_bytes == (6144 + li.wg - 1) / li.wg * li.wg * 8);
+  p.n_values = 6144;
+  CHECK(info(p, all, 197, true) == PGM_OK);
+  CHECK(li.kernel == PGM_RK_JIT && li.values_lds == 0 && li.lds_bytes == 0);
+  // every mode bit that rules the specialised kernel out; a plan without a generated source
+  p = plan_affine_nq1();
+  for (int32_t bit : {PGM_ROWS_GENERIC, PGM_ROWS_NO_JIT, PGM_ROWS_VALUES_GLOBAL, PGM_ROWS_ONE_GROUP}) {
+    CHECK(info(p, all | bit, 197, true) == PGM_OK);
+    CHECK(li.kernel == (bit == PGM_ROWS_GENERIC ? PGM_RK_TABLE : PGM_RK_AFFINE));
+  }
+  CHECK(info(p, M | PGM_ROWS_JOINT, 197, true) == PGM_OK);
+  CHECK(li.kernel == PGM_RK_TABLE && li.acc_lds == 0);  // no table component: no accumulators
+  CHECK(info(p, M, 197, false) == PGM_OK);
+  CHECK(li.kernel == PGM_RK_AFFINE && li.map == 0);
+  // two rows per thread from 50,000 rows
+  CHECK(info(p, all, 49999, true) == PGM_OK && li.kernel == PGM_RK_JIT);
+  CHECK(info(p, all, 49998, true) == PGM_OK && li.kernel == PGM_RK_JIT);
+  CHECK(info(p, all, 50000, true) == PGM_OK && li.kernel == PGM_RK_JIT2);
+  CHECK(li.blocks == (50000 + 2 * li.wg - 1) / (2 * li.wg));
+  CHECK(rows_launch_info(&p, all, codes, 50000, 0, 50000, marg + 1, joint, 50000, map, gap, true, &li) == PGM_OK);
+  CHECK(li.kernel == PGM_RK_JIT);
+  // row groups per workgroup: groups / 4096, from 8,192 groups (524,225 rows) up, at most 8
+  CHECK(info(p, all, 524224, false) == PGM_OK && li.rg == 1 && li.blocks == 8191);
+  CHECK(info(p, all, 524225, false) == PGM_OK && li.rg == 2 && li.blocks == 4096);
+  CHECK(info(p, all | PGM_ROWS_ONE_GROUP, 524225, false) == PGM_OK && li.rg == 1 && li.blocks == 8192);
+  CHECK(info(p, all | PGM_ROWS_VALUES_GLOBAL, 524225, false) == PGM_OK && li.rg == 1);
+  CHECK(info(p, all | PGM_ROWS_GENERIC, 524225, false) == PGM_OK && li.kernel == PGM_RK_TABLE && li.rg == 2);
+  CHECK(info(p, all, 64ll * 4096 * 9, false) == PGM_OK && li.rg == 8 && li.blocks == 4096 * 9 / 8);
+  // marginal accumulators in LDS while values + exchange slots + 512 B per marginal row fit 64 KiB
+  p = plan_table_hidden();  // 12 values: 112 B; one component: 1,280 B of exchange slots
+  p.n_marg = 125;
+  CHECK(info(p, all, 197, true) == PGM_OK);
+  CHECK(li.kernel == PGM_RK_TABLE && li.acc_lds == 1 && li.lds_bytes == 112 + 1280 + 125 * 512);
+  p.n_marg = 126;
+  CHECK(info(p, all, 197, true) == PGM_OK);
+  CHECK(li.kernel == PGM_RK_TABLE && li.acc_lds == 0 && li.values_lds == 1 && li.lds_bytes == 112 + 1280);
+  p.n_marg = 125;
+  CHECK(info(p, P | G, 197, true) == PGM_OK && li.acc_lds == 0);  // no marginals: no accumulators
+  // template arguments from the plan's widest component
+  p = plan_terms9();
+  CHECK(info(p, all, 197, false) == PGM_OK && li.kernel == PGM_RK_TABLE && li.maxfc == 2 && li.maxt == PGM_ROWS_MAX_EV);
+  p = plan_terms8();
+  CHECK(info(p, all, 197, false) == PGM_OK && li.kernel == PGM_RK_AFFINE && li.nf == 2 && li.nt == 8);
+  p = plan_terms4();
+  CHECK(info(p, all, 197, false) == PGM_OK && li.kernel == PGM_RK_AFFINE && li.nf == 2 && li.nt == 4);
+  // a component without factors: all-affine, one slot
+  p = plan_no_factor();
+  CHECK(info(p, all, 197, false) == PGM_OK);
+  CHECK(li.kernel == PGM_RK_AFFINE && li.values_lds == 1 && li.nf == 1 && li.wg == 128);
+  CHECK(info(p, all, 197, true) == PGM_OK && li.kernel == PGM_RK_JIT);
+  // the argument checks of pgm_rows_plan_run, in its order; nothing to launch
+  p = plan_two_comp();
+  CHECK(rows_launch_info(&p, all, nullptr, 10, 0, 10, nullptr, joint, 10, map, gap, true, &li) == PGM_EINVAL);
+  CHECK(g_last_err == "rows_plan_run: null codes");
+  CHECK(rows_launch_info(&p, all, codes, 10, 0, 10, nullptr, joint, 5, nullptr, gap, true, &li) == PGM_EINVAL);
+  CHECK(g_last_err == "rows_plan_run: marginals requested, marg is null");
+  CHECK(rows_launch_info(&p, PGM_ROWS_JOINT, codes, 10, 0, 10, marg, joint, 10, map, gap, true, &li) == PGM_EINVAL);
+  CHECK(g_last_err == "rows_plan_run: joint output needs a single-component plan");
+  CHECK(rows_launch_info(&p, all, codes, 10, 0, 10, marg, joint, 5, map, gap, true, &li) == PGM_EINVAL);
+  CHECK(g_last_err == "rows_plan_run: ld_out 5 < n_rows 10");
+  CHECK(info(p, all, 0, true) == PGM_OK && li.kernel == PGM_RK_NONE && li.blocks == 0);
+  CHECK(rows_launch_info(nullptr, all, codes, 10, 0, 10, marg, joint, 10, map, gap, true, &li) == PGM_EINVAL);
+  return 0;
+}
+
 // ---------------------------------------------------------------------------- source shape
 static int test_source_shape() {
   // LDS staging up to 6,144 values (48 KiB), global gathers above
@@ -625,7 +717,7 @@ int main(int argc, char **argv) {
   CHECK(sha256("abcdbcdecdefdefgefghfghighijhijkijkljklmklmnlmnomnopnopq", 56) ==
         "248d6a61d20638b8e5c026930c3e6039a33ce45964ff2167f6ecedd419db06c1");  // two blocks
   if (test_recorded() || test_affine_nq1() || test_nq0() || test_two_comp() || test_table_2x3() ||
-      test_term_padding() || test_rejected() || test_rows2_aligned() || test_source_shape())
+      test_term_padding() || test_rejected() || test_rows2_aligned() || test_launch_info() || test_source_shape())
     return 1;
   printf("rows_plan_selftest ok\n");
   return 0;
