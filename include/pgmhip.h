@@ -678,6 +678,61 @@ int pgm_dq_bind_pm(void *dq, void *pm_bound, void **dbound);
 int pgm_dq_run_chain(void *const *dbounds, const uint8_t *independent, int32_t n);
 int pgm_dq_profiling(void *dq, int32_t on);
 
+/* ---------------------------------------------------------------- parameter learning
+ * DiscreteBayesianNetwork.fit / fit_update (DiscreteBayesianNetwork.py:596-729) on the device: the state
+ * counts of every family (a node plus its parents) in one launch, then every CPD's values in one more.
+ * Replaces the reference's pandas groupby per node (estimators/base.py:67-176) and its per-CPD
+ * normalisation (MLE.py:183-212, BayesianEstimator.py:252-264).  An extension of ABI 25.
+ *
+ * A family lists the code column and the cardinality of the node, then of each parent in the CPD's
+ * order (the reference sorts them); at most PGM_MAX_DIMS - 1 parents.  Its count table has the CPD's
+ * layout [node_card, prod(parent_card)] in C order (last parent fastest) and sits at offsets[f] of one
+ * flat buffer of total_bins entries, families end to end in the order given.
+ *
+ * pgm_fit_count ADDS to `tables` (the caller zeroes them; several calls may count several row windows)
+ * the rows [row0, row0 + n_rows) of codes[col * ld + row] (n_cols columns of ld rows).  A row whose code
+ * is PGM_EV_MISSING in any column of a family is skipped for that family only (groupby / value_counts
+ * drop NaN per family).  weights NULL: every row counts 1, tables are int64, exact and deterministic.
+ * weights given (weights[row], ld entries; the `_weight` column): tables are fp64 and the order of
+ * addition is not fixed.  A code that is neither PGM_EV_MISSING nor < its cardinality never indexes a
+ * table: the row is skipped for that family and the call returns PGM_EINDEX (a device flag the call
+ * reads back after the launch, so the call synchronises the stream).
+ *
+ * pgm_fit_finish writes values = normalise(counts + pseudo) for every CPD: pseudo (optional, fp64, the
+ * tables' layout) is added, then each column is divided by its sum taken in state order
+ * (values / values.sum(axis=0)).  PGM_FIT_MLE: a column that is all zero becomes uniform (MLE.py:187).
+ * PGM_FIT_BAYES: no fill, 0/0 stays NaN.  | PGM_FIT_WEIGHTED: counts are the fp64 tables.
+ *
+ * Every argument is checked on the host before any HIP call; pgm_fit_plan_create and pgm_fit_plan_info
+ * need no device (the descriptors are uploaded by the first count / finish). */
+#define PGM_FIT_MLE 0
+#define PGM_FIT_BAYES 1
+#define PGM_FIT_WEIGHTED 2
+typedef struct {
+  int32_t n_vars;             /* 1 + parents */
+  int32_t col[PGM_MAX_DIMS];  /* code column: the node, then each parent */
+  int32_t card[PGM_MAX_DIMS]; /* 1 .. 255 */
+} pgm_fit_family;
+typedef struct {
+  int32_t n_families;
+  int32_t n_groups;       /* workgroup groups: consecutive families whose tables share one LDS tile */
+  int32_t tile_bins;      /* bins of the LDS tile; a larger family counts straight into global memory */
+  int32_t rows_per_block; /* rows one workgroup counts for its group */
+  int32_t n_cols;         /* 1 + the largest code column read */
+  int32_t block;          /* work-items per workgroup */
+  int64_t total_bins;     /* entries of the count / pseudo-count / value buffers */
+  int64_t total_columns;  /* CPD columns (parent configurations) over all families */
+} pgm_fit_info_t;
+int pgm_fit_plan_create(const pgm_fit_family *families, int32_t n_families, void **plan);
+int pgm_fit_plan_destroy(void *plan);
+/* layout of a plan: per family its offset, its size, its PGM_MAX_DIMS strides (node first) and its group;
+ * any output may be NULL */
+int pgm_fit_plan_info(void *plan, pgm_fit_info_t *info, int64_t *offsets, int64_t *sizes, int32_t *strides,
+                      int32_t *groups);
+int pgm_fit_count(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
+                  const double *weights, void *tables, void *stream);
+int pgm_fit_finish(void *plan, const void *counts, const double *pseudo, int32_t mode, double *values, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

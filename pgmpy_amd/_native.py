@@ -171,6 +171,21 @@ class RowsPlan(ctypes.Structure):
     ]
 
 
+class FitFamily(ctypes.Structure):
+    """pgm_fit_family: the code column and cardinality of a node, then of each of its parents."""
+    _fields_ = [("n_vars", ctypes.c_int32), ("col", ctypes.c_int32 * PGM_MAX_DIMS),
+                ("card", ctypes.c_int32 * PGM_MAX_DIMS)]
+
+
+class FitInfo(ctypes.Structure):
+    """pgm_fit_info_t: layout and launch geometry of a pgm_fit plan (host-only query)."""
+    _fields_ = [("n_families", ctypes.c_int32), ("n_groups", ctypes.c_int32), ("tile_bins", ctypes.c_int32),
+                ("rows_per_block", ctypes.c_int32), ("n_cols", ctypes.c_int32), ("block", ctypes.c_int32),
+                ("total_bins", ctypes.c_int64), ("total_columns", ctypes.c_int64)]
+
+
+FIT_MLE, FIT_BAYES, FIT_WEIGHTED = 0, 1, 2
+
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
 RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
@@ -339,6 +354,13 @@ _SIGS = {
     "pgm_dq_profiling": ([_P, ctypes.c_int32], ctypes.c_int),
     "pgm_dq_timer_dispatch_times": ([_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                      ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "pgm_fit_plan_create": ([ctypes.POINTER(FitFamily), ctypes.c_int32, ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_fit_plan_destroy": ([_P], ctypes.c_int),
+    "pgm_fit_plan_info": ([_P, ctypes.POINTER(FitInfo), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                           ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "pgm_fit_count": ([_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, _P, _P],
+                      ctypes.c_int),
+    "pgm_fit_finish": ([_P, _P, _P, ctypes.c_int32, _P, _P], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

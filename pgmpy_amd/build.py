@@ -17,6 +17,8 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmhip.hip",        # primitive factor kernels + their C-ABI, the error string
     "pgmrows.hip",       # fused row plan: kernels + C-ABI
     "pgmrows_plan.cpp",  # fused row plan: plan compiler + generator of the specialised source (host only)
+    "pgmfit.hip",        # parameter learning: family-count + CPD finishing kernels, their C-ABI
+    "pgmfit_plan.cpp",   # parameter learning: family validation, table layout, argument checks (host only)
     "pgmdq.cpp",         # direct AQL dispatch (host code, HSA runtime)
     "pgmpm.cpp",         # plan-specialised batched-BP steps (host code, hipRTC)
     "pgmhost.cpp",       # DataFrame ingestion helpers (host threads only)

@@ -1,0 +1,65 @@
+// pgm_fit.h — private interface between the two units of parameter learning: pgmfit_plan.cpp (host only:
+// family validation, table layout, grouping of families per workgroup, the argument checks of the
+// pgm_fit_* entry points) and pgmfit.hip (the counting and finishing kernels, the device side of the
+// handle, the launches).  Not part of include/pgmhip.h.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "pgmhip.h"
+
+// internal to the library: not in its dynamic symbol table
+#define PGM_FIT_LOCAL __attribute__((visibility("hidden")))
+
+// Launch geometry of the counting kernel.  A workgroup of kFitBlock work-items takes kFitRowsPerBlock
+// rows for one group of families whose count tables, laid end to end, fill at most kFitTileBins bins of
+// LDS: 4,096 uint32 bins are 16 KiB, so the 8 workgroups of 256 that fill a CU's 32 wave slots take
+// 128 KiB of its 160 KiB (the fp64 bins of the weighted kernel take 32 KiB: 5 workgroups, 20 waves per
+// CU).  A workgroup adds at most kFitRowsPerBlock to a bin, so a uint32 bin cannot wrap.
+static constexpr int kFitBlock = 256;
+static constexpr int kFitTileBins = 4096;
+static constexpr int kFitRowsPerBlock = 4096;
+
+// one family as the kernels read it (device memory; every field is workgroup-uniform: scalar loads)
+struct FitFam {
+  int64_t off;                   // first bin of the table in the flat count buffer
+  int32_t size, n_vars;          // bins = product of the cardinalities; 1 + parents
+  int32_t col[PGM_MAX_DIMS];     // code column of the node, then of each parent
+  int32_t card[PGM_MAX_DIMS];
+  int32_t stride[PGM_MAX_DIMS];  // the CPD's layout [node][parents in C order]: last parent fastest
+};
+// consecutive families one workgroup counts together: their tables are one contiguous run of bins
+struct FitGroup {
+  int64_t off;                 // first bin of the run
+  int32_t fam_begin, fam_end;  // families [fam_begin, fam_end)
+  int32_t bins;                // bins of the run (<= kFitTileBins unless global)
+  int32_t global;              // 1: a single family larger than the tile, counted straight into global memory
+};
+static_assert(sizeof(FitFam) % 8 == 0 && sizeof(FitGroup) == 24, "descriptor packing");
+
+// a validated set of families: everything the kernels need, before anything touches a device
+struct PGM_FIT_LOCAL FitPlan {
+  std::vector<FitFam> fams;
+  std::vector<FitGroup> groups;
+  std::vector<int32_t> group_of;  // group of each family
+  std::vector<int64_t> col_off;   // first CPD column (parent configuration) of each family, + the total
+  int64_t total_bins = 0;
+  int n_cols = 0;  // 1 + the largest code column read
+};
+
+// the handle behind pgm_fit_plan_create: the plan plus its lazily uploaded device copy (pgmfit.hip)
+struct PGM_FIT_LOCAL FitHandle {
+  FitPlan p;
+  int device = -1;  // the device the copies below live on (-1: not uploaded)
+  void *d_fams = nullptr, *d_groups = nullptr, *d_col_off = nullptr, *d_err = nullptr;
+};
+
+// validate the families and lay the tables out; PGM_OK, or PGM_EINVAL with pgm_last_error set
+PGM_FIT_LOCAL int fit_plan_build(const pgm_fit_family *fams, int32_t n, FitPlan &out);
+// the argument checks of pgm_fit_count / pgm_fit_finish (no HIP call); *blocks: workgroups of the launch
+PGM_FIT_LOCAL int fit_count_check(const FitHandle *h, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0,
+                                  int64_t n_rows, const void *tables, int64_t *blocks);
+// whether a count launch takes the four-rows-per-lane kernel: a lane's dword load of 4 codes must be aligned
+// in every column (codes, ld and row0 multiples of 4); else the one-row kernel runs
+PGM_FIT_LOCAL bool fit_count_vec4(const uint8_t *codes, int64_t ld, int64_t row0);
+PGM_FIT_LOCAL int fit_finish_check(const FitHandle *h, const void *counts, int32_t mode, const double *values);

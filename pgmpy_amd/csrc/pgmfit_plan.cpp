@@ -1,0 +1,138 @@
+// pgmfit_plan.cpp — the host side of parameter learning (DiscreteBayesianNetwork.fit): family validation,
+// the layout of the flat count buffer, the grouping of families per workgroup and the argument checks
+// of the pgm_fit_* entry points.  No HIP include: this unit is tested on the CPU on its own
+// (tools/fit_plan_selftest.cpp).  The kernels and launches are pgmfit.hip.
+#include <cstring>
+#include <new>
+
+#include "pgm_fit.h"
+#include "pgm_internal.h"
+
+int fit_plan_build(const pgm_fit_family *fams, int32_t n, FitPlan &out) {
+  if (!fams) return pgmi_fail(PGM_EINVAL, "fit_plan_create: null families");
+  if (n <= 0) return pgmi_failf(PGM_EINVAL, "fit_plan_create: %d families", n);
+  out = FitPlan();
+  out.fams.resize((size_t)n);
+  out.group_of.resize((size_t)n);
+  out.col_off.resize((size_t)n + 1);
+  int64_t off = 0, cols = 0;
+  for (int32_t f = 0; f < n; ++f) {
+    const pgm_fit_family &in = fams[f];
+    // the node and up to PGM_MAX_DIMS - 1 parents
+    if (in.n_vars < 1 || in.n_vars > PGM_MAX_DIMS)
+      return pgmi_failf(PGM_EINVAL, "fit_plan_create: family %d has %d variables (1 .. %d)", f, in.n_vars,
+                        PGM_MAX_DIMS);
+    FitFam &k = out.fams[(size_t)f];
+    memset(&k, 0, sizeof k);
+    k.n_vars = in.n_vars;
+    int64_t size = 1;
+    for (int v = in.n_vars - 1; v >= 0; --v) {
+      // uint8 codes: states 0 .. 254, 255 is PGM_EV_MISSING
+      if (in.card[v] <= 0 || in.card[v] > PGM_EV_MISSING)
+        return pgmi_failf(PGM_EINVAL, "fit_plan_create: family %d variable %d cardinality %d (1 .. %d)", f, v,
+                          in.card[v], PGM_EV_MISSING);
+      if (in.col[v] < 0) return pgmi_failf(PGM_EINVAL, "fit_plan_create: family %d variable %d column %d", f, v, in.col[v]);
+      k.col[v] = in.col[v];
+      k.card[v] = in.card[v];
+      // the CPD's layout: the node outermost, then the parents in C order
+      k.stride[v] = (int32_t)size;
+      size *= in.card[v];
+      if (size > INT32_MAX)
+        return pgmi_failf(PGM_EINVAL, "fit_plan_create: family %d table exceeds 2^31 - 1 bins", f);
+      if (in.col[v] + 1 > out.n_cols) out.n_cols = in.col[v] + 1;
+    }
+    k.size = (int32_t)size;
+    k.off = off;
+    out.col_off[(size_t)f] = cols;
+    off += size;
+    cols += size / in.card[0];
+    // consecutive families share a workgroup while their tables fit the LDS tile together; a family
+    // larger than the tile is a group of its own and counts into global memory
+    const bool big = size > kFitTileBins;
+    if (big || out.groups.empty() || out.groups.back().global ||
+        out.groups.back().bins + size > kFitTileBins) {
+      FitGroup g;
+      g.off = k.off, g.fam_begin = f, g.fam_end = f + 1, g.bins = (int32_t)size, g.global = big ? 1 : 0;
+      out.groups.push_back(g);
+    } else {
+      out.groups.back().fam_end = f + 1;
+      out.groups.back().bins += (int32_t)size;
+    }
+    out.group_of[(size_t)f] = (int32_t)out.groups.size() - 1;
+  }
+  out.col_off[(size_t)n] = cols;
+  out.total_bins = off;
+  return PGM_OK;
+}
+
+int fit_count_check(const FitHandle *h, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
+                    const void *tables, int64_t *blocks) {
+  if (!h) return pgmi_fail(PGM_EINVAL, "fit_count: null plan");
+  if (!codes) return pgmi_fail(PGM_EINVAL, "fit_count: null codes");
+  if (!tables) return pgmi_fail(PGM_EINVAL, "fit_count: null tables");
+  if (n_rows < 0 || row0 < 0) return pgmi_failf(PGM_EINVAL, "fit_count: n_rows %lld row0 %lld", (long long)n_rows, (long long)row0);
+  if (ld < n_rows || row0 > ld - n_rows)
+    return pgmi_failf(PGM_EINVAL, "fit_count: rows [%lld, %lld) outside ld %lld", (long long)row0,
+                      (long long)(row0 + n_rows), (long long)ld);
+  if (n_cols < h->p.n_cols)
+    return pgmi_failf(PGM_EINVAL, "fit_count: the plan reads column %d, codes has %d columns", h->p.n_cols - 1, n_cols);
+  const int64_t chunks = (n_rows + kFitRowsPerBlock - 1) / kFitRowsPerBlock;
+  const int64_t nb = chunks * (int64_t)h->p.groups.size();
+  if (nb > INT32_MAX)
+    return pgmi_failf(PGM_EINVAL, "fit_count: %lld workgroups (count the rows in several calls)", (long long)nb);
+  if (blocks) *blocks = nb;
+  return PGM_OK;
+}
+
+bool fit_count_vec4(const uint8_t *codes, int64_t ld, int64_t row0) {
+  return ((uintptr_t)codes & 3) == 0 && (ld & 3) == 0 && (row0 & 3) == 0;
+}
+
+int fit_finish_check(const FitHandle *h, const void *counts, int32_t mode, const double *values) {
+  if (!h) return pgmi_fail(PGM_EINVAL, "fit_finish: null plan");
+  if (!counts) return pgmi_fail(PGM_EINVAL, "fit_finish: null counts");
+  if (!values) return pgmi_fail(PGM_EINVAL, "fit_finish: null values");
+  if (mode & ~(PGM_FIT_BAYES | PGM_FIT_WEIGHTED)) return pgmi_failf(PGM_EINVAL, "fit_finish: mode %d", mode);
+  return PGM_OK;
+}
+
+extern "C" {
+
+int pgm_fit_plan_create(const pgm_fit_family *fams, int32_t n, void **plan) {
+  if (!plan) return pgmi_fail(PGM_EINVAL, "fit_plan_create: null plan");
+  *plan = nullptr;
+  FitHandle *h = new (std::nothrow) FitHandle();
+  if (!h) return pgmi_fail(PGM_ENOMEM, "fit_plan_create: out of memory");
+  const int st = fit_plan_build(fams, n, h->p);
+  if (st != PGM_OK) {
+    delete h;
+    return st;
+  }
+  *plan = h;
+  return PGM_OK;
+}
+
+int pgm_fit_plan_info(void *plan, pgm_fit_info_t *info, int64_t *offsets, int64_t *sizes, int32_t *strides,
+                      int32_t *groups) {
+  if (!plan) return pgmi_fail(PGM_EINVAL, "fit_plan_info: null plan");
+  const FitPlan &p = static_cast<const FitHandle *>(plan)->p;
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->n_families = (int32_t)p.fams.size();
+    info->n_groups = (int32_t)p.groups.size();
+    info->tile_bins = kFitTileBins;
+    info->rows_per_block = kFitRowsPerBlock;
+    info->n_cols = p.n_cols;
+    info->block = kFitBlock;
+    info->total_bins = p.total_bins;
+    info->total_columns = p.col_off.back();
+  }
+  for (size_t f = 0; f < p.fams.size(); ++f) {
+    if (offsets) offsets[f] = p.fams[f].off;
+    if (sizes) sizes[f] = p.fams[f].size;
+    if (strides) memcpy(strides + f * PGM_MAX_DIMS, p.fams[f].stride, sizeof p.fams[f].stride);
+    if (groups) groups[f] = p.group_of[f];
+  }
+  return PGM_OK;
+}
+}

@@ -1,0 +1,94 @@
+"""Binding of the pgm_fit_* entry points (include/pgmhip.h, pgmpy_amd/csrc/pgmfit.hip): the state counts
+of a set of families in one launch and every CPD's values in one more.
+
+A family is ``(columns, cardinalities)``: the code column and cardinality of the node, then of each
+parent in the CPD's order.  The count tables, the pseudo-counts and the values share one flat layout:
+family f occupies ``[offsets[f], offsets[f] + sizes[f])``, shaped ``[node_card, prod(parent_card)]`` in
+C order.
+"""
+import ctypes
+
+import numpy as np
+
+from .. import _native as N
+
+
+class FitPlan:
+    def __init__(self, families):
+        L = N.load_library()  # building and inspecting a plan needs no device
+        families = [(list(cols), list(cards)) for cols, cards in families]
+        fams = (N.FitFamily * max(len(families), 1))()
+        for f, (cols, cards) in enumerate(families):
+            if len(cols) != len(cards):
+                raise ValueError(f"family {f}: {len(cols)} columns, {len(cards)} cardinalities")
+            if not 1 <= len(cols) <= N.PGM_MAX_DIMS:
+                raise ValueError(f"family {f} has {len(cols) - 1} parents; at most {N.PGM_MAX_DIMS - 1} are supported")
+            fams[f].n_vars = len(cols)
+            for v, (c, k) in enumerate(zip(cols, cards)):
+                fams[f].col[v], fams[f].card[v] = int(c), int(k)
+        self._h = ctypes.c_void_p()
+        N.check(L.pgm_fit_plan_create(fams, len(families), ctypes.byref(self._h)), "fit_plan_create")
+        n = len(families)
+        self.families = families
+        self.info = N.FitInfo()
+        off, size = (ctypes.c_int64 * n)(), (ctypes.c_int64 * n)()
+        strides, groups = (ctypes.c_int32 * (n * N.PGM_MAX_DIMS))(), (ctypes.c_int32 * n)()
+        N.check(L.pgm_fit_plan_info(self._h, ctypes.byref(self.info), off, size, strides, groups), "fit_plan_info")
+        self.offsets, self.sizes, self.groups = list(off), list(size), list(groups)
+        self.strides = [list(strides[f * N.PGM_MAX_DIMS:f * N.PGM_MAX_DIMS + len(families[f][0])]) for f in range(n)]
+        self.total_bins = int(self.info.total_bins)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                N.load_library().pgm_fit_plan_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def table(self, flat, f):
+        """Family f's [node_card, columns] view of a flat buffer (device tensor or ndarray)."""
+        card = self.families[f][1][0]
+        return flat[self.offsets[f]:self.offsets[f] + self.sizes[f]].reshape(card, self.sizes[f] // card)
+
+    def count(self, codes, n_rows=None, row0=0, weights=None, tables=None):
+        """Add the rows [row0, row0 + n_rows) of the device codes [n_cols, ld] (uint8) to `tables` (a
+        zeroed flat buffer when None): int64 counts, or fp64 sums of `weights` (a device fp64 tensor of
+        ld entries).  Raises IndexError when a code is neither 255 nor a state."""
+        import torch
+
+        L = N.lib()
+        if codes.dtype != torch.uint8 or codes.dim() != 2 or not codes.is_contiguous():
+            raise ValueError("codes must be a contiguous [n_cols, ld] uint8 device tensor")
+        n_cols, ld = int(codes.shape[0]), int(codes.shape[1])
+        n_rows = ld - row0 if n_rows is None else int(n_rows)
+        dtype = torch.int64 if weights is None else torch.float64
+        if weights is not None and (weights.dtype != torch.float64 or weights.numel() < ld
+                                    or not weights.is_contiguous()):
+            raise ValueError("weights must be a contiguous fp64 device tensor with one entry per row of codes")
+        if tables is None:
+            tables = torch.zeros(self.total_bins, dtype=dtype, device=codes.device)
+        elif tables.dtype != dtype or tables.numel() < self.total_bins or not tables.is_contiguous():
+            raise ValueError(f"tables must be a contiguous {dtype} device tensor of {self.total_bins} entries")
+        N.check(L.pgm_fit_count(self._h, N.ptr(codes), n_cols, ld, int(row0), n_rows, N.ptr(weights), N.ptr(tables),
+                                N.stream_handle()), "fit_count")
+        return tables
+
+    def finish(self, counts, pseudo=None, bayes=False, out=None):
+        """Every CPD's values from the count tables (+ fp64 pseudo-counts of the same layout): each
+        column divided by its sum; MLE (bayes=False) fills an all-zero column uniformly, Bayes keeps
+        0/0 = NaN.  Returns the flat fp64 device buffer."""
+        import torch
+
+        L = N.lib()
+        if counts.dtype not in (torch.int64, torch.float64) or counts.numel() < self.total_bins:
+            raise ValueError(f"counts must be an int64 or fp64 device tensor of {self.total_bins} entries")
+        mode = (N.FIT_BAYES if bayes else N.FIT_MLE) | (N.FIT_WEIGHTED if counts.dtype == torch.float64 else 0)
+        if pseudo is not None and (pseudo.dtype != torch.float64 or pseudo.numel() < self.total_bins):
+            raise ValueError(f"pseudo-counts must be an fp64 device tensor of {self.total_bins} entries")
+        if out is None:
+            out = torch.empty(self.total_bins, dtype=torch.float64, device=counts.device)
+        N.check(L.pgm_fit_finish(self._h, N.ptr(counts), N.ptr(pseudo), mode, N.ptr(out), N.stream_handle()),
+                "fit_finish")
+        return out

@@ -47,6 +47,17 @@ class TabularCPD(DiscreteFactor):
             raise ValueError(f"state_names must be of type dict. Got {type(state_names)}")
         super(TabularCPD, self).__init__(variables, cardinality, values_casted.flatten(), state_names=state_names)
 
+    @classmethod
+    def _from_device(cls, variable, variable_card, values, evidence, evidence_card, state_names):
+        """A CPD over device values the engine computed itself (estimators: a view of the finishing
+        kernel's buffer, [variable_card, prod(evidence_card)] in C order): no host round trip."""
+        self = cls.__new__(cls)
+        self.variable = variable
+        self.variable_card = int(variable_card)
+        DiscreteFactor.__init__(self, [variable] + list(evidence), [int(variable_card)] + [int(c) for c in evidence_card],
+                                values, state_names=state_names)
+        return self
+
     def __repr__(self):
         var_str = f"<TabularCPD representing P({self.variable}:{self.variable_card}"
         evidence = self.variables[1:]

@@ -36,7 +36,13 @@ def _lookup_codes(values, st):
 
 
 def encode_frame(model, data, columns=None):
-    """[n_cols, n_rows] uint8 codes of `data` (state names -> state numbers, NaN -> 255).
+    """encode_states against the model's own state names (model.states)."""
+    return encode_states(model.states, data, columns)
+
+
+def encode_states(states, data, columns=None):
+    """[n_cols, n_rows] uint8 codes of `data` (state names -> state numbers, NaN -> 255) against a
+    {variable: state names} mapping (a model's states, or the ones an estimator collected).
 
     Evidence ingestion: categorical columns remap their category codes
     (O(n) integer work); other columns take one hash-table lookup per cell against the variable's
@@ -45,7 +51,6 @@ def encode_frame(model, data, columns=None):
     import pandas as pd
 
     columns = list(data.columns) if columns is None else list(columns)
-    states = model.states
     n = len(data)
     codes = np.empty((len(columns), n), dtype=np.uint8)
     for j, col in enumerate(columns):
@@ -158,7 +163,13 @@ def _column_raw(v, st, col, fallback=None):
 
 
 def ingest_frame(model, data, columns=None, row_hash=False):
-    """Evidence of a DataFrame on the device.
+    """ingest_states against the model's own state names (model.states)."""
+    return ingest_states(model.states, data, columns, row_hash)
+
+
+def ingest_states(states, data, columns=None, row_hash=False):
+    """Evidence of a DataFrame on the device, its cells encoded against a
+    {variable: state names} mapping.
 
     Host: per column, its int8 category indices (pandas Categorical codes, zero-copy of the frame's
     own codes) or one hash pass for object columns, into a pinned [n_cols, n] buffer, plus a small
@@ -169,7 +180,6 @@ def ingest_frame(model, data, columns=None, row_hash=False):
     import torch
 
     columns = list(data.columns) if columns is None else list(columns)
-    states = model.states
     n = len(data)
     nc = len(columns)
     raws, luts = [], []
@@ -180,7 +190,7 @@ def ingest_frame(model, data, columns=None, row_hash=False):
             raise ValueError(f"variable {col} has {len(st)} states; uint8 codes hold at most 254")
         r = _column_raw(data[col], st, col, fallback)
         if r is None:
-            codes = encode_frame(model, data, columns)
+            codes = encode_states(states, data, columns)
             ev = Evidence(upload_codes(codes), group_patterns(codes), n)
             ev.fallback_cols = None  # unknown: the host encoder does not report it
             if row_hash:
@@ -213,7 +223,7 @@ def ingest_frame(model, data, columns=None, row_hash=False):
                                   N.ptr(d_rk), N.ptr(d_nm), N.ptr(d_hash), N.ptr(err), s), "codes_remap")
     nm = download(d_nm)
     if int(download(err)[0]):
-        encode_frame(model, data, columns)  # raises the reference's KeyError for the offending cell
+        encode_states(states, data, columns)  # raises the reference's KeyError for the offending cell
         raise KeyError("evidence holds a category that is not a state name")
     if not nm.any():
         groups = [(np.ones(nc, dtype=bool), np.arange(n))]

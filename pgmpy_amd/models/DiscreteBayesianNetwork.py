@@ -265,6 +265,60 @@ class DiscreteBayesianNetwork(nx.DiGraph):
 
         return junction_tree_from_model(self)
 
+    # ------------------------------------------------------------------ parameter learning
+    @E.serialized
+    def fit(self, data, estimator=None, state_names=[], n_jobs=1, **kwargs):
+        """Estimate every CPD from `data` and add them to the model (DiscreteBayesianNetwork.py:596-666).
+
+        estimator: MaximumLikelihoodEstimator (default) or BayesianEstimator (then prior_type and
+        pseudo_counts / equivalent_sample_size as keyword arguments).  The counts of all families are
+        one fused device launch and the CPDs one more (pgmpy_amd.estimators); n_jobs is accepted and
+        ignored.  Existing CPDs are replaced through add_cpds, so compiled plans go stale.  Returns
+        the model."""
+        from ..estimators import BaseEstimator, MaximumLikelihoodEstimator
+
+        if estimator is None:
+            estimator = MaximumLikelihoodEstimator
+        elif not (isinstance(estimator, type) and issubclass(estimator, BaseEstimator)):
+            raise TypeError("Estimator object should be a valid pgmpy estimator.")
+        _estimator = estimator(self, data, state_names=state_names)
+        cpds_list = _estimator.get_parameters(n_jobs=n_jobs, **kwargs)
+        self.add_cpds(*cpds_list)
+        return self
+
+    @E.serialized
+    def fit_update(self, data, n_prev_samples=None, n_jobs=1):
+        """Update the CPDs with more data (DiscreteBayesianNetwork.py:668-729): a dirichlet prior whose
+        pseudo-counts are the current CPD values x n_prev_samples (default: the rows of `data`), state
+        names from the current CPDs.  The pseudo-counts are built on the device; a current CPD whose
+        parents are not in sorted order is transposed there first."""
+        from ..estimators import BayesianEstimator
+
+        if n_prev_samples is None:
+            n_prev_samples = data.shape[0]
+        pseudo_counts, state_names = {}, {}
+        for var in data.columns:
+            cpd = self.get_cpds(var)
+            t = cpd._d()
+            parents = list(cpd.variables[1:])
+            if parents != sorted(parents):  # the estimator's layout: parents sorted
+                t = E.contract(t, list(cpd.variables), None, None, [cpd.variable] + sorted(parents), combine="copy")
+            pseudo_counts[var] = t.reshape(int(cpd.cardinality[0]), -1) * float(n_prev_samples)
+            state_names.update(cpd.state_names)
+        _est = BayesianEstimator(self, data, state_names=state_names)
+        cpds = _est.get_parameters(prior_type="dirichlet", pseudo_counts=pseudo_counts, n_jobs=n_jobs)
+        self._add_cpds_quietly(cpds)
+
+    def _add_cpds_quietly(self, cpds):
+        """add_cpds without the "Replacing existing CPD" warning per node (fit_update,
+        DiscreteBayesianNetwork.py:726-729)."""
+        disabled = logger.disabled
+        logger.disabled = True
+        try:
+            self.add_cpds(*cpds)
+        finally:
+            logger.disabled = disabled
+
     # ------------------------------------------------------------------ data-parallel callers
     @E.serialized
     def predict(self, data, algo=None, stochastic=False, n_jobs=-1, seed=None, **kwargs):
