@@ -733,6 +733,68 @@ int pgm_fit_count(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, 
                   const double *weights, void *tables, void *stream);
 int pgm_fit_finish(void *plan, const void *counts, const double *pseudo, int32_t mode, double *values, void *stream);
 
+/* ---------------------------------------------------------------- forward sampling
+ * BayesianModelSampling.forward_sample / likelihood_weighted_sample / rejection_sample and
+ * DiscreteBayesianNetwork.simulate (sampling/Sampling.py:30-406, DiscreteBayesianNetwork.py:1400-1704)
+ * on the device: every node of every row in one launch, into the column-major uint8 codes that
+ * pgm_fit_count and the fused row plan read.  An extension of ABI 25.
+ *
+ * A plan is built from pgm_fit_family records given in a TOPOLOGICAL order: every parent's column is
+ * the node column of an earlier family, with the cardinality it has there, and no column is the node of
+ * two families (PGM_EINVAL otherwise).  values and cdf share the fit plan's flat layout: family f at
+ * [offsets[f], offsets[f] + sizes[f]), shaped [node_card, parent configurations] in C order.
+ *
+ * pgm_sample_cdf writes the running sums of every CPD column in state order (c_0 = p_0,
+ * c_s = c_{s-1} + p_s, fp64); values may be the buffer pgm_fit_finish wrote.  A column whose total is
+ * not finite or not > 0 returns PGM_EINVAL (a device flag read back after the launch: the call
+ * synchronises the stream).
+ *
+ * pgm_sample_forward draws the rows [row0, row0 + n_rows) of codes[col * ld + row]; buffer row row0 + i
+ * is row first_row + i of the endless stream of `seed`.  The uniform of stream row r and code column c
+ * is Philox4x32-10 with counter (r & 0xffffffff, r >> 32, c >> 1, 0) and key (seed & 0xffffffff,
+ * seed >> 32): words (x0, x1) for an even c, (x2, x3) for an odd one, u = ((x_hi << 21) | (x_lo >> 11))
+ * * 2^-53.  With t = u * c_{K-1} the state is min{s : c_s > t}, or min{s : c_s == c_{K-1}} if there is
+ * none.  So a result depends on (seed, stream row, column) only: not on the launch geometry, the
+ * alignment path, the row window or the device.
+ *
+ * modes (host, one uint8 per family, NULL: all PGM_SAMPLE_FREE): PGM_SAMPLE_GIVEN takes the code the
+ * column already holds; PGM_SAMPLE_OBSERVED does too and multiplies the row's weight by
+ * value / column total (likelihood weighting); a row whose given code is PGM_EV_MISSING is drawn (and
+ * its weight left alone).  A given code that is neither a state nor PGM_EV_MISSING never indexes a table:
+ * the nodes after it in plan order are written PGM_EV_MISSING for that row, its weight is 0 and the call
+ * returns PGM_EINDEX (a device flag read back after the launch: the call synchronises the stream).
+ * weights (optional, fp64, ld entries indexed by buffer row; needs values) start at 1 and are multiplied
+ * in plan order.  uniforms (optional, fp64 [n_cols, ld], the layout of codes, values in [0, 1)) replace
+ * the generator: the test hook for the boundaries of the running sums.
+ *
+ * Every argument is checked on the host before any HIP call; pgm_sample_plan_create and
+ * pgm_sample_plan_info need no device. */
+#define PGM_SAMPLE_FREE 0
+#define PGM_SAMPLE_GIVEN 1
+#define PGM_SAMPLE_OBSERVED 2
+typedef struct {
+  int32_t n_families;
+  int32_t n_cols;            /* 1 + the largest code column */
+  int32_t block;             /* work-items per workgroup */
+  int32_t rows_per_block;    /* rows one workgroup draws */
+  int64_t total_bins;        /* entries of the values / cdf buffers */
+  int64_t total_columns;     /* CPD columns (parent configurations) over all families */
+  int32_t vec4;              /* the launch takes the four-rows-per-lane path (codes, ld, row0 multiples of 4) */
+  int32_t weighted;          /* weights given */
+  int32_t explicit_uniforms; /* uniforms given */
+  int32_t reserved;
+} pgm_sample_info_t;
+int pgm_sample_plan_create(const pgm_fit_family *families, int32_t n_families, void **plan);
+int pgm_sample_plan_destroy(void *plan);
+/* layout, launch geometry and the kernel path of a launch with these (codes, ld, row0, weights, uniforms):
+ * only NULL and alignment of the pointers matter; any output may be NULL */
+int pgm_sample_plan_info(void *plan, const void *codes, int64_t ld, int64_t row0, const void *weights,
+                         const void *uniforms, pgm_sample_info_t *info, int64_t *offsets, int64_t *sizes);
+int pgm_sample_cdf(void *plan, const double *values, double *cdf, void *stream);
+int pgm_sample_forward(void *plan, const double *values, const double *cdf, const uint8_t *modes, uint8_t *codes,
+                       int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, int64_t first_row, uint64_t seed,
+                       double *weights, const double *uniforms, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

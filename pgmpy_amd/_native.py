@@ -186,6 +186,17 @@ class FitInfo(ctypes.Structure):
 
 FIT_MLE, FIT_BAYES, FIT_WEIGHTED = 0, 1, 2
 
+
+class SampleInfo(ctypes.Structure):
+    """pgm_sample_info_t: layout, launch geometry and kernel path of a pgm_sample plan (host-only query)."""
+    _fields_ = [("n_families", ctypes.c_int32), ("n_cols", ctypes.c_int32), ("block", ctypes.c_int32),
+                ("rows_per_block", ctypes.c_int32), ("total_bins", ctypes.c_int64), ("total_columns", ctypes.c_int64),
+                ("vec4", ctypes.c_int32), ("weighted", ctypes.c_int32), ("explicit_uniforms", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+SAMPLE_FREE, SAMPLE_GIVEN, SAMPLE_OBSERVED = 0, 1, 2
+
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
 RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
@@ -361,6 +372,13 @@ _SIGS = {
     "pgm_fit_count": ([_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, _P, _P],
                       ctypes.c_int),
     "pgm_fit_finish": ([_P, _P, _P, ctypes.c_int32, _P, _P], ctypes.c_int),
+    "pgm_sample_plan_create": ([ctypes.POINTER(FitFamily), ctypes.c_int32, ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_sample_plan_destroy": ([_P], ctypes.c_int),
+    "pgm_sample_plan_info": ([_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, ctypes.POINTER(SampleInfo),
+                              ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
+    "pgm_sample_cdf": ([_P, _P, _P, _P], ctypes.c_int),
+    "pgm_sample_forward": ([_P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                            ctypes.c_int64, ctypes.c_uint64, _P, _P, _P], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -19,6 +19,8 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmrows_plan.cpp",  # fused row plan: plan compiler + generator of the specialised source (host only)
     "pgmfit.hip",        # parameter learning: family-count + CPD finishing kernels, their C-ABI
     "pgmfit_plan.cpp",   # parameter learning: family validation, table layout, argument checks (host only)
+    "pgmsample.hip",     # forward sampling: running-sum + sampling kernels, their C-ABI
+    "pgmsample_plan.cpp",  # forward sampling: family validation, argument checks, host-only queries (host only)
     "pgmdq.cpp",         # direct AQL dispatch (host code, HSA runtime)
     "pgmpm.cpp",         # plan-specialised batched-BP steps (host code, hipRTC)
     "pgmhost.cpp",       # DataFrame ingestion helpers (host threads only)

@@ -319,6 +319,130 @@ class DiscreteBayesianNetwork(nx.DiGraph):
         finally:
             logger.disabled = disabled
 
+    # ------------------------------------------------------------------ intervention and simulation
+    def do(self, nodes, inplace=False):
+        """The do operation (DiscreteBayesianNetwork.py:1347-1398): the incoming edges of `nodes` are
+        removed and their CPDs marginalised to the node alone.  Returns the modified network (a copy
+        unless inplace)."""
+        nodes = [nodes] if isinstance(nodes, (str, int)) else list(nodes)
+        if not set(nodes).issubset(set(self.nodes())):
+            raise ValueError(f"Nodes not found in the model: {set(nodes) - set(self.nodes)}")
+        model = self if inplace else self.copy()
+        for node in nodes:
+            model.remove_edges_from([(p, node) for p in list(model.predecessors(node))])
+        if model.cpds:
+            for node in nodes:
+                cpd = model.get_cpds(node=node)
+                if cpd is not None and len(cpd.variables) > 1:
+                    cpd.marginalize(cpd.variables[1:], inplace=True)
+        model._bump()
+        return model
+
+    def simulate(self, n_samples=10, do=None, evidence=None, virtual_evidence=None, virtual_intervention=None,
+                 missing_prob=None, include_latents=False, partial_samples=None, seed=None, show_progress=True,
+                 return_full=False):
+        """Simulate data from the model (DiscreteBayesianNetwork.py:1400-1704) on the device.
+
+        The host rewrites the model, then one sampler runs (pgmpy_amd.sampling): `do` nodes are given
+        constants on the mutilated graph; each virtual evidence / intervention CPD adds a binary child
+        `__var` with CPD [v; 1 - v] that is held at 0; each `missing_prob` CPD adds its `var*` node,
+        and `var` is blanked where it drew 1 (`var_full` keeps the drawn value when return_full).
+        Evidence goes through rejection sampling.  The nodes added take code columns after the model's
+        own, so they change no other column's uniforms.  Returns a frame of categorical columns in
+        model.nodes() order followed by the added ones; latents are dropped unless asked for.
+        show_progress is accepted and ignored."""
+        from ..sampling import BayesianModelSampling
+
+        self.check_model()
+        state_names = self.states
+        evidence = {} if evidence is None else dict(evidence)
+        for var, state in evidence.items():
+            if state not in state_names[var]:
+                raise ValueError(f"Evidence state: {state} for {var} doesn't exist")
+        do = {} if do is None else dict(do)
+        for var, state in do.items():
+            if state not in state_names[var]:
+                raise ValueError(f"Do state: {state} for {var} doesn't exist")
+        virtual_intervention = [] if virtual_intervention is None else list(virtual_intervention)
+        virtual_evidence = [] if virtual_evidence is None else list(virtual_evidence)
+        if set(do).intersection(evidence):
+            raise ValueError("Variable can't be in both do and evidence")
+        virtual = [*virtual_evidence, *virtual_intervention]
+        for cpd in virtual:
+            var = cpd.variables[0]
+            if var not in self.nodes():
+                raise ValueError("Evidence provided for variable which is not in the model")
+            if len(cpd.variables) > 1:
+                raise ValueError("Virtual evidence should be defined on individual variables. Maybe you are looking "
+                                 "for soft evidence.")
+            if self.get_cardinality(var) != cpd.get_cardinality([var])[var]:
+                raise ValueError("The number of states/cardinality for the evidence should be same as the number of "
+                                 "states/cardinality of the variable in the model")
+        if missing_prob is not None:
+            if isinstance(missing_prob, list):
+                for cpd in missing_prob:
+                    if not isinstance(cpd, TabularCPD):
+                        raise ValueError(f"missing_prob must be a list of TabularCPD objects. Got {type(cpd)}")
+            elif isinstance(missing_prob, TabularCPD):
+                missing_prob = [missing_prob]
+            else:
+                raise ValueError(f"missing_prob should be TabularCPD. Got {type(missing_prob)}")
+            for cpd in missing_prob:
+                variable = cpd.variables[0]
+                if not (isinstance(variable, str) and variable.endswith("*")):
+                    raise ValueError(f"Got {variable}. TabularCPD variable should end with * symbol to represent "
+                                     "missingnness variable.")
+                if variable.split("*")[0] not in self.nodes:
+                    raise ValueError(f"Got {variable}. TabularCPD variable not in model nodes.")
+                if cpd.cardinality[0] != 2:
+                    raise ValueError(f"Got cardinality of variable = {cpd.cardinality[0]}. Tabular CPD variable should "
+                                     "have 2 possible states : Missing (1) and Not Missing (0)")
+                for node in cpd.variables[1:]:
+                    if node not in self.nodes():
+                        raise ValueError(f"TabularCPD evidence {node} not in model nodes.")
+        else:
+            missing_prob = []
+
+        model, given = self, {}
+        if do or virtual or missing_prob:  # rewrite a copy; the model's own columns come first
+            columns = sorted(self.nodes())
+            model = self.do(list(do) + [cpd.variables[0] for cpd in virtual_intervention])
+            for var, state in do.items():
+                given[var] = model.get_cpds(var).get_state_no(var, state)
+            for cpd in virtual:
+                var, new_var = cpd.variables[0], "__" + cpd.variables[0]
+                v = np.asarray(cpd._values_readonly(), dtype=np.float64).reshape(1, -1)
+                model.add_edge(var, new_var)
+                model.add_cpds(TabularCPD(new_var, 2, np.vstack((v, 1 - v)), evidence=[var],
+                                          evidence_card=[int(model.get_cardinality(var))],
+                                          state_names={new_var: [0, 1], var: cpd.state_names[var]}))
+                evidence[new_var] = 0
+                columns.append(new_var)
+            for cpd in missing_prob:
+                variable = cpd.variables[0]
+                model.add_node(variable)
+                for node in cpd.variables[1:]:
+                    model.add_edge(node, variable)
+                model.add_cpds(cpd)
+                columns.append(variable)
+            model.__dict__["_sample_columns"] = columns
+
+        sampler = BayesianModelSampling(model)
+        if partial_samples is not None:
+            sampler._partial(partial_samples, int(n_samples))  # the shape and state checks
+        samples = sampler.rejection_sample(evidence=list(evidence.items()), size=n_samples, include_latents=True,
+                                           seed=seed, partial_samples=partial_samples, _given=given)
+        for cpd in missing_prob:
+            variable = cpd.variables[0]
+            var = variable.split("*")[0]
+            if return_full:
+                samples[var + "_full"] = samples.loc[:, var]
+            samples.loc[samples[variable] == cpd.state_names[variable][1], var] = np.nan
+            samples.drop(columns=[variable], inplace=True)
+        if not include_latents:
+            samples = samples.loc[:, [c for c in samples.columns if c not in self.latents]]
+        return samples.astype("category")
+
     # ------------------------------------------------------------------ data-parallel callers
     @E.serialized
     def predict(self, data, algo=None, stochastic=False, n_jobs=-1, seed=None, **kwargs):
