@@ -733,6 +733,38 @@ int pgm_fit_count(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, 
                   const double *weights, void *tables, void *stream);
 int pgm_fit_finish(void *plan, const void *counts, const double *pseudo, int32_t mode, double *values, void *stream);
 
+/* ---------------------------------------------------------------- structure scores
+ * The data-dependent part of the decomposable structure scores (estimators/StructureScore.py: K2, BDeu,
+ * BDs, LogLikeliHood, BIC, AIC) of every family of a fit plan, from the int64 tables pgm_fit_count
+ * wrote, without bringing them to the host.  An extension of ABI 25.
+ *
+ * Family f has r states and q columns (parent configurations); N_jk is the count of state k in column
+ * j, N_j = sum_k N_jk.  scores[f] is the sum over the family's columns of the column term
+ *   PGM_SCORE_BD   sum_k lgamma(N_jk + beta[f]) - lgamma(N_j + alpha[f])
+ *                  | PGM_SCORE_SKIP_EMPTY: a column with N_j = 0 contributes exactly 0
+ *   PGM_SCORE_LL   sum_{k: N_jk > 0} N_jk * (log N_jk - log N_j)      (alpha, beta ignored, may be NULL)
+ * and n_observed[f] (optional) the number of columns with N_j > 0.  The constants that depend only on
+ * (r, q, equivalent sample size) are the caller's.  alpha, beta, scores and n_observed are device
+ * arrays with one entry per family.  fp64 (weighted) tables are not accepted.
+ *
+ * A family's columns are cut into chunks of PGM_SCORE_CHUNK columns counted from its own column 0; one
+ * workgroup sums a chunk in a fixed order (a work-item its column's terms in state order, then a
+ * fixed-shape tree), a second launch sums each family's chunk partials in a fixed order.  No
+ * floating-point atomics: a family's score is bit-identical from run to run and does not depend on
+ * which other families share the plan.  The chunk partials live in the plan: calls on one plan must
+ * not overlap on different streams.  Every argument is checked on the host before any HIP call. */
+#define PGM_SCORE_BD 0
+#define PGM_SCORE_LL 1
+#define PGM_SCORE_SKIP_EMPTY 2
+#define PGM_SCORE_CHUNK 128 /* CPD columns per workgroup (two waves): small families waste few lanes */
+int pgm_fit_score(void *plan, const int64_t *counts, int32_t mode, const double *alpha, const double *beta,
+                  double *scores, int64_t *n_observed, void *stream);
+/* n_states[f] (device, one per family) = the number of states k of family f's node with sum_j N_jk > 0.
+ * The reference's state_counts(reindex=False) drops the other states' rows from a family with parents
+ * (groupby(observed=True)), so its BDeu / BDs leave out their lgamma(beta) terms (StructureScore.py:
+ * 463-473): the caller's correction needs their number.  Integer work only; checked on the host. */
+int pgm_fit_states_observed(void *plan, const int64_t *counts, int64_t *n_states, void *stream);
+
 /* ---------------------------------------------------------------- forward sampling
  * BayesianModelSampling.forward_sample / likelihood_weighted_sample / rejection_sample and
  * DiscreteBayesianNetwork.simulate (sampling/Sampling.py:30-406, DiscreteBayesianNetwork.py:1400-1704)

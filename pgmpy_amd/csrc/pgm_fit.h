@@ -19,6 +19,11 @@
 static constexpr int kFitBlock = 256;
 static constexpr int kFitTileBins = 4096;
 static constexpr int kFitRowsPerBlock = 4096;
+// The score kernel: one workgroup of kScoreChunk work-items per chunk of kScoreChunk CPD columns of one
+// family, chunks counted from the family's own column 0 (so a family's partial sums do not depend on
+// the families around it); the second launch sums a family's chunk partials with kScoreSumBlock work-items.
+static constexpr int kScoreChunk = PGM_SCORE_CHUNK;
+static constexpr int kScoreSumBlock = 64;
 
 // one family as the kernels read it (device memory; every field is workgroup-uniform: scalar loads)
 struct FitFam {
@@ -43,6 +48,7 @@ struct PGM_FIT_LOCAL FitPlan {
   std::vector<FitGroup> groups;
   std::vector<int32_t> group_of;  // group of each family
   std::vector<int64_t> col_off;   // first CPD column (parent configuration) of each family, + the total
+  std::vector<int64_t> chunk_off;  // first score chunk (kScoreChunk columns) of each family, + the total
   int64_t total_bins = 0;
   int n_cols = 0;  // 1 + the largest code column read
 };
@@ -52,6 +58,8 @@ struct PGM_FIT_LOCAL FitHandle {
   FitPlan p;
   int device = -1;  // the device the copies below live on (-1: not uploaded)
   void *d_fams = nullptr, *d_groups = nullptr, *d_col_off = nullptr, *d_err = nullptr;
+  // the score launches: chunk_off, and one fp64 partial + one int64 observed-column count per chunk
+  void *d_chunk_off = nullptr, *d_part = nullptr, *d_part_obs = nullptr;
 };
 
 // validate the families and lay the tables out; PGM_OK, or PGM_EINVAL with pgm_last_error set
@@ -63,3 +71,7 @@ PGM_FIT_LOCAL int fit_count_check(const FitHandle *h, const uint8_t *codes, int3
 // in every column (codes, ld and row0 multiples of 4); else the one-row kernel runs
 PGM_FIT_LOCAL bool fit_count_vec4(const uint8_t *codes, int64_t ld, int64_t row0);
 PGM_FIT_LOCAL int fit_finish_check(const FitHandle *h, const void *counts, int32_t mode, const double *values);
+// the argument checks of pgm_fit_score (no HIP call); *blocks: workgroups of the chunk launch
+PGM_FIT_LOCAL int fit_score_check(const FitHandle *h, const int64_t *counts, int32_t mode, const double *alpha,
+                                  const double *beta, const double *scores, int64_t *blocks);
+PGM_FIT_LOCAL int fit_states_check(const FitHandle *h, const int64_t *counts, const int64_t *n_states);

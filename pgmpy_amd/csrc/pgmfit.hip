@@ -1,6 +1,7 @@
 // pgmfit.hip — parameter learning on the device (gfx950): the family-count kernel and the CPD finishing
 // kernel behind DiscreteBayesianNetwork.fit / fit_update, and their C-ABI (pgm_fit_plan_destroy,
-// pgm_fit_count, pgm_fit_finish).  Replaces the reference's per-node pandas groupby
+// pgm_fit_count, pgm_fit_finish), and the structure-score kernels behind estimators/StructureScore.py and
+// HillClimbSearch (pgm_fit_score).  Replaces the reference's per-node pandas groupby
 // (estimators/base.py:67-176) and the per-CPD normalisation (MLE.py:183-212, BayesianEstimator.py:252-264).
 // The host side (validation, table layout, family groups, argument checks) is pgmfit_plan.cpp.
 #include <mutex>
@@ -149,11 +150,129 @@ __global__ __launch_bounds__(256) void k_fit_finish(const FitFam *__restrict__ f
   }
 }
 
+// ---------------------------------------------------------------------------- structure scores
+// The data-dependent sum of a structure score (StructureScore.py:346-380, 462-494, 654-685, 706-728) for
+// every family, from the int64 count tables.  Workgroup b takes one chunk of kScoreChunk columns of one
+// family (bisection over chunk_off: workgroup-uniform); a work-item takes one column.  For a fixed state
+// consecutive work-items read consecutive int64 of the [r, q] table.  A work-item adds its column's
+// terms in state order, the workgroup adds its work-items' sums in a fixed tree (work-items past the
+// family's last column add +0.0), and writes one partial per chunk: the order of every addition depends
+// only on the family's own shape.  fp64 throughout, no floating-point atomics.
+template <bool LL>
+__global__ __launch_bounds__(kScoreChunk) void k_fit_score(const FitFam *__restrict__ fams,
+                                                           const int64_t *__restrict__ chunk_off, int32_t n_fam,
+                                                           const int64_t *__restrict__ counts,
+                                                           const double *__restrict__ alpha,
+                                                           const double *__restrict__ beta, int32_t skip_empty,
+                                                           double *__restrict__ part, int64_t *__restrict__ part_obs) {
+  __shared__ double s_sum[kScoreChunk];
+  __shared__ int32_t s_obs[kScoreChunk];
+  const int64_t b = blockIdx.x;
+  int32_t lo = 0, hi = n_fam;  // chunk_off[lo] <= b < chunk_off[hi]; empty ranges do not occur (q >= 1)
+  while (hi - lo > 1) {
+    const int32_t mid = (lo + hi) >> 1;
+    if (chunk_off[mid] <= b) lo = mid;
+    else hi = mid;
+  }
+  const FitFam &F = fams[lo];
+  const int32_t card = F.card[0];
+  const int64_t ncol = F.size / card;
+  const int64_t col = (b - chunk_off[lo]) * kScoreChunk + threadIdx.x;
+  double sum = 0.0;
+  int32_t obs = 0;
+  if (col < ncol) {
+    const int64_t *cnt = counts + F.off + col;
+    int64_t nj = 0;
+    for (int32_t s = 0; s < card; ++s) nj += cnt[s * ncol];
+    obs = nj > 0;
+    if (LL) {
+      if (nj > 0) {
+        const double lnj = log((double)nj);
+        for (int32_t s = 0; s < card; ++s) {
+          const int64_t n = cnt[s * ncol];
+          if (n > 0) sum += (double)n * (log((double)n) - lnj);
+        }
+      }
+    } else if (nj > 0 || !skip_empty) {
+      const double be = beta[lo];
+      for (int32_t s = 0; s < card; ++s) sum += lgamma((double)cnt[s * ncol] + be);
+      sum -= lgamma((double)nj + alpha[lo]);
+    }
+  }
+  s_sum[threadIdx.x] = sum;
+  s_obs[threadIdx.x] = obs;
+  __syncthreads();
+  for (int32_t w = kScoreChunk / 2; w > 0; w >>= 1) {
+    if ((int32_t)threadIdx.x < w) {
+      s_sum[threadIdx.x] += s_sum[threadIdx.x + w];
+      s_obs[threadIdx.x] += s_obs[threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    part[b] = s_sum[0];
+    part_obs[b] = s_obs[0];
+  }
+}
+
+// One workgroup per family adds the family's chunk partials: work-item t takes partials t, t + 64, ... in
+// index order, then the same fixed tree.
+__global__ __launch_bounds__(kScoreSumBlock) void k_fit_score_sum(const int64_t *__restrict__ chunk_off,
+                                                                  const double *__restrict__ part,
+                                                                  const int64_t *__restrict__ part_obs,
+                                                                  double *__restrict__ scores,
+                                                                  int64_t *__restrict__ n_observed) {
+  __shared__ double s_sum[kScoreSumBlock];
+  __shared__ int64_t s_obs[kScoreSumBlock];
+  const int64_t begin = chunk_off[blockIdx.x], end = chunk_off[blockIdx.x + 1];
+  double sum = 0.0;
+  int64_t obs = 0;
+  for (int64_t i = begin + threadIdx.x; i < end; i += kScoreSumBlock) {
+    sum += part[i];
+    obs += part_obs[i];
+  }
+  s_sum[threadIdx.x] = sum;
+  s_obs[threadIdx.x] = obs;
+  __syncthreads();
+  for (int32_t w = kScoreSumBlock / 2; w > 0; w >>= 1) {
+    if ((int32_t)threadIdx.x < w) {
+      s_sum[threadIdx.x] += s_sum[threadIdx.x + w];
+      s_obs[threadIdx.x] += s_obs[threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    scores[blockIdx.x] = s_sum[0];
+    if (n_observed) n_observed[blockIdx.x] = s_obs[0];
+  }
+}
+
+// One workgroup per family marks the states that hold a count in any column (consecutive work-items read
+// consecutive bins) and counts the marks.  A cardinality is at most 255, so a state indexes s_seen.
+__global__ __launch_bounds__(256) void k_fit_states_observed(const FitFam *__restrict__ fams,
+                                                             const int64_t *__restrict__ counts,
+                                                             int64_t *__restrict__ n_states) {
+  __shared__ int32_t s_seen[256];
+  const FitFam &F = fams[blockIdx.x];
+  const int32_t card = F.card[0];
+  const int64_t size = F.size, ncol = size / card;
+  s_seen[threadIdx.x] = 0;
+  __syncthreads();
+  for (int64_t i = threadIdx.x; i < size; i += 256)
+    if (counts[F.off + i] > 0) atomicOr(&s_seen[i / ncol], 1);
+  __syncthreads();
+  for (int32_t w = 128; w > 0; w >>= 1) {
+    if ((int32_t)threadIdx.x < w) s_seen[threadIdx.x] += s_seen[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) n_states[blockIdx.x] = s_seen[0];
+}
+
 // ---------------------------------------------------------------------------- the handle's device side
 static std::mutex g_fit_mu;
 
 static void fit_free_device(FitHandle *h) {
-  for (void **p : {&h->d_fams, &h->d_groups, &h->d_col_off, &h->d_err}) {
+  for (void **p : {&h->d_fams, &h->d_groups, &h->d_col_off, &h->d_err, &h->d_chunk_off, &h->d_part, &h->d_part_obs}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
@@ -178,6 +297,20 @@ static int fit_upload(FitHandle *h) {
   HIP_TRY(hipMemcpy(h->d_groups, p.groups.data(), ng, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->d_col_off, p.col_off.data(), nc, hipMemcpyHostToDevice));
   h->device = dev;
+  return PGM_OK;
+}
+
+// what only the score launches need, on the device fit_upload chose (allocated by the first pgm_fit_score)
+static int fit_score_upload(FitHandle *h) {
+  std::lock_guard<std::mutex> lk(g_fit_mu);
+  if (h->d_part) return PGM_OK;
+  const FitPlan &p = h->p;
+  const size_t nc = p.chunk_off.size() * sizeof(int64_t), chunks = (size_t)p.chunk_off.back();
+  // d_part is set last: a call that failed half-way starts over (fit_free_device releases the rest)
+  if (!h->d_chunk_off) HIP_TRY(hipMalloc(&h->d_chunk_off, nc));
+  if (!h->d_part_obs) HIP_TRY(hipMalloc(&h->d_part_obs, chunks * sizeof(int64_t)));
+  HIP_TRY(hipMemcpy(h->d_chunk_off, p.chunk_off.data(), nc, hipMemcpyHostToDevice));
+  HIP_TRY(hipMalloc(&h->d_part, chunks * sizeof(double)));
   return PGM_OK;
 }
 
@@ -249,6 +382,46 @@ int pgm_fit_finish(void *plan, const void *counts, const double *pseudo, int32_t
   else
     hipLaunchKernelGGL(k_fit_finish<false>, dim3((unsigned)blocks), dim3(256), 0, S(stream), fams, col_off, nf, counts,
                        pseudo, bayes, values);
+  HIP_TRY(hipGetLastError());
+  return PGM_OK;
+}
+
+int pgm_fit_score(void *plan, const int64_t *counts, int32_t mode, const double *alpha, const double *beta,
+                  double *scores, int64_t *n_observed, void *stream) {
+  FitHandle *h = static_cast<FitHandle *>(plan);
+  int64_t blocks = 0;
+  const int st = fit_score_check(h, counts, mode, alpha, beta, scores, &blocks);
+  if (st != PGM_OK) return st;
+  int up = fit_upload(h);
+  if (up == PGM_OK) up = fit_score_upload(h);
+  if (up != PGM_OK) return up;
+  const FitFam *fams = static_cast<const FitFam *>(h->d_fams);
+  const int64_t *chunk_off = static_cast<const int64_t *>(h->d_chunk_off);
+  double *part = static_cast<double *>(h->d_part);
+  int64_t *part_obs = static_cast<int64_t *>(h->d_part_obs);
+  const int32_t nf = (int32_t)h->p.fams.size(), skip = mode & PGM_SCORE_SKIP_EMPTY ? 1 : 0;
+  const dim3 grid((unsigned)blocks), wg(kScoreChunk);
+  if (mode & PGM_SCORE_LL)
+    hipLaunchKernelGGL(k_fit_score<true>, grid, wg, 0, S(stream), fams, chunk_off, nf, counts, alpha, beta, skip, part,
+                       part_obs);
+  else
+    hipLaunchKernelGGL(k_fit_score<false>, grid, wg, 0, S(stream), fams, chunk_off, nf, counts, alpha, beta, skip, part,
+                       part_obs);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_fit_score_sum, dim3((unsigned)nf), dim3(kScoreSumBlock), 0, S(stream), chunk_off, part, part_obs,
+                     scores, n_observed);
+  HIP_TRY(hipGetLastError());
+  return PGM_OK;
+}
+
+int pgm_fit_states_observed(void *plan, const int64_t *counts, int64_t *n_states, void *stream) {
+  FitHandle *h = static_cast<FitHandle *>(plan);
+  const int st = fit_states_check(h, counts, n_states);
+  if (st != PGM_OK) return st;
+  const int up = fit_upload(h);
+  if (up != PGM_OK) return up;
+  hipLaunchKernelGGL(k_fit_states_observed, dim3((unsigned)h->p.fams.size()), dim3(256), 0, S(stream),
+                     static_cast<const FitFam *>(h->d_fams), counts, n_states);
   HIP_TRY(hipGetLastError());
   return PGM_OK;
 }

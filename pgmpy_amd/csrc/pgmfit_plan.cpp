@@ -15,7 +15,8 @@ int fit_plan_build(const pgm_fit_family *fams, int32_t n, FitPlan &out) {
   out.fams.resize((size_t)n);
   out.group_of.resize((size_t)n);
   out.col_off.resize((size_t)n + 1);
-  int64_t off = 0, cols = 0;
+  out.chunk_off.resize((size_t)n + 1);
+  int64_t off = 0, cols = 0, chunks = 0;
   for (int32_t f = 0; f < n; ++f) {
     const pgm_fit_family &in = fams[f];
     // the node and up to PGM_MAX_DIMS - 1 parents
@@ -46,6 +47,9 @@ int fit_plan_build(const pgm_fit_family *fams, int32_t n, FitPlan &out) {
     out.col_off[(size_t)f] = cols;
     off += size;
     cols += size / in.card[0];
+    // the score kernel's work list: (family, chunk) for every kScoreChunk columns of the family
+    out.chunk_off[(size_t)f] = chunks;
+    chunks += (size / in.card[0] + kScoreChunk - 1) / kScoreChunk;
     // consecutive families share a workgroup while their tables fit the LDS tile together; a family
     // larger than the tile is a group of its own and counts into global memory
     const bool big = size > kFitTileBins;
@@ -61,6 +65,7 @@ int fit_plan_build(const pgm_fit_family *fams, int32_t n, FitPlan &out) {
     out.group_of[(size_t)f] = (int32_t)out.groups.size() - 1;
   }
   out.col_off[(size_t)n] = cols;
+  out.chunk_off[(size_t)n] = chunks;
   out.total_bins = off;
   return PGM_OK;
 }
@@ -93,6 +98,29 @@ int fit_finish_check(const FitHandle *h, const void *counts, int32_t mode, const
   if (!counts) return pgmi_fail(PGM_EINVAL, "fit_finish: null counts");
   if (!values) return pgmi_fail(PGM_EINVAL, "fit_finish: null values");
   if (mode & ~(PGM_FIT_BAYES | PGM_FIT_WEIGHTED)) return pgmi_failf(PGM_EINVAL, "fit_finish: mode %d", mode);
+  return PGM_OK;
+}
+
+int fit_score_check(const FitHandle *h, const int64_t *counts, int32_t mode, const double *alpha, const double *beta,
+                    const double *scores, int64_t *blocks) {
+  if (!h) return pgmi_fail(PGM_EINVAL, "fit_score: null plan");
+  if (!counts) return pgmi_fail(PGM_EINVAL, "fit_score: null counts");
+  if (!scores) return pgmi_fail(PGM_EINVAL, "fit_score: null scores");
+  if (mode & ~(PGM_SCORE_LL | PGM_SCORE_SKIP_EMPTY)) return pgmi_failf(PGM_EINVAL, "fit_score: mode %d", mode);
+  if (!(mode & PGM_SCORE_LL)) {
+    if (!alpha) return pgmi_fail(PGM_EINVAL, "fit_score: null alpha in BD mode");
+    if (!beta) return pgmi_fail(PGM_EINVAL, "fit_score: null beta in BD mode");
+  }
+  const int64_t nb = h->p.chunk_off.back();
+  if (nb > INT32_MAX) return pgmi_failf(PGM_EINVAL, "fit_score: %lld workgroups (score the families in several plans)", (long long)nb);
+  if (blocks) *blocks = nb;
+  return PGM_OK;
+}
+
+int fit_states_check(const FitHandle *h, const int64_t *counts, const int64_t *n_states) {
+  if (!h) return pgmi_fail(PGM_EINVAL, "fit_states_observed: null plan");
+  if (!counts) return pgmi_fail(PGM_EINVAL, "fit_states_observed: null counts");
+  if (!n_states) return pgmi_fail(PGM_EINVAL, "fit_states_observed: null n_states");
   return PGM_OK;
 }
 

@@ -92,3 +92,36 @@ class FitPlan:
         N.check(L.pgm_fit_finish(self._h, N.ptr(counts), N.ptr(pseudo), mode, N.ptr(out), N.stream_handle()),
                 "fit_finish")
         return out
+
+    def score(self, counts, mode, alpha=None, beta=None, want_observed=False):
+        """The data-dependent sum of a structure score per family (pgm_fit_score) from the int64 count
+        tables: `mode` is N.SCORE_BD (alpha, beta: fp64 device tensors, one entry per family) or
+        N.SCORE_LL, | N.SCORE_SKIP_EMPTY.  Returns the fp64 device scores [n_families], and with
+        want_observed the int64 device counts of observed columns beside them."""
+        import torch
+
+        L = N.lib()
+        n = len(self.families)
+        if counts.dtype != torch.int64 or counts.numel() < self.total_bins or not counts.is_contiguous():
+            raise ValueError(f"counts must be a contiguous int64 device tensor of {self.total_bins} entries "
+                             "(weighted tables have no structure score)")
+        for name, t in (("alpha", alpha), ("beta", beta)):
+            if t is not None and (t.dtype != torch.float64 or t.numel() < n or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous fp64 device tensor with one entry per family")
+        scores = torch.empty(n, dtype=torch.float64, device=counts.device)
+        observed = torch.empty(n, dtype=torch.int64, device=counts.device) if want_observed else None
+        N.check(L.pgm_fit_score(self._h, N.ptr(counts), int(mode), N.ptr(alpha), N.ptr(beta), N.ptr(scores),
+                                N.ptr(observed), N.stream_handle()), "fit_score")
+        return (scores, observed) if want_observed else scores
+
+    def states_observed(self, counts):
+        """Per family the number of the node's states that hold a count in any column
+        (pgm_fit_states_observed): an int64 device tensor [n_families]."""
+        import torch
+
+        L = N.lib()
+        if counts.dtype != torch.int64 or counts.numel() < self.total_bins or not counts.is_contiguous():
+            raise ValueError(f"counts must be a contiguous int64 device tensor of {self.total_bins} entries")
+        out = torch.empty(len(self.families), dtype=torch.int64, device=counts.device)
+        N.check(L.pgm_fit_states_observed(self._h, N.ptr(counts), N.ptr(out), N.stream_handle()), "fit_states_observed")
+        return out
