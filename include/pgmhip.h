@@ -765,6 +765,37 @@ int pgm_fit_score(void *plan, const int64_t *counts, int32_t mode, const double 
  * 463-473): the caller's correction needs their number.  Integer work only; checked on the host. */
 int pgm_fit_states_observed(void *plan, const int64_t *counts, int64_t *n_states, void *stream);
 
+/* ---------------------------------------------------------------- conditional-independence tests
+ * (an extension of ABI 25.)  The Cressie-Read power-divergence test of X _|_ Y | Z for every family of a
+ * fit plan, read as (X, Y, Z1 .. Zk), from the int64 tables pgm_fit_count filled: family f's table is
+ * [rx][ry][qz], the Z configuration fastest.  The reference's CITests.power_divergence (CITests.py:445-499)
+ * over scipy.stats.chi2_contingency, one pandas groupby and one scipy call per stratum there.
+ *
+ * Per stratum z with n_z > 0 rows: the rows x and columns y whose marginal R_x, C_y is zero are dropped,
+ * dof_z = (rows left - 1)(columns left - 1); a stratum with dof_z = 0 adds nothing.  E_xy = R_x C_y / n_z.
+ * With PGM_CI_YATES and dof_z = 1 each observed cell first moves towards its expectation by
+ * min(0.5, |E - O|) (chi2_contingency's correction=True).  The stratum's statistic is
+ *   lambda = 1    sum (O - E)^2 / E
+ *   lambda = 0    2 sum O ln(O / E)            (a cell with O = 0 adds 0)
+ *   lambda = -1   2 sum E ln(E / O)            (a cell with O = 0 gives +inf)
+ *   otherwise     2 / (lambda (lambda + 1)) sum O ((O / E)^lambda - 1)
+ * stat[f] and dof[f] are the sums over the strata and pvalue[f] = Q(dof / 2, stat / 2), the chi-square
+ * survival function (csrc/pgm_igamc.h).  dof = 0: pvalue = 1 for a family without Z, NaN with one (the
+ * reference's 1 - chi2.cdf(0, 0)); stat = +inf: pvalue = 0.  stat, dof, pvalue: device arrays, one entry
+ * per family.  fp64 (weighted) tables are not accepted.
+ *
+ * A family's strata are cut into chunks of PGM_CI_CHUNK counted from its own stratum 0; a chunk is summed
+ * in a fixed order and a second launch adds a family's chunk partials in index order.  No floating-point
+ * atomics: a family's three outputs are bit-identical from run to run and do not depend on which other
+ * families share the plan.  The chunk partials live in the plan: calls on one plan must not overlap on
+ * different streams.  Every argument is checked on the host before any HIP call: PGM_EINVAL for a null
+ * plan / counts / stat / dof / pvalue, a non-finite lambda, unknown flag bits, or a family with fewer
+ * than two variables. */
+#define PGM_CI_YATES 1
+#define PGM_CI_CHUNK 128 /* strata per workgroup */
+int pgm_fit_citest(void *plan, const int64_t *counts, double lambda, int32_t flags, double *stat, int64_t *dof,
+                   double *pvalue, void *stream);
+
 /* ---------------------------------------------------------------- forward sampling
  * BayesianModelSampling.forward_sample / likelihood_weighted_sample / rejection_sample and
  * DiscreteBayesianNetwork.simulate (sampling/Sampling.py:30-406, DiscreteBayesianNetwork.py:1400-1704)

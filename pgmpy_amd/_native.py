@@ -187,6 +187,8 @@ class FitInfo(ctypes.Structure):
 FIT_MLE, FIT_BAYES, FIT_WEIGHTED = 0, 1, 2
 SCORE_BD, SCORE_LL, SCORE_SKIP_EMPTY = 0, 1, 2
 SCORE_CHUNK = 128  # PGM_SCORE_CHUNK
+CI_YATES = 1  # PGM_CI_YATES
+CI_CHUNK = 128  # PGM_CI_CHUNK
 
 
 class SampleInfo(ctypes.Structure):
@@ -376,6 +378,7 @@ _SIGS = {
     "pgm_fit_finish": ([_P, _P, _P, ctypes.c_int32, _P, _P], ctypes.c_int),
     "pgm_fit_score": ([_P, _P, ctypes.c_int32, _P, _P, _P, _P, _P], ctypes.c_int),
     "pgm_fit_states_observed": ([_P, _P, _P, _P], ctypes.c_int),
+    "pgm_fit_citest": ([_P, _P, ctypes.c_double, ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
     "pgm_sample_plan_create": ([ctypes.POINTER(FitFamily), ctypes.c_int32, ctypes.POINTER(_P)], ctypes.c_int),
     "pgm_sample_plan_destroy": ([_P], ctypes.c_int),
     "pgm_sample_plan_info": ([_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, ctypes.POINTER(SampleInfo),

@@ -24,6 +24,14 @@ static constexpr int kFitRowsPerBlock = 4096;
 // the families around it); the second launch sums a family's chunk partials with kScoreSumBlock work-items.
 static constexpr int kScoreChunk = PGM_SCORE_CHUNK;
 static constexpr int kScoreSumBlock = 64;
+// The CI-test kernels (pgm_fit_citest): one workgroup of kCiChunk work-items per chunk of kCiChunk strata
+// (Z configurations) of one test, chunks counted from the test's own stratum 0.  A table with
+// rx + ry <= kCiSmall (every table up to 8 x 8) takes one work-item per stratum with its marginals in LDS:
+// kCiSmall int64 per work-item, 16 KiB, plus 2 KiB for the tree: 18 KiB per workgroup, so 8 workgroups (16
+// waves) share a CU's 160 KiB, which is also what the kernel's registers allow (4 waves per SIMD).
+// Small tests without Z (one stratum) are packed kCiChunk to a workgroup instead of one workgroup each.
+static constexpr int kCiChunk = PGM_CI_CHUNK;
+static constexpr int kCiSmall = 16;
 
 // one family as the kernels read it (device memory; every field is workgroup-uniform: scalar loads)
 struct FitFam {
@@ -49,6 +57,11 @@ struct PGM_FIT_LOCAL FitPlan {
   std::vector<int32_t> group_of;  // group of each family
   std::vector<int64_t> col_off;   // first CPD column (parent configuration) of each family, + the total
   std::vector<int64_t> chunk_off;  // first score chunk (kScoreChunk columns) of each family, + the total
+  // the CI-test work lists: a family (X, Y, Z...) has qz = size / (rx ry) strata in ceil(qz / kCiChunk) chunks
+  std::vector<int64_t> ci_off;        // first chunk partial of each family, + the total
+  std::vector<int64_t> ci_multi_off;  // first workgroup of each family in the chunk launch (packed families: none)
+  std::vector<int32_t> ci_single;     // the packed families: qz = 1 and rx + ry <= kCiSmall
+  int32_t ci_bad = -1;                // first family with fewer than two variables (no CI test), or -1
   int64_t total_bins = 0;
   int n_cols = 0;  // 1 + the largest code column read
 };
@@ -60,6 +73,8 @@ struct PGM_FIT_LOCAL FitHandle {
   void *d_fams = nullptr, *d_groups = nullptr, *d_col_off = nullptr, *d_err = nullptr;
   // the score launches: chunk_off, and one fp64 partial + one int64 observed-column count per chunk
   void *d_chunk_off = nullptr, *d_part = nullptr, *d_part_obs = nullptr;
+  // the CI launches: the three work lists, and one fp64 statistic + one int64 dof per chunk
+  void *d_ci_off = nullptr, *d_ci_multi_off = nullptr, *d_ci_single = nullptr, *d_ci_part = nullptr, *d_ci_dof = nullptr;
 };
 
 // validate the families and lay the tables out; PGM_OK, or PGM_EINVAL with pgm_last_error set
@@ -74,4 +89,7 @@ PGM_FIT_LOCAL int fit_finish_check(const FitHandle *h, const void *counts, int32
 // the argument checks of pgm_fit_score (no HIP call); *blocks: workgroups of the chunk launch
 PGM_FIT_LOCAL int fit_score_check(const FitHandle *h, const int64_t *counts, int32_t mode, const double *alpha,
                                   const double *beta, const double *scores, int64_t *blocks);
+// the argument checks of pgm_fit_citest (no HIP call); *blocks: workgroups of the chunk launch (may be 0)
+PGM_FIT_LOCAL int fit_citest_check(const FitHandle *h, const int64_t *counts, double lambda, int32_t flags,
+                                   const double *stat, const int64_t *dof, const double *pvalue, int64_t *blocks);
 PGM_FIT_LOCAL int fit_states_check(const FitHandle *h, const int64_t *counts, const int64_t *n_states);

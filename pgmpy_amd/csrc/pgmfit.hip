@@ -9,6 +9,7 @@
 
 #include "pgm_fit.h"
 #include "pgm_hip_common.h"
+#include "pgm_igamc.h"
 
 // ---------------------------------------------------------------------------- counting
 // One launch counts every family: workgroup b takes row chunk b / n_groups for family group
@@ -268,11 +269,200 @@ __global__ __launch_bounds__(256) void k_fit_states_observed(const FitFam *__res
   if (threadIdx.x == 0) n_states[blockIdx.x] = s_seen[0];
 }
 
+// ---------------------------------------------------------------------------- CI tests
+// The power-divergence test of X _|_ Y | Z per family (X, Y, Z...) from its int64 table [rx][ry][qz]
+// (CITests.py:445-499 over scipy's chi2_contingency).  For a fixed cell consecutive strata are consecutive
+// int64, so work-items that take consecutive strata read coalesced.  kind: 0 lambda = 1, 1 lambda = 0,
+// 2 lambda = -1, 3 any other lambda; scale: the factor in front of the stratum's sum.
+__device__ inline double ci_term(double o, double e, double lambda, int32_t kind) {
+  if (kind == 0) {
+    const double d = o - e;
+    return d * d / e;
+  }
+  if (kind == 1) return o > 0.0 ? o * log(o / e) : 0.0;
+  if (kind == 2) return e * log(e / o);  // o = 0: e * log(inf) = +inf, as scipy's xlogy
+  return o * (pow(o / e, lambda) - 1.0);  // o = 0 and lambda < 0: 0 * inf = NaN, as scipy
+}
+
+// chi2_contingency's continuity correction: the observed cell moves towards e by min(0.5, |e - o|)
+__device__ inline double ci_yates(double o, double e) {
+  const double diff = e - o, mag = fmin(0.5, fabs(diff));
+  return diff > 0.0 ? o + mag : (diff < 0.0 ? o - mag : o);
+}
+
+// One stratum of a small table (rx + ry <= kCiSmall) by one work-item.  cnt points at the stratum's
+// [0][0] cell (cells are qz apart); m[k * kCiChunk], k < rx + ry, is the work-item's own column of the LDS
+// marginals (consecutive work-items are 8 bytes apart: conflict-free).  Cells are added row-major.
+__device__ inline void ci_stratum_small(const int64_t *__restrict__ cnt, int32_t rx, int32_t ry, int64_t qz,
+                                        double lambda, int32_t kind, double scale, int32_t yates, int64_t *m,
+                                        double &stat, int64_t &dof) {
+  stat = 0.0, dof = 0;
+  for (int32_t k = 0; k < rx + ry; ++k) m[k * kCiChunk] = 0;
+  for (int32_t x = 0; x < rx; ++x)
+    for (int32_t y = 0; y < ry; ++y) {
+      const int64_t o = cnt[((int64_t)x * ry + y) * qz];
+      m[x * kCiChunk] += o;
+      m[(rx + y) * kCiChunk] += o;
+    }
+  int64_t n = 0;
+  int32_t nr = 0, nc = 0;
+  for (int32_t x = 0; x < rx; ++x) n += m[x * kCiChunk], nr += m[x * kCiChunk] > 0;
+  for (int32_t y = 0; y < ry; ++y) nc += m[(rx + y) * kCiChunk] > 0;
+  const int32_t d = (nr - 1) * (nc - 1);
+  if (n == 0 || d <= 0) return;
+  const bool adjust = yates && d == 1;
+  double sum = 0.0;
+  for (int32_t x = 0; x < rx; ++x) {
+    const int64_t R = m[x * kCiChunk];
+    if (R == 0) continue;
+    for (int32_t y = 0; y < ry; ++y) {
+      const int64_t C = m[(rx + y) * kCiChunk];
+      if (C == 0) continue;
+      const double e = (double)R * (double)C / (double)n;
+      double o = (double)cnt[((int64_t)x * ry + y) * qz];
+      if (adjust) o = ci_yates(o, e);
+      sum += ci_term(o, e, lambda, kind);
+    }
+  }
+  stat = scale * sum, dof = d;
+}
+
+// Workgroup b takes one chunk of kCiChunk strata of one family (bisection over multi_off: workgroup-uniform;
+// packed families have an empty range there and are never found).  Small table: one work-item per
+// stratum, then a fixed tree over the workgroup (work-items past the last stratum add +0.0).  General
+// table (any cardinalities): the workgroup takes the chunk's strata one after the other; the marginals of
+// a stratum go to LDS (integer sums: exact), work-item t adds the cells t, t + kCiChunk, ... in index order,
+// the same fixed tree adds the work-items' sums, and work-item 0 adds the strata in index order.  Either
+// way the order of every addition depends only on the family's own shape.
+__global__ __launch_bounds__(kCiChunk) void k_fit_ci_chunk(const FitFam *__restrict__ fams,
+                                                           const int64_t *__restrict__ ci_off,
+                                                           const int64_t *__restrict__ multi_off, int32_t n_fam,
+                                                           const int64_t *__restrict__ counts, double lambda,
+                                                           int32_t kind, double scale, int32_t yates,
+                                                           double *__restrict__ part, int64_t *__restrict__ part_dof) {
+  __shared__ int64_t s_m[kCiSmall * kCiChunk];  // general path: R[0 .. rx), C[0 .. ry) (rx + ry <= 510)
+  __shared__ double s_sum[kCiChunk];
+  __shared__ int64_t s_dof[kCiChunk];
+  const int32_t tid = (int32_t)threadIdx.x;
+  const int64_t b = blockIdx.x;
+  int32_t lo = 0, hi = n_fam;  // the last family with multi_off[lo] <= b: the one whose range holds b
+  while (hi - lo > 1) {
+    const int32_t mid = (lo + hi) >> 1;
+    if (multi_off[mid] <= b) lo = mid;
+    else hi = mid;
+  }
+  const FitFam &F = fams[lo];
+  const int32_t rx = F.card[0], ry = F.card[1];
+  const int64_t qz = (int64_t)F.size / ((int64_t)rx * ry);
+  const int64_t chunk = b - multi_off[lo], z0 = chunk * kCiChunk;
+  const int64_t *cnt = counts + F.off;
+  double sum = 0.0;
+  int64_t dof = 0;
+  if (rx + ry <= kCiSmall) {
+    if (z0 + tid < qz) ci_stratum_small(cnt + z0 + tid, rx, ry, qz, lambda, kind, scale, yates, s_m + tid, sum, dof);
+    s_sum[tid] = sum;
+    s_dof[tid] = dof;
+    __syncthreads();
+    for (int32_t w = kCiChunk / 2; w > 0; w >>= 1) {
+      if (tid < w) {
+        s_sum[tid] += s_sum[tid + w];
+        s_dof[tid] += s_dof[tid + w];
+      }
+      __syncthreads();
+    }
+    sum = s_sum[0], dof = s_dof[0];
+  } else {
+    const int64_t z_end = z0 + kCiChunk < qz ? z0 + kCiChunk : qz;
+    const int32_t cells = rx * ry;
+    for (int64_t z = z0; z < z_end; ++z) {
+      for (int32_t k = tid; k < rx + ry; k += kCiChunk) {
+        int64_t v = 0;
+        if (k < rx)
+          for (int32_t y = 0; y < ry; ++y) v += cnt[((int64_t)k * ry + y) * qz + z];
+        else
+          for (int32_t x = 0; x < rx; ++x) v += cnt[((int64_t)x * ry + (k - rx)) * qz + z];
+        s_m[k] = v;
+      }
+      __syncthreads();
+      int64_t n = 0;
+      int32_t nr = 0, nc = 0;
+      for (int32_t x = 0; x < rx; ++x) n += s_m[x], nr += s_m[x] > 0;
+      for (int32_t y = 0; y < ry; ++y) nc += s_m[rx + y] > 0;
+      const int32_t d = (nr - 1) * (nc - 1);
+      if (n > 0 && d > 0) {  // workgroup-uniform: every work-item read the same marginals
+        const bool adjust = yates && d == 1;
+        double mine = 0.0;
+        for (int32_t i = tid; i < cells; i += kCiChunk) {
+          const int64_t R = s_m[i / ry], C = s_m[rx + i % ry];
+          if (R == 0 || C == 0) continue;
+          const double e = (double)R * (double)C / (double)n;
+          double o = (double)cnt[(int64_t)i * qz + z];
+          if (adjust) o = ci_yates(o, e);
+          mine += ci_term(o, e, lambda, kind);
+        }
+        s_sum[tid] = mine;
+        __syncthreads();
+        for (int32_t w = kCiChunk / 2; w > 0; w >>= 1) {
+          if (tid < w) s_sum[tid] += s_sum[tid + w];
+          __syncthreads();
+        }
+        if (tid == 0) sum += scale * s_sum[0], dof += d;
+      }
+      __syncthreads();  // s_m and s_sum are rewritten by the next stratum
+    }
+  }
+  if (tid == 0) {
+    part[ci_off[lo] + chunk] = sum;
+    part_dof[ci_off[lo] + chunk] = dof;
+  }
+}
+
+// The packed families (one stratum, small table): one work-item per family, kCiChunk families per workgroup,
+// so the n (n - 1) / 2 tests of PC's level 0 are one launch of n (n - 1) / 2 / kCiChunk workgroups.  The value
+// is the family's only chunk partial.
+__global__ __launch_bounds__(kCiChunk) void k_fit_ci_single(const FitFam *__restrict__ fams,
+                                                            const int64_t *__restrict__ ci_off,
+                                                            const int32_t *__restrict__ single, int32_t n_single,
+                                                            const int64_t *__restrict__ counts, double lambda,
+                                                            int32_t kind, double scale, int32_t yates,
+                                                            double *__restrict__ part, int64_t *__restrict__ part_dof) {
+  __shared__ int64_t s_m[kCiSmall * kCiChunk];
+  const int64_t i = (int64_t)blockIdx.x * kCiChunk + threadIdx.x;
+  if (i >= n_single) return;
+  const int32_t f = single[i];
+  const FitFam &F = fams[f];
+  double sum;
+  int64_t dof;
+  ci_stratum_small(counts + F.off, F.card[0], F.card[1], 1, lambda, kind, scale, yates, s_m + threadIdx.x, sum, dof);
+  part[ci_off[f]] = sum;
+  part_dof[ci_off[f]] = dof;
+}
+
+// One work-item per family adds the family's chunk partials in index order and turns the sums into the
+// p-value.  dof = 0: 1 without Z (chi2_contingency's answer), NaN with Z (the reference's 1 - chi2.cdf(0, 0)).
+__global__ __launch_bounds__(kCiChunk) void k_fit_ci_finish(const FitFam *__restrict__ fams,
+                                                            const int64_t *__restrict__ ci_off, int32_t n_fam,
+                                                            const double *__restrict__ part,
+                                                            const int64_t *__restrict__ part_dof,
+                                                            double *__restrict__ stat, int64_t *__restrict__ dof,
+                                                            double *__restrict__ pvalue) {
+  const int64_t f = (int64_t)blockIdx.x * kCiChunk + threadIdx.x;
+  if (f >= n_fam) return;
+  double s = 0.0;
+  int64_t d = 0;
+  for (int64_t i = ci_off[f]; i < ci_off[f + 1]; ++i) s += part[i], d += part_dof[i];
+  stat[f] = s;
+  dof[f] = d;
+  if (d == 0) pvalue[f] = fams[f].n_vars > 2 ? NAN : 1.0;
+  else pvalue[f] = pgm_chi2_sf(s, (double)d);
+}
+
 // ---------------------------------------------------------------------------- the handle's device side
 static std::mutex g_fit_mu;
 
 static void fit_free_device(FitHandle *h) {
-  for (void **p : {&h->d_fams, &h->d_groups, &h->d_col_off, &h->d_err, &h->d_chunk_off, &h->d_part, &h->d_part_obs}) {
+  for (void **p : {&h->d_fams, &h->d_groups, &h->d_col_off, &h->d_err, &h->d_chunk_off, &h->d_part, &h->d_part_obs,
+                   &h->d_ci_off, &h->d_ci_multi_off, &h->d_ci_single, &h->d_ci_part, &h->d_ci_dof}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
@@ -311,6 +501,26 @@ static int fit_score_upload(FitHandle *h) {
   if (!h->d_part_obs) HIP_TRY(hipMalloc(&h->d_part_obs, chunks * sizeof(int64_t)));
   HIP_TRY(hipMemcpy(h->d_chunk_off, p.chunk_off.data(), nc, hipMemcpyHostToDevice));
   HIP_TRY(hipMalloc(&h->d_part, chunks * sizeof(double)));
+  return PGM_OK;
+}
+
+// what only the CI launches need, on the device fit_upload chose (allocated by the first pgm_fit_citest)
+static int fit_ci_upload(FitHandle *h) {
+  std::lock_guard<std::mutex> lk(g_fit_mu);
+  if (h->d_ci_part) return PGM_OK;
+  const FitPlan &p = h->p;
+  const size_t no = p.ci_off.size() * sizeof(int64_t), chunks = (size_t)p.ci_off.back();
+  const size_t ns = (p.ci_single.empty() ? 1 : p.ci_single.size()) * sizeof(int32_t);
+  // d_ci_part is set last: a call that failed half-way starts over (fit_free_device releases the rest)
+  if (!h->d_ci_off) HIP_TRY(hipMalloc(&h->d_ci_off, no));
+  if (!h->d_ci_multi_off) HIP_TRY(hipMalloc(&h->d_ci_multi_off, no));
+  if (!h->d_ci_single) HIP_TRY(hipMalloc(&h->d_ci_single, ns));
+  if (!h->d_ci_dof) HIP_TRY(hipMalloc(&h->d_ci_dof, chunks * sizeof(int64_t)));
+  HIP_TRY(hipMemcpy(h->d_ci_off, p.ci_off.data(), no, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->d_ci_multi_off, p.ci_multi_off.data(), no, hipMemcpyHostToDevice));
+  if (!p.ci_single.empty())
+    HIP_TRY(hipMemcpy(h->d_ci_single, p.ci_single.data(), p.ci_single.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMalloc(&h->d_ci_part, chunks * sizeof(double)));
   return PGM_OK;
 }
 
@@ -410,6 +620,42 @@ int pgm_fit_score(void *plan, const int64_t *counts, int32_t mode, const double 
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_fit_score_sum, dim3((unsigned)nf), dim3(kScoreSumBlock), 0, S(stream), chunk_off, part, part_obs,
                      scores, n_observed);
+  HIP_TRY(hipGetLastError());
+  return PGM_OK;
+}
+
+int pgm_fit_citest(void *plan, const int64_t *counts, double lambda, int32_t flags, double *stat, int64_t *dof,
+                   double *pvalue, void *stream) {
+  FitHandle *h = static_cast<FitHandle *>(plan);
+  int64_t blocks = 0;
+  const int st = fit_citest_check(h, counts, lambda, flags, stat, dof, pvalue, &blocks);
+  if (st != PGM_OK) return st;
+  int up = fit_upload(h);
+  if (up == PGM_OK) up = fit_ci_upload(h);
+  if (up != PGM_OK) return up;
+  const FitFam *fams = static_cast<const FitFam *>(h->d_fams);
+  const int64_t *ci_off = static_cast<const int64_t *>(h->d_ci_off);
+  const int64_t *multi_off = static_cast<const int64_t *>(h->d_ci_multi_off);
+  const int32_t *single = static_cast<const int32_t *>(h->d_ci_single);
+  double *part = static_cast<double *>(h->d_ci_part);
+  int64_t *part_dof = static_cast<int64_t *>(h->d_ci_dof);
+  const int32_t nf = (int32_t)h->p.fams.size(), ns = (int32_t)h->p.ci_single.size();
+  const int32_t kind = lambda == 1.0 ? 0 : lambda == 0.0 ? 1 : lambda == -1.0 ? 2 : 3;
+  const double scale = kind == 0 ? 1.0 : kind == 3 ? 2.0 / (lambda * (lambda + 1.0)) : 2.0;
+  const int32_t yates = flags & PGM_CI_YATES ? 1 : 0;
+  const dim3 wg(kCiChunk);
+  if (blocks > 0) {
+    hipLaunchKernelGGL(k_fit_ci_chunk, dim3((unsigned)blocks), wg, 0, S(stream), fams, ci_off, multi_off, nf, counts,
+                       lambda, kind, scale, yates, part, part_dof);
+    HIP_TRY(hipGetLastError());
+  }
+  if (ns > 0) {
+    hipLaunchKernelGGL(k_fit_ci_single, dim3((unsigned)((ns + kCiChunk - 1) / kCiChunk)), wg, 0, S(stream), fams, ci_off,
+                       single, ns, counts, lambda, kind, scale, yates, part, part_dof);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_fit_ci_finish, dim3((unsigned)((nf + kCiChunk - 1) / kCiChunk)), wg, 0, S(stream), fams, ci_off, nf,
+                     part, part_dof, stat, dof, pvalue);
   HIP_TRY(hipGetLastError());
   return PGM_OK;
 }

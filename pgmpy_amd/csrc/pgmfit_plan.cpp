@@ -2,6 +2,7 @@
 // the layout of the flat count buffer, the grouping of families per workgroup and the argument checks
 // of the pgm_fit_* entry points.  No HIP include: this unit is tested on the CPU on its own
 // (tools/fit_plan_selftest.cpp).  The kernels and launches are pgmfit.hip.
+#include <cmath>
 #include <cstring>
 #include <new>
 
@@ -16,7 +17,9 @@ int fit_plan_build(const pgm_fit_family *fams, int32_t n, FitPlan &out) {
   out.group_of.resize((size_t)n);
   out.col_off.resize((size_t)n + 1);
   out.chunk_off.resize((size_t)n + 1);
-  int64_t off = 0, cols = 0, chunks = 0;
+  out.ci_off.resize((size_t)n + 1);
+  out.ci_multi_off.resize((size_t)n + 1);
+  int64_t off = 0, cols = 0, chunks = 0, ci_chunks = 0, ci_blocks = 0;
   for (int32_t f = 0; f < n; ++f) {
     const pgm_fit_family &in = fams[f];
     // the node and up to PGM_MAX_DIMS - 1 parents
@@ -50,6 +53,18 @@ int fit_plan_build(const pgm_fit_family *fams, int32_t n, FitPlan &out) {
     // the score kernel's work list: (family, chunk) for every kScoreChunk columns of the family
     out.chunk_off[(size_t)f] = chunks;
     chunks += (size / in.card[0] + kScoreChunk - 1) / kScoreChunk;
+    // the CI work lists: a packed family has a partial of its own but no workgroup in the chunk launch
+    out.ci_off[(size_t)f] = ci_chunks;
+    out.ci_multi_off[(size_t)f] = ci_blocks;
+    if (in.n_vars < 2) {
+      if (out.ci_bad < 0) out.ci_bad = f;
+    } else {
+      const int64_t qz = size / ((int64_t)in.card[0] * in.card[1]);
+      const int64_t nc = (qz + kCiChunk - 1) / kCiChunk;
+      ci_chunks += nc;
+      if (qz == 1 && in.card[0] + in.card[1] <= kCiSmall) out.ci_single.push_back(f);
+      else ci_blocks += nc;
+    }
     // consecutive families share a workgroup while their tables fit the LDS tile together; a family
     // larger than the tile is a group of its own and counts into global memory
     const bool big = size > kFitTileBins;
@@ -66,6 +81,8 @@ int fit_plan_build(const pgm_fit_family *fams, int32_t n, FitPlan &out) {
   }
   out.col_off[(size_t)n] = cols;
   out.chunk_off[(size_t)n] = chunks;
+  out.ci_off[(size_t)n] = ci_chunks;
+  out.ci_multi_off[(size_t)n] = ci_blocks;
   out.total_bins = off;
   return PGM_OK;
 }
@@ -113,6 +130,24 @@ int fit_score_check(const FitHandle *h, const int64_t *counts, int32_t mode, con
   }
   const int64_t nb = h->p.chunk_off.back();
   if (nb > INT32_MAX) return pgmi_failf(PGM_EINVAL, "fit_score: %lld workgroups (score the families in several plans)", (long long)nb);
+  if (blocks) *blocks = nb;
+  return PGM_OK;
+}
+
+int fit_citest_check(const FitHandle *h, const int64_t *counts, double lambda, int32_t flags, const double *stat,
+                     const int64_t *dof, const double *pvalue, int64_t *blocks) {
+  if (!h) return pgmi_fail(PGM_EINVAL, "fit_citest: null plan");
+  if (!counts) return pgmi_fail(PGM_EINVAL, "fit_citest: null counts");
+  if (!stat) return pgmi_fail(PGM_EINVAL, "fit_citest: null stat");
+  if (!dof) return pgmi_fail(PGM_EINVAL, "fit_citest: null dof");
+  if (!pvalue) return pgmi_fail(PGM_EINVAL, "fit_citest: null pvalue");
+  if (!std::isfinite(lambda)) return pgmi_failf(PGM_EINVAL, "fit_citest: lambda %g is not finite", lambda);
+  if (flags & ~PGM_CI_YATES) return pgmi_failf(PGM_EINVAL, "fit_citest: flags %d", flags);
+  if (h->p.ci_bad >= 0)
+    return pgmi_failf(PGM_EINVAL, "fit_citest: family %d has fewer than two variables (a test needs X and Y)",
+                      h->p.ci_bad);
+  const int64_t nb = h->p.ci_multi_off.back();
+  if (nb > INT32_MAX) return pgmi_failf(PGM_EINVAL, "fit_citest: %lld workgroups (test the families in several plans)", (long long)nb);
   if (blocks) *blocks = nb;
   return PGM_OK;
 }

@@ -19,11 +19,8 @@ import numpy as np
 from .. import _native as N
 from .. import engine as E
 from ._fit import FitPlan
+from ._rounds import SCORE_BIN_BUDGET, rounds as _rounds  # noqa: F401  (module attributes the tests patch)
 from .base import BaseEstimator
-
-# Largest number of count bins one round of local_scores keeps on the device (int64: 128 MiB).  A batch
-# with more is scored in several rounds; a single family above the budget runs alone.
-SCORE_BIN_BUDGET = 1 << 24
 
 _DISCRETE = ("k2", "bdeu", "bds", "bic-d", "aic-d", "ll-d")
 _NOT_BUILT = ("bic-g", "ll-g", "aic-g", "bic-cg", "ll-cg", "aic-cg")
@@ -51,20 +48,6 @@ def get_scoring_method(scoring_method, data, use_cache=True):
     else:
         raise ValueError(f"scoring_method should either be one of {list(_DISCRETE)} or an instance of StructureScore")
     return score, score
-
-
-def _rounds(sizes, budget):
-    """Consecutive runs of families whose bins stay within `budget`; a family above it is a run of its own."""
-    rounds, cur, bins = [], [], 0
-    for i, s in enumerate(sizes):
-        if cur and bins + s > budget:
-            rounds.append(cur)
-            cur, bins = [], 0
-        cur.append(i)
-        bins += s
-    if cur:
-        rounds.append(cur)
-    return rounds
 
 
 class StructureScore(BaseEstimator):

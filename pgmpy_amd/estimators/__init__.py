@@ -1,20 +1,26 @@
 """Estimators (mirror of pgmpy/estimators).  Parameter learning: the counting and the normalisation run
 in two fused HIP launches per model (pgm_fit_count, pgm_fit_finish).  Structure learning: the discrete
 structure scores and HillClimbSearch score all the candidate families of a step in one count launch and
-one score launch (pgm_fit_score).
+one score launch (pgm_fit_score); the conditional-independence tests and PC test all the candidate
+separating sets of a level in one count launch and one CI launch per round (pgm_fit_citest).
 
 Built: BaseEstimator, ParameterEstimator, MaximumLikelihoodEstimator, BayesianEstimator; StructureScore,
 K2, BDeu, BDs, LogLikeliHood, BIC, AIC, get_scoring_method; HillClimbSearch, ExpertKnowledge (required and
-forbidden edges).  Not built: ExpectationMaximization, MarginalEstimator / IPF
-(MaximumLikelihoodEstimator on a JunctionTree), PC, GES, MMHC, TreeSearch, ExhaustiveSearch, the Gaussian
-and conditional-Gaussian scores.
+forbidden edges); CITests (chi_square, g_sq, log_likelihood, modified_log_likelihood, power_divergence,
+get_callable_ci_test, CITester) and PC (orig / stable / parallel; a PDAG from pgmpy_amd.base).  Not built:
+ExpectationMaximization, MarginalEstimator / IPF (MaximumLikelihoodEstimator on a JunctionTree), GES, MMHC,
+TreeSearch, ExhaustiveSearch, the Gaussian and conditional-Gaussian scores, the continuous and mixed CI
+tests (pearsonr, gcm, pillai) and independence_match.
 """
 from .base import BaseEstimator, ParameterEstimator
 from .MLE import MaximumLikelihoodEstimator
 from .BayesianEstimator import BayesianEstimator
 from .StructureScore import AIC, BIC, K2, BDeu, BDs, LogLikeliHood, StructureScore, get_scoring_method
 from .HillClimbSearch import ExpertKnowledge, HillClimbSearch
+from . import CITests
+from .CITests import CITester
+from .PC import PC
 
 __all__ = ["BaseEstimator", "ParameterEstimator", "MaximumLikelihoodEstimator", "BayesianEstimator",
            "StructureScore", "K2", "BDeu", "BDs", "LogLikeliHood", "BIC", "AIC", "get_scoring_method",
-           "HillClimbSearch", "ExpertKnowledge"]
+           "HillClimbSearch", "ExpertKnowledge", "CITests", "CITester", "PC"]

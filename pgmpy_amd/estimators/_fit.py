@@ -114,6 +114,24 @@ class FitPlan:
                                 N.ptr(observed), N.stream_handle()), "fit_score")
         return (scores, observed) if want_observed else scores
 
+    def citest(self, counts, lambda_, yates=True):
+        """The power-divergence test of X _|_ Y | Z for every family read as (X, Y, Z...) from its int64
+        count table (pgm_fit_citest): the device tensors (stat fp64, dof int64, pvalue fp64), one entry
+        per family.  `yates`: chi2_contingency's continuity correction in strata with one degree of freedom."""
+        import torch
+
+        L = N.lib()
+        n = len(self.families)
+        if counts.dtype != torch.int64 or counts.numel() < self.total_bins or not counts.is_contiguous():
+            raise ValueError(f"counts must be a contiguous int64 device tensor of {self.total_bins} entries "
+                             "(weighted tables have no CI test)")
+        stat = torch.empty(n, dtype=torch.float64, device=counts.device)
+        dof = torch.empty(n, dtype=torch.int64, device=counts.device)
+        pvalue = torch.empty(n, dtype=torch.float64, device=counts.device)
+        N.check(L.pgm_fit_citest(self._h, N.ptr(counts), float(lambda_), N.CI_YATES if yates else 0, N.ptr(stat),
+                                 N.ptr(dof), N.ptr(pvalue), N.stream_handle()), "fit_citest")
+        return stat, dof, pvalue
+
     def states_observed(self, counts):
         """Per family the number of the node's states that hold a count in any column
         (pgm_fit_states_observed): an int64 device tensor [n_families]."""
