@@ -796,6 +796,56 @@ int pgm_fit_states_observed(void *plan, const int64_t *counts, int64_t *n_states
 int pgm_fit_citest(void *plan, const int64_t *counts, double lambda, int32_t flags, double *stat, int64_t *dof,
                    double *pvalue, void *stream);
 
+/* ---------------------------------------------------------------- expectation maximisation: the E-step
+ * (an extension of ABI 25.)  The expected family counts of a network with latent variables, for the
+ * reference's ExpectationMaximization (estimators/EM.py:130-180, 389-397), in one launch: no frame of
+ * unique rows x latent configurations, no get_value per CPD and expanded row.  The M-step is
+ * pgm_fit_finish | PGM_FIT_WEIGHTED on the tables this call fills.
+ *
+ * plan is an ordinary fit plan: the families whose CPDs EM updates.  values (device, fp64: the current
+ * CPDs) and tables (device, fp64, ADDED to, as pgm_fit_count does) have the plan's flat layout.
+ * latent_cols (host, n_latent entries) names the code columns that are latent.  They are virtual: codes
+ * is never read for them and n_cols bounds the observed columns only.  A latent's cardinality is the one
+ * its families give it.
+ *
+ * For a row r of the window, with L the product of the latent cardinalities:
+ *   p_l = product over the families with a latent in scope of max(values[entry], PGM_EM_FLOOR), the entry
+ *         taken from the row's observed codes with the latents set to configuration l   (EM.py:116-126)
+ *   Z = sum_l p_l,  w_l = p_l / Z
+ *   tables[entry(l)] += w_l for every l, in every family with a latent
+ *   tables[entry] += 1.0 in a family without one (its factor is the same for every l and cancels in w,
+ *         and sum_l w_l = 1): those tables hold exact integers
+ *   loglik[row0 + r] = log Z + sum over the latent-free families of log max(values[entry], PGM_EM_FLOOR)
+ *         (loglik: optional, device, fp64, ld entries indexed by buffer row)
+ * A row with PGM_EV_MISSING in any observed column of any family of the plan adds nothing to any table and
+ * its loglik is 0 (the reference drops such rows, EM.py:93-102).  A row with a code that is neither
+ * missing nor a state adds nothing either and the call returns PGM_EINDEX, through the device flag of
+ * pgm_fit_count (so the call synchronises the stream).
+ *
+ * At most PGM_EM_MAX_FAMILIES clamped factors make p_l >= 1e-320, above fp64's smallest denormal: Z > 0
+ * for every row and no row needs a rule of its own; below about 1e-290 p_l is denormal and the weights lose
+ * precision.  The tables are added with fp64 atomics in no fixed order: nothing is bit-identical from run
+ * to run.
+ *
+ * Every argument is checked on the host before any HIP call: PGM_EINVAL for a null plan / values / codes /
+ * tables, n_latent outside 1 .. PGM_EM_MAX_LATENT, a latent column listed twice, in no family, or with two
+ * cardinalities, L > PGM_EM_MAX_CONFIGS, more than PGM_EM_MAX_FAMILIES families with a latent, an observed
+ * column >= n_cols, and a window outside ld.  pgm_fit_estep_info needs no device. */
+#define PGM_EM_MAX_LATENT 8      /* latent variables of one call */
+#define PGM_EM_MAX_CONFIGS 4096  /* product of their cardinalities */
+#define PGM_EM_MAX_FAMILIES 32   /* families of the plan with a latent in scope */
+#define PGM_EM_FLOOR 1e-10       /* EM.py:116-126: max(cpd value, 1e-10) */
+typedef struct {
+  int32_t n_latent, n_configs;                 /* L = n_configs */
+  int32_t n_latent_families, n_plain_families; /* families with / without a latent in scope */
+  int32_t block, rows_per_block;               /* work-items per workgroup, rows it takes for its group */
+  int32_t lds_bytes, reserved;                 /* dynamic LDS of the launch: the fp64 tile + the index scratch */
+} pgm_em_info_t;
+int pgm_fit_estep_info(void *plan, const int32_t *latent_cols, int32_t n_latent, pgm_em_info_t *info);
+int pgm_fit_estep(void *plan, const int32_t *latent_cols, int32_t n_latent, const double *values,
+                  const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
+                  double *tables, double *loglik, void *stream);
+
 /* ---------------------------------------------------------------- forward sampling
  * BayesianModelSampling.forward_sample / likelihood_weighted_sample / rejection_sample and
  * DiscreteBayesianNetwork.simulate (sampling/Sampling.py:30-406, DiscreteBayesianNetwork.py:1400-1704)

@@ -189,6 +189,14 @@ SCORE_BD, SCORE_LL, SCORE_SKIP_EMPTY = 0, 1, 2
 SCORE_CHUNK = 128  # PGM_SCORE_CHUNK
 CI_YATES = 1  # PGM_CI_YATES
 CI_CHUNK = 128  # PGM_CI_CHUNK
+EM_MAX_LATENT, EM_MAX_CONFIGS, EM_MAX_FAMILIES, EM_FLOOR = 8, 4096, 32, 1e-10  # PGM_EM_*
+
+
+class EmInfo(ctypes.Structure):
+    """pgm_em_info_t: the latent side and launch geometry of a pgm_fit_estep call (host-only query)."""
+    _fields_ = [("n_latent", ctypes.c_int32), ("n_configs", ctypes.c_int32), ("n_latent_families", ctypes.c_int32),
+                ("n_plain_families", ctypes.c_int32), ("block", ctypes.c_int32), ("rows_per_block", ctypes.c_int32),
+                ("lds_bytes", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class SampleInfo(ctypes.Structure):
@@ -379,6 +387,9 @@ _SIGS = {
     "pgm_fit_score": ([_P, _P, ctypes.c_int32, _P, _P, _P, _P, _P], ctypes.c_int),
     "pgm_fit_states_observed": ([_P, _P, _P, _P], ctypes.c_int),
     "pgm_fit_citest": ([_P, _P, ctypes.c_double, ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
+    "pgm_fit_estep_info": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(EmInfo)], ctypes.c_int),
+    "pgm_fit_estep": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_int64,
+                       ctypes.c_int64, ctypes.c_int64, _P, _P, _P], ctypes.c_int),
     "pgm_sample_plan_create": ([ctypes.POINTER(FitFamily), ctypes.c_int32, ctypes.POINTER(_P)], ctypes.c_int),
     "pgm_sample_plan_destroy": ([_P], ctypes.c_int),
     "pgm_sample_plan_info": ([_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, ctypes.POINTER(SampleInfo),

@@ -92,4 +92,25 @@ PGM_FIT_LOCAL int fit_score_check(const FitHandle *h, const int64_t *counts, int
 // the argument checks of pgm_fit_citest (no HIP call); *blocks: workgroups of the chunk launch (may be 0)
 PGM_FIT_LOCAL int fit_citest_check(const FitHandle *h, const int64_t *counts, double lambda, int32_t flags,
                                    const double *stat, const int64_t *dof, const double *pvalue, int64_t *blocks);
+// The latent side of one pgm_fit_estep call, passed to the kernel by value (every field is
+// workgroup-uniform: scalar loads from the kernarg segment).  Latent configuration l is the mixed-radix
+// number of the latents' states in the order of latent_cols, the last one fastest.
+struct EmSpec {
+  int32_t n_latent, n_configs;  // L = n_configs = the product of card[]
+  int32_t n_lat_fam, n_fam;     // families with a latent in scope; families of the plan
+  int32_t col[PGM_EM_MAX_LATENT], card[PGM_EM_MAX_LATENT];
+  int32_t fam[PGM_EM_MAX_FAMILIES];                        // the families with a latent, ascending
+  int32_t stride[PGM_EM_MAX_FAMILIES][PGM_EM_MAX_LATENT];  // table stride of latent j in fam[k] (0: not in scope)
+};
+// dynamic LDS of the E-step launch: the fp64 tile, then the [family][work-item] scratch of observed indices
+static constexpr int32_t fit_estep_lds(int32_t n_lat_fam) {
+  return kFitTileBins * (int32_t)sizeof(double) + n_lat_fam * kFitBlock * (int32_t)sizeof(int32_t);
+}
+// the latent columns of pgm_fit_estep(_info) against the plan (no HIP call); what: the entry point's name
+PGM_FIT_LOCAL int fit_estep_spec(const FitHandle *h, const int32_t *latent_cols, int32_t n_latent, const char *what,
+                                 EmSpec *spec, int32_t *n_obs_cols);
+// the argument checks of pgm_fit_estep (no HIP call); *blocks: workgroups of the launch
+PGM_FIT_LOCAL int fit_estep_check(const FitHandle *h, const int32_t *latent_cols, int32_t n_latent, const double *values,
+                                  const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
+                                  const double *tables, EmSpec *spec, int64_t *blocks);
 PGM_FIT_LOCAL int fit_states_check(const FitHandle *h, const int64_t *counts, const int64_t *n_states);

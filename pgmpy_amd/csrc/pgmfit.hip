@@ -1,6 +1,7 @@
 // pgmfit.hip — parameter learning on the device (gfx950): the family-count kernel and the CPD finishing
 // kernel behind DiscreteBayesianNetwork.fit / fit_update, and their C-ABI (pgm_fit_plan_destroy,
-// pgm_fit_count, pgm_fit_finish), and the structure-score kernels behind estimators/StructureScore.py and
+// pgm_fit_count, pgm_fit_finish), the E-step kernel of ExpectationMaximization (pgm_fit_estep), and the
+// structure-score kernels behind estimators/StructureScore.py and
 // HillClimbSearch (pgm_fit_score).  Replaces the reference's per-node pandas groupby
 // (estimators/base.py:67-176) and the per-CPD normalisation (MLE.py:183-212, BayesianEstimator.py:252-264).
 // The host side (validation, table layout, family groups, argument checks) is pgmfit_plan.cpp.
@@ -105,6 +106,159 @@ __global__ __launch_bounds__(kFitBlock) void k_fit_count(const FitFam *__restric
     for (int32_t i = (int32_t)tid; i < g.bins; i += kFitBlock) {
       const Bin v = lds[i];
       if (v != Bin(0)) atomicAdd(&out[i], (Out)v);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------- the E-step
+// Expected family counts of a network with latent variables (pgm_fit_estep; the reference's
+// _compute_weights + weighted state_counts, EM.py:130-180).  The geometry is k_fit_count<true>'s: workgroup
+// b takes row chunk b / n_groups for family group b % n_groups, privatises the group's run of bins in LDS
+// as fp64 and adds the non-zero bins to global memory; a global group adds straight into its table.
+// A work-item takes one row at a time.  It first walks every family of the plan: the observed part of the
+// family's index (code x stride over the observed variables) decides whether the row is counted at all (a
+// missing or bad code in any family drops the row from every table), and for a family with a latent it
+// goes to the LDS scratch [family][work-item] (consecutive lanes, consecutive banks).  Pass 1 adds
+// Z = sum_l p_l over the latent configurations, p_l the product over ALL latent families of the plan of
+// max(value, floor), the values gathered from global memory (the tables are small: L1 / L2).  Pass 2
+// recomputes p_l and adds p_l / Z to the latent families of the workgroup's own group only; a latent-free
+// family of the group gets 1.0 (its factor is the same for every l and cancels; sum_l w_l = 1).  The
+// latent digits of l, the latent strides (EmSpec, in the kernarg segment) and the family descriptors are
+// workgroup-uniform: scalar work.  Nothing of size [L, rows] leaves the CU.  The workgroups of group 0
+// write loglik.
+// LDS: the 32 KiB fp64 tile + 1 KiB of scratch per latent family (fit_estep_lds).  A plan with up to 8
+// latent families takes at most 40 KiB: 4 workgroups (16 waves) share a CU's 160 KiB; at the cap of 32
+// families it is 64 KiB: 2 workgroups, 8 waves per CU.
+__device__ inline bool em_observed_index(const FitFam &F, const EmSpec &s, const uint8_t *__restrict__ codes,
+                                         int64_t ld, int64_t row, int32_t &idx, bool &bad) {
+  bool ok = true;
+  idx = 0;
+  for (int32_t v = 0; v < F.n_vars; ++v) {
+    const int32_t col = F.col[v];
+    bool latent = false;
+    for (int32_t j = 0; j < s.n_latent; ++j) latent |= s.col[j] == col;
+    if (latent) continue;  // virtual: codes is never read for it
+    const uint32_t c = codes[(int64_t)col * ld + row];
+    if (c >= (uint32_t)F.card[v]) {  // missing, or not a state
+      bad |= c != PGM_EV_MISSING;
+      ok = false;
+    } else {
+      idx += (int32_t)c * F.stride[v];
+    }
+  }
+  return ok;
+}
+
+// the part of family s.fam[k]'s index that latent configuration d adds
+__device__ inline int32_t em_latent_index(const EmSpec &s, int32_t k, const int32_t (&d)[PGM_EM_MAX_LATENT]) {
+  int32_t e = 0;
+#pragma unroll
+  for (int j = 0; j < PGM_EM_MAX_LATENT; ++j) e += d[j] * s.stride[k][j];  // stride 0 past n_latent
+  return e;
+}
+
+// the next configuration: the last latent fastest
+__device__ inline void em_next(const EmSpec &s, int32_t (&d)[PGM_EM_MAX_LATENT]) {
+  bool carry = true;
+#pragma unroll
+  for (int j = PGM_EM_MAX_LATENT - 1; j >= 0; --j)
+    if (carry && j < s.n_latent) {
+      if (++d[j] == s.card[j]) d[j] = 0;
+      else carry = false;
+    }
+}
+
+__device__ inline double em_floor(double v) { return PGM_EM_FLOOR > v ? PGM_EM_FLOOR : v; }  // Python's max(v, 1e-10)
+
+__global__ __launch_bounds__(kFitBlock) void k_fit_estep(const FitFam *__restrict__ fams,
+                                                         const FitGroup *__restrict__ groups, uint32_t n_groups,
+                                                         const EmSpec s, const double *__restrict__ values,
+                                                         const uint8_t *__restrict__ codes, int64_t ld, int64_t row0,
+                                                         int64_t n_rows, double *__restrict__ tables,
+                                                         double *__restrict__ loglik, int32_t *__restrict__ err) {
+  extern __shared__ unsigned char fit_lds[];
+  double *lds = reinterpret_cast<double *>(fit_lds);
+  int32_t *scratch = reinterpret_cast<int32_t *>(fit_lds + kFitTileBins * sizeof(double));
+  const uint32_t tid = threadIdx.x;
+  const uint32_t gi = blockIdx.x % n_groups;
+  const FitGroup g = groups[gi];
+  const int64_t r_begin = (int64_t)(blockIdx.x / n_groups) * kFitRowsPerBlock;
+  const int64_t r_end = r_begin + kFitRowsPerBlock < n_rows ? r_begin + kFitRowsPerBlock : n_rows;
+  double *out = tables + g.off;
+  if (!g.global) {
+    for (int32_t i = (int32_t)tid; i < g.bins; i += kFitBlock) lds[i] = 0.0;
+    __syncthreads();
+  }
+  // the latent families of this group: s.fam[kb .. ke)
+  int32_t kb = 0;
+  while (kb < s.n_lat_fam && s.fam[kb] < g.fam_begin) ++kb;
+  int32_t ke = kb;
+  while (ke < s.n_lat_fam && s.fam[ke] < g.fam_end) ++ke;
+  const bool want_ll = loglik && gi == 0;
+  // p_l of the row whose observed indices are in the scratch
+  auto weight = [&](const int32_t (&d)[PGM_EM_MAX_LATENT]) {
+    double p = 1.0;
+    for (int32_t k = 0; k < s.n_lat_fam; ++k) {
+      const int32_t e = scratch[k * kFitBlock + (int32_t)tid] + em_latent_index(s, k, d);
+      p *= em_floor(values[fams[s.fam[k]].off + e]);
+    }
+    return p;
+  };
+  bool bad = false;
+  for (int64_t r = r_begin + tid; r < r_end; r += kFitBlock) {
+    const int64_t row = row0 + r;
+    bool ok = true;
+    for (int32_t f = 0, k = 0; f < s.n_fam; ++f) {
+      int32_t idx;
+      ok &= em_observed_index(fams[f], s, codes, ld, row, idx, bad);
+      if (k < s.n_lat_fam && s.fam[k] == f) scratch[k++ * kFitBlock + (int32_t)tid] = idx;
+    }
+    if (!ok) {  // not counted in any table
+      if (want_ll) loglik[row] = 0.0;
+      continue;
+    }
+    double Z = 0.0;
+    {
+      int32_t d[PGM_EM_MAX_LATENT] = {0, 0, 0, 0, 0, 0, 0, 0};
+      for (int32_t l = 0; l < s.n_configs; ++l, em_next(s, d)) Z += weight(d);
+    }
+    if (kb < ke) {
+      int32_t d[PGM_EM_MAX_LATENT] = {0, 0, 0, 0, 0, 0, 0, 0};
+      for (int32_t l = 0; l < s.n_configs; ++l, em_next(s, d)) {
+        const double w = weight(d) / Z;
+        for (int32_t k = kb; k < ke; ++k) {
+          const int32_t e = scratch[k * kFitBlock + (int32_t)tid] + em_latent_index(s, k, d);
+          if (g.global) atomicAdd(&out[e], w);
+          else atomicAdd(&lds[(int32_t)(fams[s.fam[k]].off - g.off) + e], w);
+        }
+      }
+    }
+    double ll = want_ll ? log(Z) : 0.0;
+    for (int32_t f = 0, k = 0; f < s.n_fam; ++f) {
+      if (k < s.n_lat_fam && s.fam[k] == f) {
+        ++k;
+        continue;
+      }
+      const bool mine = f >= g.fam_begin && f < g.fam_end;
+      if (!mine && !want_ll) continue;
+      const FitFam &F = fams[f];
+      int32_t idx;
+      bool unused = false;
+      (void)em_observed_index(F, s, codes, ld, row, idx, unused);  // every code is a state: checked above
+      if (mine) {
+        if (g.global) atomicAdd(&out[idx], 1.0);
+        else atomicAdd(&lds[(int32_t)(F.off - g.off) + idx], 1.0);
+      }
+      if (want_ll) ll += log(em_floor(values[F.off + idx]));
+    }
+    if (want_ll) loglik[row] = ll;
+  }
+  if (bad) atomicOr(err, 1);
+  if (!g.global) {
+    __syncthreads();
+    for (int32_t i = (int32_t)tid; i < g.bins; i += kFitBlock) {
+      const double v = lds[i];
+      if (v != 0.0) atomicAdd(&out[i], v);
     }
   }
 }
@@ -571,6 +725,31 @@ int pgm_fit_count(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, 
   HIP_TRY(hipMemcpyAsync(&bad, err, sizeof bad, hipMemcpyDeviceToHost, S(stream)));
   HIP_TRY(hipStreamSynchronize(S(stream)));
   if (bad) return pgmi_fail(PGM_EINDEX, "fit_count: a state code is >= its variable's cardinality");
+  return PGM_OK;
+}
+
+int pgm_fit_estep(void *plan, const int32_t *latent_cols, int32_t n_latent, const double *values, const uint8_t *codes,
+                  int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, double *tables, double *loglik,
+                  void *stream) {
+  FitHandle *h = static_cast<FitHandle *>(plan);
+  EmSpec spec;
+  int64_t blocks = 0;
+  const int st = fit_estep_check(h, latent_cols, n_latent, values, codes, n_cols, ld, row0, n_rows, tables, &spec, &blocks);
+  if (st != PGM_OK) return st;
+  if (blocks == 0) return PGM_OK;
+  const int up = fit_upload(h);
+  if (up != PGM_OK) return up;
+  int32_t *err = static_cast<int32_t *>(h->d_err);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), S(stream)));
+  hipLaunchKernelGGL(k_fit_estep, dim3((unsigned)blocks), dim3(kFitBlock), (size_t)fit_estep_lds(spec.n_lat_fam), S(stream),
+                     static_cast<const FitFam *>(h->d_fams), static_cast<const FitGroup *>(h->d_groups),
+                     (uint32_t)h->p.groups.size(), spec, values, codes, ld, row0, n_rows, tables, loglik, err);
+  HIP_TRY(hipGetLastError());
+  // PGM_EINDEX is this call's status, as in pgm_fit_count (synchronises the stream)
+  int32_t bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, err, sizeof bad, hipMemcpyDeviceToHost, S(stream)));
+  HIP_TRY(hipStreamSynchronize(S(stream)));
+  if (bad) return pgmi_fail(PGM_EINDEX, "fit_estep: a state code is >= its variable's cardinality");
   return PGM_OK;
 }
 

@@ -152,6 +152,86 @@ int fit_citest_check(const FitHandle *h, const int64_t *counts, double lambda, i
   return PGM_OK;
 }
 
+int fit_estep_spec(const FitHandle *h, const int32_t *latent_cols, int32_t n_latent, const char *what, EmSpec *spec,
+                   int32_t *n_obs_cols) {
+  if (!h) return pgmi_failf(PGM_EINVAL, "%s: null plan", what);
+  if (!latent_cols) return pgmi_failf(PGM_EINVAL, "%s: null latent_cols", what);
+  if (n_latent < 1 || n_latent > PGM_EM_MAX_LATENT)
+    return pgmi_failf(PGM_EINVAL, "%s: %d latent columns (1 .. %d)", what, n_latent, PGM_EM_MAX_LATENT);
+  EmSpec s;
+  memset(&s, 0, sizeof s);
+  s.n_latent = n_latent;
+  s.n_fam = (int32_t)h->p.fams.size();
+  for (int32_t j = 0; j < n_latent; ++j) {
+    if (latent_cols[j] < 0) return pgmi_failf(PGM_EINVAL, "%s: latent column %d", what, latent_cols[j]);
+    for (int32_t i = 0; i < j; ++i)
+      if (latent_cols[i] == latent_cols[j])
+        return pgmi_failf(PGM_EINVAL, "%s: latent column %d is listed twice", what, latent_cols[j]);
+    s.col[j] = latent_cols[j];
+  }
+  int32_t obs_cols = 0;
+  for (int32_t f = 0; f < s.n_fam; ++f) {
+    const FitFam &F = h->p.fams[(size_t)f];
+    int32_t k = -1;  // the family's slot in s.fam once a latent is found in its scope
+    for (int32_t v = 0; v < F.n_vars; ++v) {
+      int32_t j = 0;
+      while (j < n_latent && s.col[j] != F.col[v]) ++j;
+      if (j == n_latent) {
+        if (F.col[v] + 1 > obs_cols) obs_cols = F.col[v] + 1;
+        continue;
+      }
+      if (s.card[j] != 0 && s.card[j] != F.card[v])
+        return pgmi_failf(PGM_EINVAL, "%s: latent column %d has cardinality %d in family %d and %d in an earlier one",
+                          what, s.col[j], F.card[v], f, s.card[j]);
+      s.card[j] = F.card[v];
+      if (k < 0) {
+        if (s.n_lat_fam == PGM_EM_MAX_FAMILIES)
+          return pgmi_failf(PGM_EINVAL, "%s: more than %d families have a latent in scope", what, PGM_EM_MAX_FAMILIES);
+        k = s.n_lat_fam++;
+        s.fam[k] = f;
+      }
+      // a column listed twice in one family adds both strides, as the count kernel adds both codes
+      s.stride[k][j] += F.stride[v];
+    }
+  }
+  int64_t configs = 1;
+  for (int32_t j = 0; j < n_latent; ++j) {
+    if (s.card[j] == 0) return pgmi_failf(PGM_EINVAL, "%s: latent column %d is in no family of the plan", what, s.col[j]);
+    configs *= s.card[j];
+    if (configs > PGM_EM_MAX_CONFIGS)
+      return pgmi_failf(PGM_EINVAL, "%s: more than %d latent configurations", what, PGM_EM_MAX_CONFIGS);
+  }
+  s.n_configs = (int32_t)configs;
+  if (spec) *spec = s;
+  if (n_obs_cols) *n_obs_cols = obs_cols;
+  return PGM_OK;
+}
+
+int fit_estep_check(const FitHandle *h, const int32_t *latent_cols, int32_t n_latent, const double *values,
+                    const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, const double *tables,
+                    EmSpec *spec, int64_t *blocks) {
+  if (!h) return pgmi_fail(PGM_EINVAL, "fit_estep: null plan");
+  if (!values) return pgmi_fail(PGM_EINVAL, "fit_estep: null values");
+  if (!codes) return pgmi_fail(PGM_EINVAL, "fit_estep: null codes");
+  if (!tables) return pgmi_fail(PGM_EINVAL, "fit_estep: null tables");
+  int32_t obs_cols = 0;
+  const int st = fit_estep_spec(h, latent_cols, n_latent, "fit_estep", spec, &obs_cols);
+  if (st != PGM_OK) return st;
+  if (n_rows < 0 || row0 < 0) return pgmi_failf(PGM_EINVAL, "fit_estep: n_rows %lld row0 %lld", (long long)n_rows, (long long)row0);
+  if (ld < n_rows || row0 > ld - n_rows)
+    return pgmi_failf(PGM_EINVAL, "fit_estep: rows [%lld, %lld) outside ld %lld", (long long)row0,
+                      (long long)(row0 + n_rows), (long long)ld);
+  if (n_cols < obs_cols)
+    return pgmi_failf(PGM_EINVAL, "fit_estep: the plan reads the observed column %d, codes has %d columns", obs_cols - 1,
+                      n_cols);
+  const int64_t chunks = (n_rows + kFitRowsPerBlock - 1) / kFitRowsPerBlock;
+  const int64_t nb = chunks * (int64_t)h->p.groups.size();
+  if (nb > INT32_MAX)
+    return pgmi_failf(PGM_EINVAL, "fit_estep: %lld workgroups (count the rows in several calls)", (long long)nb);
+  if (blocks) *blocks = nb;
+  return PGM_OK;
+}
+
 int fit_states_check(const FitHandle *h, const int64_t *counts, const int64_t *n_states) {
   if (!h) return pgmi_fail(PGM_EINVAL, "fit_states_observed: null plan");
   if (!counts) return pgmi_fail(PGM_EINVAL, "fit_states_observed: null counts");
@@ -196,6 +276,22 @@ int pgm_fit_plan_info(void *plan, pgm_fit_info_t *info, int64_t *offsets, int64_
     if (strides) memcpy(strides + f * PGM_MAX_DIMS, p.fams[f].stride, sizeof p.fams[f].stride);
     if (groups) groups[f] = p.group_of[f];
   }
+  return PGM_OK;
+}
+
+int pgm_fit_estep_info(void *plan, const int32_t *latent_cols, int32_t n_latent, pgm_em_info_t *info) {
+  if (!info) return pgmi_fail(PGM_EINVAL, "fit_estep_info: null info");
+  EmSpec s;
+  const int st = fit_estep_spec(static_cast<const FitHandle *>(plan), latent_cols, n_latent, "fit_estep_info", &s, nullptr);
+  if (st != PGM_OK) return st;
+  memset(info, 0, sizeof *info);
+  info->n_latent = s.n_latent;
+  info->n_configs = s.n_configs;
+  info->n_latent_families = s.n_lat_fam;
+  info->n_plain_families = s.n_fam - s.n_lat_fam;
+  info->block = kFitBlock;
+  info->rows_per_block = kFitRowsPerBlock;
+  info->lds_bytes = fit_estep_lds(s.n_lat_fam);
   return PGM_OK;
 }
 }

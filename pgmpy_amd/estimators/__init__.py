@@ -2,14 +2,16 @@
 in two fused HIP launches per model (pgm_fit_count, pgm_fit_finish).  Structure learning: the discrete
 structure scores and HillClimbSearch score all the candidate families of a step in one count launch and
 one score launch (pgm_fit_score); the conditional-independence tests and PC test all the candidate
-separating sets of a level in one count launch and one CI launch per round (pgm_fit_citest).
+separating sets of a level in one count launch and one CI launch per round (pgm_fit_citest).  Latent
+variables: ExpectationMaximization runs one E-step launch (pgm_fit_estep: every row's posterior over the
+latent configurations added straight into fp64 family tables) and one finishing launch per iteration.
 
 Built: BaseEstimator, ParameterEstimator, MaximumLikelihoodEstimator, BayesianEstimator; StructureScore,
 K2, BDeu, BDs, LogLikeliHood, BIC, AIC, get_scoring_method; HillClimbSearch, ExpertKnowledge (required and
 forbidden edges); CITests (chi_square, g_sq, log_likelihood, modified_log_likelihood, power_divergence,
-get_callable_ci_test, CITester) and PC (orig / stable / parallel; a PDAG from pgmpy_amd.base).  Not built:
-ExpectationMaximization, MarginalEstimator / IPF (MaximumLikelihoodEstimator on a JunctionTree), GES, MMHC,
-TreeSearch, ExhaustiveSearch, the Gaussian and conditional-Gaussian scores, the continuous and mixed CI
+get_callable_ci_test, CITester) and PC (orig / stable / parallel; a PDAG from pgmpy_amd.base);
+ExpectationMaximization (every row complete in its observed columns).  Not built: MarginalEstimator / IPF
+(MaximumLikelihoodEstimator on a JunctionTree), GES, MMHC, TreeSearch, ExhaustiveSearch, the Gaussian and conditional-Gaussian scores, the continuous and mixed CI
 tests (pearsonr, gcm, pillai) and independence_match (DESIGN.md).
 """
 from .base import BaseEstimator, ParameterEstimator
@@ -20,7 +22,8 @@ from .HillClimbSearch import ExpertKnowledge, HillClimbSearch
 from . import CITests
 from .CITests import CITester
 from .PC import PC
+from .EM import ExpectationMaximization
 
 __all__ = ["BaseEstimator", "ParameterEstimator", "MaximumLikelihoodEstimator", "BayesianEstimator",
            "StructureScore", "K2", "BDeu", "BDs", "LogLikeliHood", "BIC", "AIC", "get_scoring_method",
-           "HillClimbSearch", "ExpertKnowledge", "CITests", "CITester", "PC"]
+           "HillClimbSearch", "ExpertKnowledge", "CITests", "CITester", "PC", "ExpectationMaximization"]

@@ -75,6 +75,47 @@ class FitPlan:
                                 N.stream_handle()), "fit_count")
         return tables
 
+    @staticmethod
+    def _latent_array(latent_cols):
+        cols = [int(c) for c in latent_cols]
+        return (ctypes.c_int32 * max(len(cols), 1))(*cols), len(cols)
+
+    def estep_info(self, latent_cols):
+        """pgm_em_info_t of an E-step over this plan with the code columns `latent_cols` latent: the number
+        of latent configurations, the family split and the LDS bytes of the launch.  Needs no device."""
+        L = N.load_library()
+        arr, n = self._latent_array(latent_cols)
+        info = N.EmInfo()
+        N.check(L.pgm_fit_estep_info(self._h, arr, n, ctypes.byref(info)), "fit_estep_info")
+        return info
+
+    def estep(self, latent_cols, values, codes, n_rows=None, row0=0, tables=None, want_loglik=False):
+        """The E-step of expectation maximisation (pgm_fit_estep) over the rows [row0, row0 + n_rows) of
+        the device codes [n_cols, ld] (uint8): under the CPD `values` (a flat fp64 device tensor) each row
+        adds its posterior over the configurations of the latent code columns `latent_cols` (virtual:
+        never read) to the fp64 `tables` (a zeroed flat buffer when None) of the families with a latent,
+        and 1.0 to the others.  A row with 255 in an observed column of any family is not counted.
+        Returns the tables, and with want_loglik the fp64 device tensor [ld] of the rows' log-likelihoods
+        beside them.  Raises IndexError when a code is neither 255 nor a state."""
+        import torch
+
+        L = N.lib()
+        if codes.dtype != torch.uint8 or codes.dim() != 2 or not codes.is_contiguous():
+            raise ValueError("codes must be a contiguous [n_cols, ld] uint8 device tensor")
+        n_cols, ld = int(codes.shape[0]), int(codes.shape[1])
+        n_rows = ld - row0 if n_rows is None else int(n_rows)
+        if values.dtype != torch.float64 or values.numel() < self.total_bins or not values.is_contiguous():
+            raise ValueError(f"values must be a contiguous fp64 device tensor of {self.total_bins} entries")
+        if tables is None:
+            tables = torch.zeros(self.total_bins, dtype=torch.float64, device=codes.device)
+        elif tables.dtype != torch.float64 or tables.numel() < self.total_bins or not tables.is_contiguous():
+            raise ValueError(f"tables must be a contiguous torch.float64 device tensor of {self.total_bins} entries")
+        arr, n = self._latent_array(latent_cols)
+        loglik = torch.zeros(ld, dtype=torch.float64, device=codes.device) if want_loglik else None
+        N.check(L.pgm_fit_estep(self._h, arr, n, N.ptr(values), N.ptr(codes), n_cols, ld, int(row0), n_rows,
+                                N.ptr(tables), N.ptr(loglik), N.stream_handle()), "fit_estep")
+        return (tables, loglik) if want_loglik else tables
+
     def finish(self, counts, pseudo=None, bayes=False, out=None):
         """Every CPD's values from the count tables (+ fp64 pseudo-counts of the same layout): each
         column divided by its sum; MLE (bayes=False) fills an all-zero column uniformly, Bayes keeps

@@ -77,6 +77,38 @@ class TabularCPD(DiscreteFactor):
     def get_evidence(self):
         return self.variables[:0:-1]
 
+    @staticmethod
+    def _filled(variable, evidence, cardinality, state_names, fill):
+        # the shared body of get_random / get_uniform (CPD.py:783-817, 867-899)
+        evidence = [] if evidence is None else list(evidence)
+        if cardinality is None:
+            cardinality = {var: 2 for var in [variable] + evidence}
+        else:
+            for var in [variable] + evidence:
+                if var not in cardinality.keys():
+                    raise ValueError(f"Cardinality for variable: {var} not specified.")
+        parent_card = [cardinality[var] for var in evidence]
+        values = fill((cardinality[variable], int(np.prod(parent_card, dtype=np.int64)) if evidence else 1))
+        values = values / np.sum(values, axis=0)
+        if not evidence:
+            return TabularCPD(variable, cardinality[variable], values, state_names=state_names)
+        return TabularCPD(variable, cardinality[variable], values, evidence=evidence, evidence_card=parent_card,
+                          state_names=state_names)
+
+    @staticmethod
+    def get_random(variable, evidence=None, cardinality=None, state_names={}, seed=None):
+        """A CPD of `variable` given `evidence` with random values (CPD.py:737-817): cardinality 2 for
+        every variable when `cardinality` is None; the values are np.random.default_rng(seed).random of
+        the reference's shape, column-normalised, so a seed gives the reference's values."""
+        generator = np.random.default_rng(seed=seed)
+        return TabularCPD._filled(variable, evidence, cardinality, state_names, generator.random)
+
+    @staticmethod
+    def get_uniform(variable, evidence=None, cardinality=None, state_names={}, seed=None):
+        """A CPD of `variable` given `evidence` with every column uniform (CPD.py:819-899); `seed` is
+        accepted and unused, as in the reference."""
+        return TabularCPD._filled(variable, evidence, cardinality, state_names, np.ones)
+
     def copy(self):
         evidence = self.variables[1:] if len(self.variables) > 1 else None
         evidence_card = self.cardinality[1:] if len(self.variables) > 1 else None
