@@ -365,6 +365,20 @@ int pgm_batch_add_gather(void *handle, const pgm_gather_desc *d, const double *A
 int pgm_batch_add_product_n(void *handle, const pgm_productn_desc *d, const double *const *ops, double *C);
 /* r06: an n-ary contraction job (pgm_contractn_desc; ops: a HOST array of n_ops device pointers). */
 int pgm_batch_add_contract_n(void *batch, const pgm_contractn_desc *d, const double *const *ops, double *C);
+/* What pgm_batch_add_contract_n plans for this descriptor, without adding a job: the kept / reduced dims
+ * after unit dims are dropped and adjacent dims merged, the lanes per output, and the 256-thread blocks the
+ * job takes in a PGM_BATCH_GRID batch.  Host-only (no HIP call, no device needed; ops is not read and may
+ * be NULL: the plan depends on cardinalities and strides alone).  The batch entry point plans with the same
+ * function, so what is reported is what runs.  An empty output reports n_out = 0 and blocks = 0. */
+typedef struct {
+  int32_t nk, nr;                /* kept / reduced dims after merging (at most 12 each) */
+  int32_t g_log2;                /* log2 of the lanes per output */
+  uint32_t blocks;               /* 256-thread blocks of the job in a grid batch */
+  uint32_t n_out, n_red;         /* outputs, reduction entries per output */
+  uint32_t kcard[PGM_MAX_DIMS];  /* merged kept extents, the last fastest */
+  uint32_t rcard[PGM_MAX_DIMS];  /* merged reduced extents */
+} pgm_contractn_info_t;
+int pgm_contract_n_info(const pgm_contractn_desc *d, const double *const *ops, pgm_contractn_info_t *info);
 /* a findings-indicator job (pgm_indicator's arguments): all of a BP sweep's findings in one launch */
 int pgm_batch_add_indicator(void *handle, const uint8_t *codes, int64_t n_rows, int64_t card, double *out,
                             int64_t s_state, int64_t s_row, int32_t *err_flag);

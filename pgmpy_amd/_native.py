@@ -120,6 +120,20 @@ class ContractNDesc(ctypes.Structure):
     ]
 
 
+class ContractNInfo(ctypes.Structure):
+    """pgm_contractn_info_t: the plan pgm_batch_add_contract_n makes for a descriptor (host-only query)."""
+    _fields_ = [
+        ("nk", ctypes.c_int32),
+        ("nr", ctypes.c_int32),
+        ("g_log2", ctypes.c_int32),
+        ("blocks", ctypes.c_uint32),
+        ("n_out", ctypes.c_uint32),
+        ("n_red", ctypes.c_uint32),
+        ("kcard", ctypes.c_uint32 * PGM_MAX_DIMS),
+        ("rcard", ctypes.c_uint32 * PGM_MAX_DIMS),
+    ]
+
+
 class GemmDesc(ctypes.Structure):
     _fields_ = [("batch", ctypes.c_int64), ("m", ctypes.c_int64), ("n", ctypes.c_int64), ("k", ctypes.c_int64),
                 ("offsets", ctypes.c_void_p), ("stride", ctypes.c_int64 * 9), ("lane_order", ctypes.c_int32),
@@ -294,6 +308,7 @@ _SIGS = {
     "pgm_batch_add_contract": ([_P, ctypes.POINTER(ContractDesc), _P, _P, _P], ctypes.c_int),
     "pgm_batch_add_gather": ([_P, ctypes.POINTER(GatherDesc), _P, _P, _P, _P], ctypes.c_int),
     "pgm_batch_add_product_n": ([_P, ctypes.POINTER(ProductNDesc), ctypes.POINTER(_P), _P], ctypes.c_int),
+    "pgm_contract_n_info": ([ctypes.POINTER(ContractNDesc), ctypes.POINTER(_P), ctypes.POINTER(ContractNInfo)], ctypes.c_int),
     "pgm_batch_add_contract_n": ([_P, ctypes.POINTER(ContractNDesc), ctypes.POINTER(_P), _P], ctypes.c_int),
     "pgm_batch_add_indicator": ([_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P],
                                 ctypes.c_int),

@@ -2415,9 +2415,14 @@ int pgm_batch_create(void **handle) {
   return *handle ? PGM_OK : fail(PGM_ENOMEM, "batch_create: host allocation");
 }
 
+// 256-thread blocks a batch job of `threads` lanes takes (cap 0: kBatchMaxBlocks; its lanes grid-stride beyond)
+static uint64_t batch_job_blocks(uint64_t threads, uint64_t cap = 0) {
+  return std::min<uint64_t>(std::max<uint64_t>((threads + 255) / 256, 1), cap ? cap : kBatchMaxBlocks);
+}
+
 static int batch_append(BatchHandle *h, BatchJob &J, uint64_t threads, uint64_t cap = 0) {
   if (h->d_jobs) return fail(PGM_EINVAL, "batch: already finalized");
-  const uint64_t nb = std::min<uint64_t>(std::max<uint64_t>((threads + 255) / 256, 1), cap ? cap : kBatchMaxBlocks);
+  const uint64_t nb = batch_job_blocks(threads, cap);
   if (h->block_job.size() + nb > 0x7fffffffull) return fail(PGM_EINVAL, "batch: too many blocks");
   J.block0 = (uint32_t)h->block_job.size();
   J.nblocks = (uint32_t)nb;
@@ -2519,14 +2524,14 @@ int pgm_batch_add_product_n(void *handle, const pgm_productn_desc *d, const doub
 
 // an n-ary contraction's plan: unit dims dropped, adjacent dims merged where every operand (and C, for
 // kept dims) steps through them as one, G lanes per output for long reductions of few outputs
-static int plan_contract_n(const pgm_contractn_desc *d, const double *const *ops, ContractNK &k) {
-  if (!d || !ops) return fail(PGM_EINVAL, "contract_n: null argument");
+static int plan_contract_n(const pgm_contractn_desc *d, const double *const *ops, ContractNK &k, bool need_ops = true) {
+  if (!d || (need_ops && !ops)) return fail(PGM_EINVAL, "contract_n: null argument");
   const int n = d->n_ops;
   if (n < 1 || n > MOPS) return fail(PGM_EINVAL, "contract_n: %d operands (1..%d)", n, MOPS);
   if (d->reduce != PGM_RED_SUM && d->reduce != PGM_RED_MAX) return fail(PGM_EINVAL, "contract_n: reduce must be sum or max");
   if (d->n_keep < 0 || d->n_keep > PGM_MAX_DIMS || d->n_red < 0 || d->n_red > PGM_MAX_DIMS)
     return fail(PGM_EINVAL, "contract_n: %d kept / %d reduced dims", d->n_keep, d->n_red);
-  for (int t = 0; t < n; ++t)
+  for (int t = 0; need_ops && t < n; ++t)
     if (!ops[t]) return fail(PGM_EINVAL, "contract_n: operand %d is null", t);
   memset(&k, 0, sizeof k);
   k.n_ops = n;
@@ -2601,6 +2606,10 @@ static int plan_contract_n(const pgm_contractn_desc *d, const double *const *ops
   return PGM_OK;
 }
 
+// an n-ary job's lanes and block cap in a batch (pgm_batch_add_contract_n and pgm_contract_n_info)
+static uint64_t contract_n_threads(const ContractNK &k) { return (uint64_t)k.n_out << k.g_log2; }
+static uint64_t contract_n_cap(const ContractNK &k) { return k.nr == 0 ? kBatchMaxBlocksProduct : 0; }
+
 int pgm_batch_add_contract_n(void *handle, const pgm_contractn_desc *d, const double *const *ops, double *C) {
   STALE_PROBE();
   BatchHandle *h = (BatchHandle *)handle;
@@ -2615,10 +2624,27 @@ int pgm_batch_add_contract_n(void *handle, const pgm_contractn_desc *d, const do
   J.red = k.red;
   J.C = C;
   J._pad = (int32_t)h->njobs.size();
-  rc = batch_append(h, J, (uint64_t)k.n_out << k.g_log2, k.nr == 0 ? kBatchMaxBlocksProduct : 0);
+  rc = batch_append(h, J, contract_n_threads(k), contract_n_cap(k));
   if (rc != PGM_OK) return rc;
   h->njobs.push_back(k);
   h->nops.emplace_back(ops, ops + k.n_ops);
+  return PGM_OK;
+}
+
+int pgm_contract_n_info(const pgm_contractn_desc *d, const double *const *ops, pgm_contractn_info_t *info) {
+  if (!info) return fail(PGM_EINVAL, "contract_n_info: null pointer");
+  ContractNK k;
+  int rc = plan_contract_n(d, ops, k, false);
+  if (rc != PGM_OK) return rc;
+  memset(info, 0, sizeof *info);
+  info->nk = k.nk;
+  info->nr = k.nr;
+  info->g_log2 = k.g_log2;
+  info->n_out = k.n_out;
+  info->n_red = k.n_red;
+  for (int i = 0; i < k.nk; ++i) info->kcard[i] = k.kcard[i];
+  for (int i = 0; i < k.nr; ++i) info->rcard[i] = k.rcard[i];
+  info->blocks = k.n_out ? (uint32_t)batch_job_blocks(contract_n_threads(k), contract_n_cap(k)) : 0;
   return PGM_OK;
 }
 

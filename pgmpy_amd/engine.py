@@ -551,20 +551,19 @@ def prepare_product_n(operands, out_labels, out=None, kinds=None):
     return d, ptrs, out
 
 
-def prepare_contract_n(operands, out_labels, reduce="sum", out=None):
-    """(descriptor, operand pointers, out) for C[out_labels] = REDUCE over the other labels of
-    prod_i X_i (pgm_contractn_desc, r06): several pairwise steps of a contraction path as one batch job.
-    operands: (device fp64 tensor, labels) pairs, up to PRODN_MAX_OPS."""
-    N.lib()
+def contract_n_desc(operands, out_labels, reduce="sum", out_stride=None):
+    """(descriptor, output shape) of C[out_labels] = REDUCE over the other labels of prod_i X_i from shapes
+    and element strides alone: no allocation, no library call.  operands: (shape, strides, labels) triples, up
+    to PRODN_MAX_OPS.  out_stride None: a C-order output."""
     out_labels = list(out_labels)
     if not 1 <= len(operands) <= N.PRODN_MAX_OPS:
         raise ValueError(f"contract_n takes 1..{N.PRODN_MAX_OPS} operands")
     card = {}
-    for t, ls in operands:
-        if len(ls) != t.dim():
+    for shape, strides, ls in operands:
+        if len(ls) != len(shape) or len(strides) != len(shape):
             raise ValueError("label count does not match tensor rank")
         for dd, l in enumerate(ls):
-            c = int(t.shape[dd])
+            c = int(shape[dd])
             if card.setdefault(l, c) != c:
                 raise ValueError(f"cardinality mismatch for {l!r}")
     for l in out_labels:
@@ -573,28 +572,59 @@ def prepare_contract_n(operands, out_labels, reduce="sum", out=None):
     red = [l for l in card if l not in out_labels]
     if len(out_labels) > N.PGM_MAX_DIMS or len(red) > N.PGM_MAX_DIMS:
         raise ValueError("too many dimensions")
-    if out is None:
-        out = empty([card[l] for l in out_labels])
+    out_shape = [card[l] for l in out_labels]
+    if out_stride is None:
+        out_stride = c_order_strides(out_shape)
+    elif len(out_stride) != len(out_labels):
+        raise ValueError("out has the wrong shape")
     d = N.ContractNDesc()
     d.n_ops = len(operands)
     d.reduce = _REDUCE[reduce]
     d.n_keep = len(out_labels)
     d.n_red = len(red)
 
-    def st(t, ls, l):
-        return int(t.stride(list(ls).index(l))) if l in ls else 0
+    def st(strides, ls, l):
+        return int(strides[list(ls).index(l)]) if l in ls else 0
 
     for i, l in enumerate(out_labels):
         d.keep_card[i] = card[l]
-        d.keep_sc[i] = int(out.stride(i))
-        for j, (t, ls) in enumerate(operands):
-            d.keep_s[j][i] = st(t, ls, l)
+        d.keep_sc[i] = int(out_stride[i])
+        for j, (_, strides, ls) in enumerate(operands):
+            d.keep_s[j][i] = st(strides, ls, l)
     for i, l in enumerate(red):
         d.red_card[i] = card[l]
-        for j, (t, ls) in enumerate(operands):
-            d.red_s[j][i] = st(t, ls, l)
+        for j, (_, strides, ls) in enumerate(operands):
+            d.red_s[j][i] = st(strides, ls, l)
+    return d, out_shape
+
+
+def prepare_contract_n(operands, out_labels, reduce="sum", out=None):
+    """(descriptor, operand pointers, out) for C[out_labels] = REDUCE over the other labels of
+    prod_i X_i (pgm_contractn_desc, r06): several pairwise steps of a contraction path as one batch job.
+    operands: (device fp64 tensor, labels) pairs, up to PRODN_MAX_OPS."""
+    N.lib()
+    for t, ls in operands:
+        if len(ls) != t.dim():
+            raise ValueError("label count does not match tensor rank")
+    d, out_shape = contract_n_desc([(t.shape, t.stride(), ls) for t, ls in operands], out_labels, reduce,
+                                   None if out is None else out.stride())
+    if out is None:
+        out = empty(out_shape)
+    elif tuple(out.shape) != tuple(out_shape):
+        raise ValueError("out has the wrong shape")
     ptrs = (ctypes.c_void_p * len(operands))(*[t.data_ptr() for t, _ in operands])
     return d, ptrs, out
+
+
+def contract_n_info(operands, out_labels, reduce="sum", out=None):
+    """The plan a contract_n job of these (tensor, labels) operands gets (N.ContractNInfo; pgm_contract_n_info:
+    no device needed, only shapes and strides are read, so host tensors do).  out None: the C-order output the
+    engine allocates."""
+    d, _ = contract_n_desc([(t.shape, t.stride(), ls) for t, ls in operands], out_labels, reduce,
+                           None if out is None else out.stride())
+    info = N.ContractNInfo()
+    N.check(N.load_library().pgm_contract_n_info(ctypes.byref(d), None, ctypes.byref(info)), "contract_n_info")
+    return info
 
 
 def product_n(operands, out_labels, out=None, kinds=None):
