@@ -922,6 +922,79 @@ int pgm_sample_forward(void *plan, const double *values, const double *cdf, cons
                        int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, int64_t first_row, uint64_t seed,
                        double *weights, const double *uniforms, void *stream);
 
+/* ---------------------------------------------------------------- Gibbs sampling
+ * GibbsSampling (sampling/Sampling.py:409-631) on the device: many chains per launch, one per lane, in
+ * the column-major uint8 codes that pgm_fit_count and the fused row plan read.  An extension of ABI 25.
+ *
+ * A plan is built from factors: pgm_fit_family records (columns, cardinalities) in the C order of the
+ * factor's table.  A CPD is the factor [node, parents...]; a Markov network's factor is given as it
+ * stands.  values share the fit plan's flat layout: factor f at [offsets[f], offsets[f] + sizes[f]).
+ * PGM_EINVAL unless every column 0 .. n_cols - 1 occurs in a factor, a column has the cardinality card[]
+ * gives wherever it occurs, cardinalities are <= 254, a factor has at most PGM_MAX_DIMS columns, fewer
+ * than 2^31 entries and lists no column twice.  The plan holds, per column, its incident factors
+ * (factor, position of the column in it) in CSR form, factors ascending, of any degree.
+ *
+ * pgm_gibbs_sweep advances the chains in rows [row0, row0 + n_chains) of codes[col * ld + row] in place:
+ * chains [first_chain, first_chain + n_chains) of the stream of `seed`, through sweeps first_sweep ..
+ * first_sweep + n_sweeps - 1 (1 <= sweep < 2^32).  A sweep visits the columns in ascending order; a column
+ * with clamp[col] != 0 (host, one uint8 per column, NULL: none) keeps its code.  For any other column of
+ * cardinality K, w_s (s = 0 .. K - 1) is the product of values[off_f + base_f + s * stride_f] over the
+ * incident factors in list order, starting from the first factor's value, base_f from the chain's
+ * current codes of the factor's other columns; c_0 = w_0, c_s = c_{s-1} + w_s, t = u * c_{K-1}; the new
+ * code is min{s : c_s > t}, or min{s : c_s == c_{K-1}} if there is none (pgm_sample_forward's rule).
+ * Every multiplication and addition is one separately rounded fp64 operation (no FMA).  u is the
+ * forward sampler's generator with the sweep as the fourth counter word: Philox4x32-10, counter
+ * (chain & 0xffffffff, chain >> 32, col >> 1, sweep); sweep 0 is pgm_sample_forward's stream.  So a
+ * result depends on (seed, chain, sweep, column) only: not on the kernel path, row0, or how the sweeps
+ * are split over calls.
+ *
+ * A conditional whose total is not finite or not > 0 cannot be drawn (the state has probability 0): the
+ * variable keeps its code, the walk goes on and the call returns PGM_EINVAL.  A chain that holds a code
+ * >= its column's cardinality in any column is not advanced and nothing is indexed with that code: the
+ * call returns PGM_EINDEX.  Both are device flags read back after the launch: the call synchronises the
+ * stream.
+ *
+ * trace (optional, uint8 [n_cols, ld_trace]): after local sweep j = 1 .. n_sweeps with j % thin == 0 the
+ * state of the chain in row row0 + r goes to trace[col * ld_trace + (j / thin - 1) * n_chains + r]; codes
+ * always receives the final state.  uniforms (optional, fp64 [n_sweeps, n_cols, ld], values in [0, 1))
+ * replace the generator: the test hook for the boundaries of the running sums.
+ *
+ * pgm_gibbs_start writes a start state for models that cannot be forward-sampled: column c of chain r is
+ * min(floor(u * card[c]), card[c] - 1) with the sweep-0 uniform of (seed, first_chain + r, c).
+ *
+ * Every argument is checked on the host before any HIP call; pgm_gibbs_plan_create and
+ * pgm_gibbs_plan_info need no device. */
+#define PGM_GIBBS_LDS 0    /* the chains' codes live in LDS for the whole launch */
+#define PGM_GIBBS_GLOBAL 1 /* the state stays in the code matrix */
+typedef struct {
+  int32_t n_factors;
+  int32_t n_cols;
+  int64_t total_entries;     /* entries of the values buffer */
+  int64_t total_incidences;  /* (column, incident factor) pairs */
+  int64_t blocks;            /* workgroups of a launch with n_chains chains */
+  int32_t max_degree;        /* most factors incident to one column */
+  int32_t max_card;
+  int32_t path;              /* PGM_GIBBS_LDS / PGM_GIBBS_GLOBAL */
+  int32_t block;             /* work-items = chains per workgroup */
+  int32_t lds_bytes;         /* dynamic LDS of the launch: n_cols * block on the LDS path, else 0 */
+  int32_t lds_budget;        /* the LDS path is taken while n_cols * block <= lds_budget */
+  int32_t reg_card;          /* cardinalities up to this keep a conditional's weights in registers */
+  int32_t reserved;
+} pgm_gibbs_info_t;
+int pgm_gibbs_plan_create(const pgm_fit_family *factors, int32_t n_factors, const int32_t *card, int32_t n_cols,
+                          void **plan);
+int pgm_gibbs_plan_destroy(void *plan);
+/* layout and the launch a call with n_chains chains makes; offsets / sizes: n_factors entries; inc_off:
+ * n_cols + 1 entries; inc: 2 * total_incidences entries (factor, position); any output may be NULL */
+int pgm_gibbs_plan_info(void *plan, int64_t n_chains, pgm_gibbs_info_t *info, int64_t *offsets, int64_t *sizes,
+                        int32_t *inc_off, int32_t *inc);
+int pgm_gibbs_start(void *plan, uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_chains,
+                    int64_t first_chain, uint64_t seed, void *stream);
+int pgm_gibbs_sweep(void *plan, const double *values, uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0,
+                    int64_t n_chains, int64_t first_chain, int64_t first_sweep, int64_t n_sweeps, uint64_t seed,
+                    const uint8_t *clamp, uint8_t *trace, int64_t ld_trace, int64_t thin, const double *uniforms,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,18 @@ class SampleInfo(ctypes.Structure):
 
 SAMPLE_FREE, SAMPLE_GIVEN, SAMPLE_OBSERVED = 0, 1, 2
 
+
+class GibbsInfo(ctypes.Structure):
+    """pgm_gibbs_info_t: layout, launch geometry and kernel path of a pgm_gibbs plan (host-only query)."""
+    _fields_ = [("n_factors", ctypes.c_int32), ("n_cols", ctypes.c_int32), ("total_entries", ctypes.c_int64),
+                ("total_incidences", ctypes.c_int64), ("blocks", ctypes.c_int64), ("max_degree", ctypes.c_int32),
+                ("max_card", ctypes.c_int32), ("path", ctypes.c_int32), ("block", ctypes.c_int32),
+                ("lds_bytes", ctypes.c_int32), ("lds_budget", ctypes.c_int32), ("reg_card", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+GIBBS_LDS, GIBBS_GLOBAL = 0, 1  # PGM_GIBBS_*
+
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
 RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
@@ -412,6 +424,17 @@ _SIGS = {
     "pgm_sample_cdf": ([_P, _P, _P, _P], ctypes.c_int),
     "pgm_sample_forward": ([_P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                             ctypes.c_int64, ctypes.c_uint64, _P, _P, _P], ctypes.c_int),
+    "pgm_gibbs_plan_create": ([ctypes.POINTER(FitFamily), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                               ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_gibbs_plan_destroy": ([_P], ctypes.c_int),
+    "pgm_gibbs_plan_info": ([_P, ctypes.c_int64, ctypes.POINTER(GibbsInfo), ctypes.POINTER(ctypes.c_int64),
+                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32),
+                             ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "pgm_gibbs_start": ([_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                         ctypes.c_uint64, _P], ctypes.c_int),
+    "pgm_gibbs_sweep": ([_P, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                         ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, _P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P],
+                        ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -21,6 +21,8 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmfit_plan.cpp",   # parameter learning: family validation, table layout, argument checks (host only)
     "pgmsample.hip",     # forward sampling: running-sum + sampling kernels, their C-ABI
     "pgmsample_plan.cpp",  # forward sampling: family validation, argument checks, host-only queries (host only)
+    "pgmgibbs.hip",      # Gibbs sampling: the fused sweep kernel, its C-ABI
+    "pgmgibbs_plan.cpp",  # Gibbs sampling: factor validation, incidence lists, argument checks (host only)
     "pgmdq.cpp",         # direct AQL dispatch (host code, HSA runtime)
     "pgmpm.cpp",         # plan-specialised batched-BP steps (host code, hipRTC)
     "pgmhost.cpp",       # DataFrame ingestion helpers (host threads only)

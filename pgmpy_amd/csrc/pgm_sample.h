@@ -42,6 +42,16 @@ PGM_HD double sample_uniform(uint64_t seed, uint64_t row, uint32_t col) {
   return (double)(((uint64_t)hi << 21) | (lo >> 11)) * 0x1.0p-53;
 }
 
+// the same stream with one more coordinate, for samplers that revisit a column (Gibbs): the fourth counter
+// word is the sweep, 1 <= sweep < 2^32.  Sweep 0 is sample_uniform's stream by construction, so the state
+// "after sweep 0" is the forward-sampled state of the same seed and no uniform is used twice.
+PGM_HD double sample_uniform3(uint64_t seed, uint64_t chain, uint32_t col, uint32_t sweep) {
+  uint32_t x[4];
+  philox4x32_10((uint32_t)chain, (uint32_t)(chain >> 32), col >> 1, sweep, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+  const uint32_t hi = col & 1u ? x[2] : x[0], lo = col & 1u ? x[3] : x[1];
+  return (double)(((uint64_t)hi << 21) | (lo >> 11)) * 0x1.0p-53;
+}
+
 // ---------------------------------------------------------------------------- the plan
 // the families of a fit plan (same descriptors, same flat table layout) given in a topological order
 struct PGM_FIT_LOCAL SamplePlan {

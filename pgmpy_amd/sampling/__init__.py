@@ -280,3 +280,6 @@ class BayesianModelSampling:
             nodes = compiled(self.model).nodes
             out = np.empty((len(nodes), 0), dtype=np.uint8)
         return self._frame(out, nodes, include_latents)
+
+
+from .gibbs import GibbsSampling  # noqa: E402  (it builds on the names above)
