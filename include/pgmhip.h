@@ -718,7 +718,16 @@ int pgm_dq_profiling(void *dq, int32_t on);
  * PGM_FIT_BAYES: no fill, 0/0 stays NaN.  | PGM_FIT_WEIGHTED: counts are the fp64 tables.
  *
  * Every argument is checked on the host before any HIP call; pgm_fit_plan_create and pgm_fit_plan_info
- * need no device (the descriptors are uploaded by the first count / finish). */
+ * need no device (the descriptors are uploaded by the first count / finish).
+ *
+ * Plan handles (pgm_fit_plan_*, pgm_sample_plan_*, pgm_gibbs_plan_*; this section and the five after it).
+ * Calls on one plan handle must not overlap, on any streams or threads: the device flag word a call reads
+ * back, the staging buffer of its modes / clamp and the chunk partials of a score or CI launch belong to
+ * the handle, not to the call.  Distinct plans are independent.  A plan follows the current device: its
+ * descriptors are uploaded on first use on the device that is current at the call, and when a later call
+ * finds another device current they are released there and uploaded again (what only the score or the CI
+ * launches need is allocated by the first such call on that device).  pgm_*_plan_destroy frees all of it
+ * and accepts NULL. */
 #define PGM_FIT_MLE 0
 #define PGM_FIT_BAYES 1
 #define PGM_FIT_WEIGHTED 2
@@ -765,8 +774,8 @@ int pgm_fit_finish(void *plan, const void *counts, const double *pseudo, int32_t
  * workgroup sums a chunk in a fixed order (a work-item its column's terms in state order, then a
  * fixed-shape tree), a second launch sums each family's chunk partials in a fixed order.  No
  * floating-point atomics: a family's score is bit-identical from run to run and does not depend on
- * which other families share the plan.  The chunk partials live in the plan: calls on one plan must
- * not overlap on different streams.  Every argument is checked on the host before any HIP call. */
+ * which other families share the plan.  The chunk partials live in the plan (plan handles, above).
+ * Every argument is checked on the host before any HIP call. */
 #define PGM_SCORE_BD 0
 #define PGM_SCORE_LL 1
 #define PGM_SCORE_SKIP_EMPTY 2
@@ -801,8 +810,8 @@ int pgm_fit_states_observed(void *plan, const int64_t *counts, int64_t *n_states
  * A family's strata are cut into chunks of PGM_CI_CHUNK counted from its own stratum 0; a chunk is summed
  * in a fixed order and a second launch adds a family's chunk partials in index order.  No floating-point
  * atomics: a family's three outputs are bit-identical from run to run and do not depend on which other
- * families share the plan.  The chunk partials live in the plan: calls on one plan must not overlap on
- * different streams.  Every argument is checked on the host before any HIP call: PGM_EINVAL for a null
+ * families share the plan.  The chunk partials live in the plan (plan handles, above).  Every argument is
+ * checked on the host before any HIP call: PGM_EINVAL for a null
  * plan / counts / stat / dof / pvalue, a non-finite lambda, unknown flag bits, or a family with fewer
  * than two variables. */
 #define PGM_CI_YATES 1

@@ -1,11 +1,15 @@
 // pgm_fit.h — private interface between the two units of parameter learning: pgmfit_plan.cpp (host only:
 // family validation, table layout, grouping of families per workgroup, the argument checks of the
 // pgm_fit_* entry points) and pgmfit.hip (the counting and finishing kernels, the device side of the
-// handle, the launches).  Not part of include/pgmhip.h.
+// handle, the launches); at the end, the host checks the sampling units share with it.  Not part of
+// include/pgmhip.h.
 #pragma once
 #include <cstdint>
+#include <new>
 #include <vector>
 
+#include "pgm_internal.h"
+#include "pgm_plan_dev.h"
 #include "pgmhip.h"
 
 // internal to the library: not in its dynamic symbol table
@@ -66,15 +70,23 @@ struct PGM_FIT_LOCAL FitPlan {
   int n_cols = 0;  // 1 + the largest code column read
 };
 
-// the handle behind pgm_fit_plan_create: the plan plus its lazily uploaded device copy (pgmfit.hip)
+// the handle behind pgm_fit_plan_create: the plan plus its lazily uploaded device copy (dev owns what the
+// d_* point to and sets them: pgmfit.hip fit_use)
 struct PGM_FIT_LOCAL FitHandle {
   FitPlan p;
-  int device = -1;  // the device the copies below live on (-1: not uploaded)
-  void *d_fams = nullptr, *d_groups = nullptr, *d_col_off = nullptr, *d_err = nullptr;
-  // the score launches: chunk_off, and one fp64 partial + one int64 observed-column count per chunk
-  void *d_chunk_off = nullptr, *d_part = nullptr, *d_part_obs = nullptr;
-  // the CI launches: the three work lists, and one fp64 statistic + one int64 dof per chunk
-  void *d_ci_off = nullptr, *d_ci_multi_off = nullptr, *d_ci_single = nullptr, *d_ci_part = nullptr, *d_ci_dof = nullptr;
+  pgmdev::PlanDev dev;
+  const FitFam *d_fams = nullptr;
+  const FitGroup *d_groups = nullptr;
+  const int64_t *d_col_off = nullptr;
+  // the score stage: chunk_off, and one fp64 partial + one int64 observed-column count per chunk
+  const int64_t *d_chunk_off = nullptr;
+  double *d_part = nullptr;
+  int64_t *d_part_obs = nullptr;
+  // the CI stage: the three work lists, and one fp64 statistic + one int64 dof per chunk
+  const int64_t *d_ci_off = nullptr, *d_ci_multi_off = nullptr;
+  const int32_t *d_ci_single = nullptr;
+  double *d_ci_part = nullptr;
+  int64_t *d_ci_dof = nullptr;
 };
 
 // validate the families and lay the tables out; PGM_OK, or PGM_EINVAL with pgm_last_error set
@@ -82,9 +94,6 @@ PGM_FIT_LOCAL int fit_plan_build(const pgm_fit_family *fams, int32_t n, FitPlan 
 // the argument checks of pgm_fit_count / pgm_fit_finish (no HIP call); *blocks: workgroups of the launch
 PGM_FIT_LOCAL int fit_count_check(const FitHandle *h, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0,
                                   int64_t n_rows, const void *tables, int64_t *blocks);
-// whether a count launch takes the four-rows-per-lane kernel: a lane's dword load of 4 codes must be aligned
-// in every column (codes, ld and row0 multiples of 4); else the one-row kernel runs
-PGM_FIT_LOCAL bool fit_count_vec4(const uint8_t *codes, int64_t ld, int64_t row0);
 PGM_FIT_LOCAL int fit_finish_check(const FitHandle *h, const void *counts, int32_t mode, const double *values);
 // the argument checks of pgm_fit_score (no HIP call); *blocks: workgroups of the chunk launch
 PGM_FIT_LOCAL int fit_score_check(const FitHandle *h, const int64_t *counts, int32_t mode, const double *alpha,
@@ -114,3 +123,30 @@ PGM_FIT_LOCAL int fit_estep_check(const FitHandle *h, const int32_t *latent_cols
                                   const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
                                   const double *tables, EmSpec *spec, int64_t *blocks);
 PGM_FIT_LOCAL int fit_states_check(const FitHandle *h, const int64_t *counts, const int64_t *n_states);
+
+// ---------------------------------------------------------------------------- shared with the other plan units
+// (pgmsample_plan.cpp, pgmgibbs_plan.cpp and their .hip units; defined in pgmfit_plan.cpp, which they link)
+// whether a launch over a code window takes the four-rows-per-lane kernel: a lane's dword of 4 codes must be
+// aligned in every column (codes, ld and row0 multiples of 4); else the one-row kernel runs
+PGM_FIT_LOCAL bool codes_vec4(const void *codes, int64_t ld, int64_t row0);
+// The window [row0, row0 + n) of a code matrix with ld rows per column, and the stream range [first,
+// first + n) it stands for (0 for an entry point without a stream).  what: the entry point's name; noun:
+// what it calls a row ("rows", "chains").
+PGM_FIT_LOCAL int window_check(const char *what, const char *noun, int64_t ld, int64_t row0, int64_t n, int64_t first);
+// the body of a pgm_*_plan_create: a new handle H filled by build(h->p); what: the entry point's name
+template <class H, class Build>
+int plan_create(const char *what, void **plan, Build build) {
+  if (!plan) return pgmi_failf(PGM_EINVAL, "%s: null plan", what);
+  *plan = nullptr;
+  H *h = new (std::nothrow) H();
+  if (!h) return pgmi_failf(PGM_ENOMEM, "%s: out of memory", what);
+  const int st = build(h->p);
+  if (st != PGM_OK) {
+    delete h;
+    return st;
+  }
+  *plan = h;
+  return PGM_OK;
+}
+// the per-family offsets / sizes of a pgm_*_plan_info (either may be NULL)
+PGM_FIT_LOCAL void plan_info_layout(const FitPlan &p, int64_t *offsets, int64_t *sizes);

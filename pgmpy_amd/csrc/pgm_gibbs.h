@@ -45,12 +45,15 @@ struct PGM_FIT_LOCAL GibbsPlan {
   int32_t max_degree = 0, max_card = 0;
 };
 
-// the handle behind pgm_gibbs_plan_create: the plan plus its lazily uploaded device copy (pgmgibbs.hip)
+// the handle behind pgm_gibbs_plan_create: the plan plus its lazily uploaded device copy (dev owns what
+// the d_* point to and sets them: pgmgibbs.hip gibbs_use)
 struct PGM_FIT_LOCAL GibbsHandle {
   GibbsPlan p;
-  int device = -1;  // the device the copies below live on (-1: not uploaded)
-  void *d_card = nullptr, *d_inc_off = nullptr, *d_inc = nullptr, *d_others = nullptr, *d_clamp = nullptr,
-       *d_err = nullptr;
+  pgmdev::PlanDev dev;
+  const int32_t *d_card = nullptr, *d_inc_off = nullptr;
+  const GibbsInc *d_inc = nullptr;
+  const GibbsOther *d_others = nullptr;
+  uint8_t *d_clamp = nullptr;  // the staging buffer of a call's clamp: one byte per column
 };
 
 // validate the factors and build the incidence lists; PGM_OK, or PGM_EINVAL with pgm_last_error set

@@ -34,23 +34,17 @@ PGM_HD void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, ui
   x[0] = c0, x[1] = c1, x[2] = c2, x[3] = c3;
 }
 
-// the uniform of stream row `row` and code column `col`: 53 bits in [0, 1); columns 2k and 2k + 1 share a call
-PGM_HD double sample_uniform(uint64_t seed, uint64_t row, uint32_t col) {
-  uint32_t x[4];
-  philox4x32_10((uint32_t)row, (uint32_t)(row >> 32), col >> 1, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
-  const uint32_t hi = col & 1u ? x[2] : x[0], lo = col & 1u ? x[3] : x[1];
-  return (double)(((uint64_t)hi << 21) | (lo >> 11)) * 0x1.0p-53;
-}
-
-// the same stream with one more coordinate, for samplers that revisit a column (Gibbs): the fourth counter
-// word is the sweep, 1 <= sweep < 2^32.  Sweep 0 is sample_uniform's stream by construction, so the state
-// "after sweep 0" is the forward-sampled state of the same seed and no uniform is used twice.
+// The uniform of stream row `chain`, code column `col` and sweep `sweep`: 53 bits in [0, 1); columns 2k and
+// 2k + 1 share a call.  The sweep, the fourth counter word, is for samplers that revisit a column (Gibbs):
+// 1 <= sweep < 2^32.  Sweep 0 is the forward sampler's stream (sample_uniform), so the state "after sweep 0"
+// is the forward-sampled state of the same seed and no uniform is used twice.
 PGM_HD double sample_uniform3(uint64_t seed, uint64_t chain, uint32_t col, uint32_t sweep) {
   uint32_t x[4];
   philox4x32_10((uint32_t)chain, (uint32_t)(chain >> 32), col >> 1, sweep, (uint32_t)seed, (uint32_t)(seed >> 32), x);
   const uint32_t hi = col & 1u ? x[2] : x[0], lo = col & 1u ? x[3] : x[1];
   return (double)(((uint64_t)hi << 21) | (lo >> 11)) * 0x1.0p-53;
 }
+PGM_HD double sample_uniform(uint64_t seed, uint64_t row, uint32_t col) { return sample_uniform3(seed, row, col, 0u); }
 
 // ---------------------------------------------------------------------------- the plan
 // the families of a fit plan (same descriptors, same flat table layout) given in a topological order
@@ -58,19 +52,19 @@ struct PGM_FIT_LOCAL SamplePlan {
   FitPlan fit;
 };
 
-// the handle behind pgm_sample_plan_create: the plan plus its lazily uploaded device copy (pgmsample.hip)
+// the handle behind pgm_sample_plan_create: the plan plus its lazily uploaded device copy (dev owns what
+// the d_* point to and sets them: pgmsample.hip sample_use)
 struct PGM_FIT_LOCAL SampleHandle {
   SamplePlan p;
-  int device = -1;  // the device the copies below live on (-1: not uploaded)
-  void *d_fams = nullptr, *d_col_off = nullptr, *d_modes = nullptr, *d_err = nullptr;
+  pgmdev::PlanDev dev;
+  const FitFam *d_fams = nullptr;
+  const int64_t *d_col_off = nullptr;
+  uint8_t *d_modes = nullptr;  // the staging buffer of a call's modes: one byte per family
 };
 
 // validate the families (fit_plan_build's layout + the sampler's ordering rules); PGM_OK, or PGM_EINVAL
 // with pgm_last_error set
 PGM_FIT_LOCAL int sample_plan_build(const pgm_fit_family *fams, int32_t n, SamplePlan &out);
-// whether a launch takes the four-rows-per-lane kernel: a lane's dword of 4 codes must be aligned in every
-// column (codes, ld and row0 multiples of 4); else the one-row kernel runs
-PGM_FIT_LOCAL bool sample_vec4(const void *codes, int64_t ld, int64_t row0);
 PGM_FIT_LOCAL int sample_cdf_check(const SampleHandle *h, const double *values, const double *cdf);
 // the argument checks of pgm_sample_forward (no HIP call); *blocks: workgroups of the launch
 PGM_FIT_LOCAL int sample_forward_check(const SampleHandle *h, const double *values, const double *cdf,

@@ -5,7 +5,6 @@
 // HillClimbSearch (pgm_fit_score).  Replaces the reference's per-node pandas groupby
 // (estimators/base.py:67-176) and the per-CPD normalisation (MLE.py:183-212, BayesianEstimator.py:252-264).
 // The host side (validation, table layout, family groups, argument checks) is pgmfit_plan.cpp.
-#include <mutex>
 #include <type_traits>
 
 #include "pgm_fit.h"
@@ -22,7 +21,7 @@
 // index leaves the family's table.
 // W = false: each row counts 1 (uint32 LDS bins, int64 tables: exact, order-independent).
 // W = true:  each row counts weights[row0 + row] (fp64 LDS bins and tables: the order of addition varies).
-// V4 = true (codes, ld and row0 all multiples of 4: fit_count_vec4): a lane takes 4 consecutive rows and
+// V4 = true (codes, ld and row0 all multiples of 4: codes_vec4): a lane takes 4 consecutive rows and
 // loads their 4 codes of a column as one dword, so a family costs a quarter of the dependent load round
 // trips; the rows of a chunk's tail that do not fill a dword take the one-row path.
 template <bool W, bool V4>
@@ -612,84 +611,34 @@ __global__ __launch_bounds__(kCiChunk) void k_fit_ci_finish(const FitFam *__rest
 }
 
 // ---------------------------------------------------------------------------- the handle's device side
-static std::mutex g_fit_mu;
+// The descriptors on the current device, and with a stage what only the score / CI launches need: the work
+// lists, and per chunk one fp64 partial and one int64 count (part_obs / dof).
+enum { kFitNoStage = -1, kFitScore = 0, kFitCi = 1 };
 
-static void fit_free_device(FitHandle *h) {
-  for (void **p : {&h->d_fams, &h->d_groups, &h->d_col_off, &h->d_err, &h->d_chunk_off, &h->d_part, &h->d_part_obs,
-                   &h->d_ci_off, &h->d_ci_multi_off, &h->d_ci_single, &h->d_ci_part, &h->d_ci_dof}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
+static int fit_use(FitHandle *h, int stage = kFitNoStage) {
+  using pgmdev::scratch;
+  using pgmdev::upload;
+  const FitPlan &p = h->p;
+  const pgmdev::Slot base[] = {upload(h->d_fams, p.fams), upload(h->d_groups, p.groups), upload(h->d_col_off, p.col_off)};
+  if (stage == kFitScore) {
+    const size_t chunks = (size_t)p.chunk_off.back();
+    const pgmdev::Slot score[] = {upload(h->d_chunk_off, p.chunk_off), scratch(h->d_part, chunks),
+                                  scratch(h->d_part_obs, chunks)};
+    return h->dev.use(kHipDevOps, base, stage, score);
   }
-  h->device = -1;
-}
-
-// the descriptors on the current device (uploaded on first use; again when the device changes)
-static int fit_upload(FitHandle *h) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_fit_mu);
-  if (h->device == dev) return PGM_OK;
-  fit_free_device(h);
-  const FitPlan &p = h->p;
-  const size_t nf = p.fams.size() * sizeof(FitFam), ng = p.groups.size() * sizeof(FitGroup);
-  const size_t nc = p.col_off.size() * sizeof(int64_t);
-  HIP_TRY(hipMalloc(&h->d_fams, nf));
-  HIP_TRY(hipMalloc(&h->d_groups, ng));
-  HIP_TRY(hipMalloc(&h->d_col_off, nc));
-  HIP_TRY(hipMalloc(&h->d_err, sizeof(int32_t)));
-  HIP_TRY(hipMemcpy(h->d_fams, p.fams.data(), nf, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->d_groups, p.groups.data(), ng, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->d_col_off, p.col_off.data(), nc, hipMemcpyHostToDevice));
-  h->device = dev;
-  return PGM_OK;
-}
-
-// what only the score launches need, on the device fit_upload chose (allocated by the first pgm_fit_score)
-static int fit_score_upload(FitHandle *h) {
-  std::lock_guard<std::mutex> lk(g_fit_mu);
-  if (h->d_part) return PGM_OK;
-  const FitPlan &p = h->p;
-  const size_t nc = p.chunk_off.size() * sizeof(int64_t), chunks = (size_t)p.chunk_off.back();
-  // d_part is set last: a call that failed half-way starts over (fit_free_device releases the rest)
-  if (!h->d_chunk_off) HIP_TRY(hipMalloc(&h->d_chunk_off, nc));
-  if (!h->d_part_obs) HIP_TRY(hipMalloc(&h->d_part_obs, chunks * sizeof(int64_t)));
-  HIP_TRY(hipMemcpy(h->d_chunk_off, p.chunk_off.data(), nc, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&h->d_part, chunks * sizeof(double)));
-  return PGM_OK;
-}
-
-// what only the CI launches need, on the device fit_upload chose (allocated by the first pgm_fit_citest)
-static int fit_ci_upload(FitHandle *h) {
-  std::lock_guard<std::mutex> lk(g_fit_mu);
-  if (h->d_ci_part) return PGM_OK;
-  const FitPlan &p = h->p;
-  const size_t no = p.ci_off.size() * sizeof(int64_t), chunks = (size_t)p.ci_off.back();
-  const size_t ns = (p.ci_single.empty() ? 1 : p.ci_single.size()) * sizeof(int32_t);
-  // d_ci_part is set last: a call that failed half-way starts over (fit_free_device releases the rest)
-  if (!h->d_ci_off) HIP_TRY(hipMalloc(&h->d_ci_off, no));
-  if (!h->d_ci_multi_off) HIP_TRY(hipMalloc(&h->d_ci_multi_off, no));
-  if (!h->d_ci_single) HIP_TRY(hipMalloc(&h->d_ci_single, ns));
-  if (!h->d_ci_dof) HIP_TRY(hipMalloc(&h->d_ci_dof, chunks * sizeof(int64_t)));
-  HIP_TRY(hipMemcpy(h->d_ci_off, p.ci_off.data(), no, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->d_ci_multi_off, p.ci_multi_off.data(), no, hipMemcpyHostToDevice));
-  if (!p.ci_single.empty())
-    HIP_TRY(hipMemcpy(h->d_ci_single, p.ci_single.data(), p.ci_single.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&h->d_ci_part, chunks * sizeof(double)));
-  return PGM_OK;
+  if (stage == kFitCi) {
+    const size_t chunks = (size_t)p.ci_off.back();
+    const pgmdev::Slot ci[] = {upload(h->d_ci_off, p.ci_off), upload(h->d_ci_multi_off, p.ci_multi_off),
+                               upload(h->d_ci_single, p.ci_single), scratch(h->d_ci_part, chunks),
+                               scratch(h->d_ci_dof, chunks)};
+    return h->dev.use(kHipDevOps, base, stage, ci);
+  }
+  return h->dev.use(kHipDevOps, base);
 }
 
 extern "C" {
 
-int pgm_fit_plan_destroy(void *plan) {
-  if (!plan) return PGM_OK;
-  FitHandle *h = static_cast<FitHandle *>(plan);
-  {
-    std::lock_guard<std::mutex> lk(g_fit_mu);
-    fit_free_device(h);
-  }
-  delete h;
-  return PGM_OK;
-}
+int pgm_fit_plan_destroy(void *plan) { return pgm_plan_destroy<FitHandle>(plan); }
 
 int pgm_fit_count(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
                   const double *weights, void *tables, void *stream) {
@@ -698,19 +647,16 @@ int pgm_fit_count(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, 
   const int st = fit_count_check(h, codes, n_cols, ld, row0, n_rows, tables, &blocks);
   if (st != PGM_OK) return st;
   if (blocks == 0) return PGM_OK;
-  const int up = fit_upload(h);
+  int up = fit_use(h);
+  if (up == PGM_OK) up = flag_reset(h->dev, stream);
   if (up != PGM_OK) return up;
-  int32_t *err = static_cast<int32_t *>(h->d_err);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), S(stream)));
-  const FitFam *fams = static_cast<const FitFam *>(h->d_fams);
-  const FitGroup *groups = static_cast<const FitGroup *>(h->d_groups);
   const uint32_t ng = (uint32_t)h->p.groups.size();
   const dim3 grid((unsigned)blocks), wg(kFitBlock);
   const size_t lds = kFitTileBins * (weights ? sizeof(double) : sizeof(uint32_t));
-  const bool v4 = fit_count_vec4(codes, ld, row0);
+  const bool v4 = codes_vec4(codes, ld, row0);
 #define FIT_LAUNCH(W, V4)                                                                                        \
-  hipLaunchKernelGGL((k_fit_count<W, V4>), grid, wg, lds, S(stream), fams, groups, ng, codes, ld, row0, n_rows, \
-                     weights, tables, err)
+  hipLaunchKernelGGL((k_fit_count<W, V4>), grid, wg, lds, S(stream), h->d_fams, h->d_groups, ng, codes, ld, row0, \
+                     n_rows, weights, tables, h->dev.flag())
   if (weights) {
     if (v4) FIT_LAUNCH(true, true);
     else FIT_LAUNCH(true, false);
@@ -719,11 +665,10 @@ int pgm_fit_count(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, 
     else FIT_LAUNCH(false, false);
   }
 #undef FIT_LAUNCH
-  HIP_TRY(hipGetLastError());
   // PGM_EINDEX is this call's status: the flag is read back after the launch (synchronises the stream)
   int32_t bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, err, sizeof bad, hipMemcpyDeviceToHost, S(stream)));
-  HIP_TRY(hipStreamSynchronize(S(stream)));
+  const int rd = flag_read(h->dev, stream, &bad);
+  if (rd != PGM_OK) return rd;
   if (bad) return pgmi_fail(PGM_EINDEX, "fit_count: a state code is >= its variable's cardinality");
   return PGM_OK;
 }
@@ -737,18 +682,16 @@ int pgm_fit_estep(void *plan, const int32_t *latent_cols, int32_t n_latent, cons
   const int st = fit_estep_check(h, latent_cols, n_latent, values, codes, n_cols, ld, row0, n_rows, tables, &spec, &blocks);
   if (st != PGM_OK) return st;
   if (blocks == 0) return PGM_OK;
-  const int up = fit_upload(h);
+  int up = fit_use(h);
+  if (up == PGM_OK) up = flag_reset(h->dev, stream);
   if (up != PGM_OK) return up;
-  int32_t *err = static_cast<int32_t *>(h->d_err);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), S(stream)));
   hipLaunchKernelGGL(k_fit_estep, dim3((unsigned)blocks), dim3(kFitBlock), (size_t)fit_estep_lds(spec.n_lat_fam), S(stream),
-                     static_cast<const FitFam *>(h->d_fams), static_cast<const FitGroup *>(h->d_groups),
-                     (uint32_t)h->p.groups.size(), spec, values, codes, ld, row0, n_rows, tables, loglik, err);
-  HIP_TRY(hipGetLastError());
+                     h->d_fams, h->d_groups, (uint32_t)h->p.groups.size(), spec, values, codes, ld, row0, n_rows, tables,
+                     loglik, h->dev.flag());
   // PGM_EINDEX is this call's status, as in pgm_fit_count (synchronises the stream)
   int32_t bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, err, sizeof bad, hipMemcpyDeviceToHost, S(stream)));
-  HIP_TRY(hipStreamSynchronize(S(stream)));
+  const int rd = flag_read(h->dev, stream, &bad);
+  if (rd != PGM_OK) return rd;
   if (bad) return pgmi_fail(PGM_EINDEX, "fit_estep: a state code is >= its variable's cardinality");
   return PGM_OK;
 }
@@ -757,13 +700,13 @@ int pgm_fit_finish(void *plan, const void *counts, const double *pseudo, int32_t
   FitHandle *h = static_cast<FitHandle *>(plan);
   const int st = fit_finish_check(h, counts, mode, values);
   if (st != PGM_OK) return st;
-  const int up = fit_upload(h);
+  const int up = fit_use(h);
   if (up != PGM_OK) return up;
   const int64_t cols = h->p.col_off.back();
   const int64_t blocks = (cols + 255) / 256;
   if (blocks > INT32_MAX) return pgmi_fail(PGM_EINVAL, "fit_finish: too many CPD columns for one launch");
-  const FitFam *fams = static_cast<const FitFam *>(h->d_fams);
-  const int64_t *col_off = static_cast<const int64_t *>(h->d_col_off);
+  const FitFam *fams = h->d_fams;
+  const int64_t *col_off = h->d_col_off;
   const int32_t nf = (int32_t)h->p.fams.size(), bayes = mode & PGM_FIT_BAYES ? 1 : 0;
   if (mode & PGM_FIT_WEIGHTED)
     hipLaunchKernelGGL(k_fit_finish<true>, dim3((unsigned)blocks), dim3(256), 0, S(stream), fams, col_off, nf, counts,
@@ -781,13 +724,12 @@ int pgm_fit_score(void *plan, const int64_t *counts, int32_t mode, const double 
   int64_t blocks = 0;
   const int st = fit_score_check(h, counts, mode, alpha, beta, scores, &blocks);
   if (st != PGM_OK) return st;
-  int up = fit_upload(h);
-  if (up == PGM_OK) up = fit_score_upload(h);
+  const int up = fit_use(h, kFitScore);
   if (up != PGM_OK) return up;
-  const FitFam *fams = static_cast<const FitFam *>(h->d_fams);
-  const int64_t *chunk_off = static_cast<const int64_t *>(h->d_chunk_off);
-  double *part = static_cast<double *>(h->d_part);
-  int64_t *part_obs = static_cast<int64_t *>(h->d_part_obs);
+  const FitFam *fams = h->d_fams;
+  const int64_t *chunk_off = h->d_chunk_off;
+  double *part = h->d_part;
+  int64_t *part_obs = h->d_part_obs;
   const int32_t nf = (int32_t)h->p.fams.size(), skip = mode & PGM_SCORE_SKIP_EMPTY ? 1 : 0;
   const dim3 grid((unsigned)blocks), wg(kScoreChunk);
   if (mode & PGM_SCORE_LL)
@@ -809,15 +751,13 @@ int pgm_fit_citest(void *plan, const int64_t *counts, double lambda, int32_t fla
   int64_t blocks = 0;
   const int st = fit_citest_check(h, counts, lambda, flags, stat, dof, pvalue, &blocks);
   if (st != PGM_OK) return st;
-  int up = fit_upload(h);
-  if (up == PGM_OK) up = fit_ci_upload(h);
+  const int up = fit_use(h, kFitCi);
   if (up != PGM_OK) return up;
-  const FitFam *fams = static_cast<const FitFam *>(h->d_fams);
-  const int64_t *ci_off = static_cast<const int64_t *>(h->d_ci_off);
-  const int64_t *multi_off = static_cast<const int64_t *>(h->d_ci_multi_off);
-  const int32_t *single = static_cast<const int32_t *>(h->d_ci_single);
-  double *part = static_cast<double *>(h->d_ci_part);
-  int64_t *part_dof = static_cast<int64_t *>(h->d_ci_dof);
+  const FitFam *fams = h->d_fams;
+  const int64_t *ci_off = h->d_ci_off, *multi_off = h->d_ci_multi_off;
+  const int32_t *single = h->d_ci_single;
+  double *part = h->d_ci_part;
+  int64_t *part_dof = h->d_ci_dof;
   const int32_t nf = (int32_t)h->p.fams.size(), ns = (int32_t)h->p.ci_single.size();
   const int32_t kind = lambda == 1.0 ? 0 : lambda == 0.0 ? 1 : lambda == -1.0 ? 2 : 3;
   const double scale = kind == 0 ? 1.0 : kind == 3 ? 2.0 / (lambda * (lambda + 1.0)) : 2.0;
@@ -843,10 +783,10 @@ int pgm_fit_states_observed(void *plan, const int64_t *counts, int64_t *n_states
   FitHandle *h = static_cast<FitHandle *>(plan);
   const int st = fit_states_check(h, counts, n_states);
   if (st != PGM_OK) return st;
-  const int up = fit_upload(h);
+  const int up = fit_use(h);
   if (up != PGM_OK) return up;
-  hipLaunchKernelGGL(k_fit_states_observed, dim3((unsigned)h->p.fams.size()), dim3(256), 0, S(stream),
-                     static_cast<const FitFam *>(h->d_fams), counts, n_states);
+  hipLaunchKernelGGL(k_fit_states_observed, dim3((unsigned)h->p.fams.size()), dim3(256), 0, S(stream), h->d_fams, counts,
+                     n_states);
   HIP_TRY(hipGetLastError());
   return PGM_OK;
 }

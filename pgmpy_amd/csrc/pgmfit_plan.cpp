@@ -4,7 +4,6 @@
 // (tools/fit_plan_selftest.cpp).  The kernels and launches are pgmfit.hip.
 #include <cmath>
 #include <cstring>
-#include <new>
 
 #include "pgm_fit.h"
 #include "pgm_internal.h"
@@ -92,10 +91,8 @@ int fit_count_check(const FitHandle *h, const uint8_t *codes, int32_t n_cols, in
   if (!h) return pgmi_fail(PGM_EINVAL, "fit_count: null plan");
   if (!codes) return pgmi_fail(PGM_EINVAL, "fit_count: null codes");
   if (!tables) return pgmi_fail(PGM_EINVAL, "fit_count: null tables");
-  if (n_rows < 0 || row0 < 0) return pgmi_failf(PGM_EINVAL, "fit_count: n_rows %lld row0 %lld", (long long)n_rows, (long long)row0);
-  if (ld < n_rows || row0 > ld - n_rows)
-    return pgmi_failf(PGM_EINVAL, "fit_count: rows [%lld, %lld) outside ld %lld", (long long)row0,
-                      (long long)(row0 + n_rows), (long long)ld);
+  const int st = window_check("fit_count", "rows", ld, row0, n_rows, 0);
+  if (st != PGM_OK) return st;
   if (n_cols < h->p.n_cols)
     return pgmi_failf(PGM_EINVAL, "fit_count: the plan reads column %d, codes has %d columns", h->p.n_cols - 1, n_cols);
   const int64_t chunks = (n_rows + kFitRowsPerBlock - 1) / kFitRowsPerBlock;
@@ -106,8 +103,25 @@ int fit_count_check(const FitHandle *h, const uint8_t *codes, int32_t n_cols, in
   return PGM_OK;
 }
 
-bool fit_count_vec4(const uint8_t *codes, int64_t ld, int64_t row0) {
+bool codes_vec4(const void *codes, int64_t ld, int64_t row0) {
   return ((uintptr_t)codes & 3) == 0 && (ld & 3) == 0 && (row0 & 3) == 0;
+}
+
+int window_check(const char *what, const char *noun, int64_t ld, int64_t row0, int64_t n, int64_t first) {
+  if (n < 0 || row0 < 0) return pgmi_failf(PGM_EINVAL, "%s: n_%s %lld row0 %lld", what, noun, (long long)n, (long long)row0);
+  if (ld < n || row0 > ld - n)
+    return pgmi_failf(PGM_EINVAL, "%s: rows [%lld, %lld) outside ld %lld", what, (long long)row0, (long long)(row0 + n),
+                      (long long)ld);
+  if (first < 0 || first > INT64_MAX - n)
+    return pgmi_failf(PGM_EINVAL, "%s: stream %s [%lld, + %lld)", what, noun, (long long)first, (long long)n);
+  return PGM_OK;
+}
+
+void plan_info_layout(const FitPlan &p, int64_t *offsets, int64_t *sizes) {
+  for (size_t f = 0; f < p.fams.size(); ++f) {
+    if (offsets) offsets[f] = p.fams[f].off;
+    if (sizes) sizes[f] = p.fams[f].size;
+  }
 }
 
 int fit_finish_check(const FitHandle *h, const void *counts, int32_t mode, const double *values) {
@@ -217,10 +231,8 @@ int fit_estep_check(const FitHandle *h, const int32_t *latent_cols, int32_t n_la
   int32_t obs_cols = 0;
   const int st = fit_estep_spec(h, latent_cols, n_latent, "fit_estep", spec, &obs_cols);
   if (st != PGM_OK) return st;
-  if (n_rows < 0 || row0 < 0) return pgmi_failf(PGM_EINVAL, "fit_estep: n_rows %lld row0 %lld", (long long)n_rows, (long long)row0);
-  if (ld < n_rows || row0 > ld - n_rows)
-    return pgmi_failf(PGM_EINVAL, "fit_estep: rows [%lld, %lld) outside ld %lld", (long long)row0,
-                      (long long)(row0 + n_rows), (long long)ld);
+  const int win = window_check("fit_estep", "rows", ld, row0, n_rows, 0);
+  if (win != PGM_OK) return win;
   if (n_cols < obs_cols)
     return pgmi_failf(PGM_EINVAL, "fit_estep: the plan reads the observed column %d, codes has %d columns", obs_cols - 1,
                       n_cols);
@@ -242,17 +254,7 @@ int fit_states_check(const FitHandle *h, const int64_t *counts, const int64_t *n
 extern "C" {
 
 int pgm_fit_plan_create(const pgm_fit_family *fams, int32_t n, void **plan) {
-  if (!plan) return pgmi_fail(PGM_EINVAL, "fit_plan_create: null plan");
-  *plan = nullptr;
-  FitHandle *h = new (std::nothrow) FitHandle();
-  if (!h) return pgmi_fail(PGM_ENOMEM, "fit_plan_create: out of memory");
-  const int st = fit_plan_build(fams, n, h->p);
-  if (st != PGM_OK) {
-    delete h;
-    return st;
-  }
-  *plan = h;
-  return PGM_OK;
+  return plan_create<FitHandle>("fit_plan_create", plan, [&](FitPlan &p) { return fit_plan_build(fams, n, p); });
 }
 
 int pgm_fit_plan_info(void *plan, pgm_fit_info_t *info, int64_t *offsets, int64_t *sizes, int32_t *strides,
@@ -270,9 +272,8 @@ int pgm_fit_plan_info(void *plan, pgm_fit_info_t *info, int64_t *offsets, int64_
     info->total_bins = p.total_bins;
     info->total_columns = p.col_off.back();
   }
+  plan_info_layout(p, offsets, sizes);
   for (size_t f = 0; f < p.fams.size(); ++f) {
-    if (offsets) offsets[f] = p.fams[f].off;
-    if (sizes) sizes[f] = p.fams[f].size;
     if (strides) memcpy(strides + f * PGM_MAX_DIMS, p.fams[f].stride, sizeof p.fams[f].stride);
     if (groups) groups[f] = p.group_of[f];
   }

@@ -6,7 +6,6 @@
 // chain.  The host side (validation, incidence lists, argument checks, host-only queries) is
 // pgmgibbs_plan.cpp.
 #include <cstring>
-#include <mutex>
 
 #include "pgm_gibbs.h"
 #include "pgm_hip_common.h"
@@ -165,53 +164,18 @@ __global__ __launch_bounds__(kGibbsBlock) void k_gibbs_start(const int32_t *__re
 }
 
 // ---------------------------------------------------------------------------- the handle's device side
-static std::mutex g_gibbs_mu;
-
-static void gibbs_free_device(GibbsHandle *h) {
-  for (void **p : {&h->d_card, &h->d_inc_off, &h->d_inc, &h->d_others, &h->d_clamp, &h->d_err}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  h->device = -1;
-}
-
-// the descriptors on the current device (uploaded on first use; again when the device changes)
-static int gibbs_upload(GibbsHandle *h) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_gibbs_mu);
-  if (h->device == dev) return PGM_OK;
-  gibbs_free_device(h);
+// the descriptors and the staging buffer of a call's clamp on the current device
+static int gibbs_use(GibbsHandle *h) {
+  using pgmdev::upload;
   const GibbsPlan &p = h->p;
-  const size_t nc = p.card.size() * sizeof(int32_t), no = p.inc_off.size() * sizeof(int32_t),
-               ni = p.inc.size() * sizeof(GibbsInc), nt = (p.others.size() + 1) * sizeof(GibbsOther);
-  HIP_TRY(hipMalloc(&h->d_card, nc));
-  HIP_TRY(hipMalloc(&h->d_inc_off, no));
-  HIP_TRY(hipMalloc(&h->d_inc, ni));
-  HIP_TRY(hipMalloc(&h->d_others, nt));
-  HIP_TRY(hipMalloc(&h->d_clamp, p.card.size()));
-  HIP_TRY(hipMalloc(&h->d_err, sizeof(int32_t)));
-  HIP_TRY(hipMemcpy(h->d_card, p.card.data(), nc, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->d_inc_off, p.inc_off.data(), no, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->d_inc, p.inc.data(), ni, hipMemcpyHostToDevice));
-  if (!p.others.empty())
-    HIP_TRY(hipMemcpy(h->d_others, p.others.data(), p.others.size() * sizeof(GibbsOther), hipMemcpyHostToDevice));
-  h->device = dev;
-  return PGM_OK;
+  const pgmdev::Slot base[] = {upload(h->d_card, p.card), upload(h->d_inc_off, p.inc_off), upload(h->d_inc, p.inc),
+                               upload(h->d_others, p.others), pgmdev::scratch(h->d_clamp, p.card.size())};
+  return h->dev.use(kHipDevOps, base);
 }
 
 extern "C" {
 
-int pgm_gibbs_plan_destroy(void *plan) {
-  if (!plan) return PGM_OK;
-  GibbsHandle *h = static_cast<GibbsHandle *>(plan);
-  {
-    std::lock_guard<std::mutex> lk(g_gibbs_mu);
-    gibbs_free_device(h);
-  }
-  delete h;
-  return PGM_OK;
-}
+int pgm_gibbs_plan_destroy(void *plan) { return pgm_plan_destroy<GibbsHandle>(plan); }
 
 int pgm_gibbs_start(void *plan, uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_chains,
                     int64_t first_chain, uint64_t seed, void *stream) {
@@ -220,10 +184,10 @@ int pgm_gibbs_start(void *plan, uint8_t *codes, int32_t n_cols, int64_t ld, int6
   const int st = gibbs_start_check(h, codes, n_cols, ld, row0, n_chains, first_chain, &blocks);
   if (st != PGM_OK) return st;
   if (blocks == 0) return PGM_OK;
-  const int up = gibbs_upload(h);
+  const int up = gibbs_use(h);
   if (up != PGM_OK) return up;
-  hipLaunchKernelGGL(k_gibbs_start, dim3((unsigned)blocks), dim3(kGibbsBlock), 0, S(stream),
-                     static_cast<const int32_t *>(h->d_card), h->p.n_cols, codes, ld, row0, n_chains, first_chain, seed);
+  hipLaunchKernelGGL(k_gibbs_start, dim3((unsigned)blocks), dim3(kGibbsBlock), 0, S(stream), h->d_card, h->p.n_cols, codes,
+                     ld, row0, n_chains, first_chain, seed);
   HIP_TRY(hipGetLastError());
   return PGM_OK;
 }
@@ -238,25 +202,15 @@ int pgm_gibbs_sweep(void *plan, const double *values, uint8_t *codes, int32_t n_
                                    trace, ld_trace, thin, &blocks);
   if (st != PGM_OK) return st;
   if (blocks == 0) return PGM_OK;
-  const int up = gibbs_upload(h);
-  if (up != PGM_OK) return up;
   const GibbsPlan &p = h->p;
-  int32_t *err = static_cast<int32_t *>(h->d_err);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), S(stream)));
-  if (clamp) {
-    bool any = false;
-    for (int32_t c = 0; c < p.n_cols; ++c) any |= clamp[c] != 0;
-    if (!any) clamp = nullptr;  // none clamped
-  }
   GibbsArgs a;
   memset(&a, 0, sizeof a);
-  if (clamp) {  // pageable source: staged before the call returns, ordered with the launch on the stream
-    HIP_TRY(hipMemcpyAsync(h->d_clamp, clamp, (size_t)p.n_cols, hipMemcpyHostToDevice, S(stream)));
-    a.clamp = static_cast<const uint8_t *>(h->d_clamp);
-  }
-  a.card = static_cast<const int32_t *>(h->d_card), a.inc_off = static_cast<const int32_t *>(h->d_inc_off);
-  a.inc = static_cast<const GibbsInc *>(h->d_inc), a.others = static_cast<const GibbsOther *>(h->d_others);
-  a.values = values, a.codes = codes, a.trace = trace, a.uniforms = uniforms, a.err = err;
+  int up = gibbs_use(h);
+  if (up == PGM_OK) up = flag_reset(h->dev, stream);
+  if (up == PGM_OK) up = stage_bytes(h->d_clamp, clamp, (size_t)p.n_cols, stream, &a.clamp);
+  if (up != PGM_OK) return up;
+  a.card = h->d_card, a.inc_off = h->d_inc_off, a.inc = h->d_inc, a.others = h->d_others;
+  a.values = values, a.codes = codes, a.trace = trace, a.uniforms = uniforms, a.err = h->dev.flag();
   a.ld = ld, a.row0 = row0, a.n_chains = n_chains, a.first_chain = first_chain, a.first_sweep = first_sweep;
   a.n_sweeps = n_sweeps, a.ld_trace = ld_trace, a.thin = thin, a.seed = seed;
   a.n_cols = p.n_cols, a.n_cols_codes = n_cols;
@@ -269,11 +223,10 @@ int pgm_gibbs_sweep(void *plan, const double *values, uint8_t *codes, int32_t n_
     if (uniforms) hipLaunchKernelGGL((k_gibbs_sweep<false, true>), grid, wg, 0, S(stream), a);
     else hipLaunchKernelGGL((k_gibbs_sweep<false, false>), grid, wg, 0, S(stream), a);
   }
-  HIP_TRY(hipGetLastError());
   // the status is this call's: the flags are read back after the launch (synchronises the stream)
   int32_t bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, err, sizeof bad, hipMemcpyDeviceToHost, S(stream)));
-  HIP_TRY(hipStreamSynchronize(S(stream)));
+  const int rd = flag_read(h->dev, stream, &bad);
+  if (rd != PGM_OK) return rd;
   if (bad & kGibbsErrCode) return pgmi_fail(PGM_EINDEX, "gibbs_sweep: a state code is >= its variable's cardinality");
   if (bad & kGibbsErrTotal)
     return pgmi_fail(PGM_EINVAL, "gibbs_sweep: a conditional's total is not finite or not > 0 (the state has probability 0)");

@@ -4,7 +4,6 @@
 // include: this unit is tested on the CPU on its own (tools/gibbs_plan_selftest.cpp, linked with
 // pgmfit_plan.cpp).  The kernels and launches are pgmgibbs.hip.
 #include <cstring>
-#include <new>
 
 #include "pgm_gibbs.h"
 #include "pgm_internal.h"
@@ -81,13 +80,8 @@ static int gibbs_window_check(const char *what, const GibbsHandle *h, const uint
                               int64_t row0, int64_t n_chains, int64_t first_chain, int64_t *blocks) {
   if (!h) return pgmi_failf(PGM_EINVAL, "%s: null plan", what);
   if (!codes) return pgmi_failf(PGM_EINVAL, "%s: null codes", what);
-  if (n_chains < 0 || row0 < 0)
-    return pgmi_failf(PGM_EINVAL, "%s: n_chains %lld row0 %lld", what, (long long)n_chains, (long long)row0);
-  if (ld < n_chains || row0 > ld - n_chains)
-    return pgmi_failf(PGM_EINVAL, "%s: rows [%lld, %lld) outside ld %lld", what, (long long)row0,
-                      (long long)(row0 + n_chains), (long long)ld);
-  if (first_chain < 0 || first_chain > INT64_MAX - n_chains)
-    return pgmi_failf(PGM_EINVAL, "%s: stream chains [%lld, + %lld)", what, (long long)first_chain, (long long)n_chains);
+  const int st = window_check(what, "chains", ld, row0, n_chains, first_chain);
+  if (st != PGM_OK) return st;
   if (n_cols < h->p.n_cols)
     return pgmi_failf(PGM_EINVAL, "%s: the plan has %d columns, codes has %d", what, h->p.n_cols, n_cols);
   const int64_t nb = (n_chains + kGibbsBlock - 1) / kGibbsBlock;
@@ -127,17 +121,8 @@ extern "C" {
 
 int pgm_gibbs_plan_create(const pgm_fit_family *factors, int32_t n_factors, const int32_t *card, int32_t n_cols,
                           void **plan) {
-  if (!plan) return pgmi_fail(PGM_EINVAL, "gibbs_plan_create: null plan");
-  *plan = nullptr;
-  GibbsHandle *h = new (std::nothrow) GibbsHandle();
-  if (!h) return pgmi_fail(PGM_ENOMEM, "gibbs_plan_create: out of memory");
-  const int st = gibbs_plan_build(factors, n_factors, card, n_cols, h->p);
-  if (st != PGM_OK) {
-    delete h;
-    return st;
-  }
-  *plan = h;
-  return PGM_OK;
+  return plan_create<GibbsHandle>("gibbs_plan_create", plan,
+                                  [&](GibbsPlan &p) { return gibbs_plan_build(factors, n_factors, card, n_cols, p); });
 }
 
 int pgm_gibbs_plan_info(void *plan, int64_t n_chains, pgm_gibbs_info_t *info, int64_t *offsets, int64_t *sizes,
@@ -161,10 +146,7 @@ int pgm_gibbs_plan_info(void *plan, int64_t n_chains, pgm_gibbs_info_t *info, in
     info->lds_budget = kGibbsLdsBudget;
     info->reg_card = kGibbsRegCard;
   }
-  for (size_t f = 0; f < p.fit.fams.size(); ++f) {
-    if (offsets) offsets[f] = p.fit.fams[f].off;
-    if (sizes) sizes[f] = p.fit.fams[f].size;
-  }
+  plan_info_layout(p.fit, offsets, sizes);
   if (inc_off) memcpy(inc_off, p.inc_off.data(), p.inc_off.size() * sizeof(int32_t));
   if (inc)
     for (size_t e = 0; e < p.inc.size(); ++e) inc[2 * e] = p.inc[e].factor, inc[2 * e + 1] = p.inc_pos[e];

@@ -3,9 +3,6 @@
 // (pgm_sample_plan_destroy, pgm_sample_cdf, pgm_sample_forward).  Replaces the reference's per-node numpy
 // loop over the unique parent configurations (sampling/Sampling.py:89-133, :341-400).  The host side
 // (validation, argument checks, the host-only queries) is pgmsample_plan.cpp.
-#include <cstring>
-#include <mutex>
-
 #include "pgm_hip_common.h"
 #include "pgm_sample.h"
 
@@ -124,7 +121,7 @@ __device__ __forceinline__ bool sample_walk(const FitFam *__restrict__ fams, int
 // `codes` is ONE pointer, read and written, without __restrict__: a work-item reads back the parent codes
 // it stored itself, so a const __restrict__ input next to a __restrict__ output would promise the compiler
 // an absence of aliasing that is false and would let it move the read-back above the store.
-// V4 (codes, ld and row0 multiples of 4: sample_vec4): a lane owns 4 consecutive rows and moves their 4
+// V4 (codes, ld and row0 multiples of 4: codes_vec4): a lane owns 4 consecutive rows and moves their 4
 // codes of a column as one aligned dword, so a wave's store is 256 contiguous bytes; the rows of the tail
 // that do not fill a dword take the one-row path.
 // W: an fp64 weight per row (likelihood weighting).  U: uniforms from the caller's matrix, not Philox.
@@ -157,65 +154,32 @@ __global__ __launch_bounds__(kSampleBlock) void k_sample_forward(const FitFam *_
 }
 
 // ---------------------------------------------------------------------------- the handle's device side
-static std::mutex g_sample_mu;
-
-static void sample_free_device(SampleHandle *h) {
-  for (void **p : {&h->d_fams, &h->d_col_off, &h->d_modes, &h->d_err}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  h->device = -1;
-}
-
-// the descriptors on the current device (uploaded on first use; again when the device changes)
-static int sample_upload(SampleHandle *h) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_sample_mu);
-  if (h->device == dev) return PGM_OK;
-  sample_free_device(h);
+// the descriptors and the staging buffer of a call's modes on the current device
+static int sample_use(SampleHandle *h) {
   const FitPlan &p = h->p.fit;
-  const size_t nf = p.fams.size() * sizeof(FitFam), nc = p.col_off.size() * sizeof(int64_t);
-  HIP_TRY(hipMalloc(&h->d_fams, nf));
-  HIP_TRY(hipMalloc(&h->d_col_off, nc));
-  HIP_TRY(hipMalloc(&h->d_modes, p.fams.size()));
-  HIP_TRY(hipMalloc(&h->d_err, sizeof(int32_t)));
-  HIP_TRY(hipMemcpy(h->d_fams, p.fams.data(), nf, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->d_col_off, p.col_off.data(), nc, hipMemcpyHostToDevice));
-  h->device = dev;
-  return PGM_OK;
+  const pgmdev::Slot base[] = {pgmdev::upload(h->d_fams, p.fams), pgmdev::upload(h->d_col_off, p.col_off),
+                               pgmdev::scratch(h->d_modes, p.fams.size())};
+  return h->dev.use(kHipDevOps, base);
 }
 
 extern "C" {
 
-int pgm_sample_plan_destroy(void *plan) {
-  if (!plan) return PGM_OK;
-  SampleHandle *h = static_cast<SampleHandle *>(plan);
-  {
-    std::lock_guard<std::mutex> lk(g_sample_mu);
-    sample_free_device(h);
-  }
-  delete h;
-  return PGM_OK;
-}
+int pgm_sample_plan_destroy(void *plan) { return pgm_plan_destroy<SampleHandle>(plan); }
 
 int pgm_sample_cdf(void *plan, const double *values, double *cdf, void *stream) {
   SampleHandle *h = static_cast<SampleHandle *>(plan);
   const int st = sample_cdf_check(h, values, cdf);
   if (st != PGM_OK) return st;
-  const int up = sample_upload(h);
+  int up = sample_use(h);
+  if (up == PGM_OK) up = flag_reset(h->dev, stream);
   if (up != PGM_OK) return up;
   const int64_t blocks = (h->p.fit.col_off.back() + 255) / 256;
-  int32_t *err = static_cast<int32_t *>(h->d_err);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), S(stream)));
-  hipLaunchKernelGGL(k_sample_cdf, dim3((unsigned)blocks), dim3(256), 0, S(stream),
-                     static_cast<const FitFam *>(h->d_fams), static_cast<const int64_t *>(h->d_col_off),
-                     (int32_t)h->p.fit.fams.size(), values, cdf, err);
-  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_sample_cdf, dim3((unsigned)blocks), dim3(256), 0, S(stream), h->d_fams, h->d_col_off,
+                     (int32_t)h->p.fit.fams.size(), values, cdf, h->dev.flag());
   // PGM_EINVAL is this call's status: the flag is read back after the launch (synchronises the stream)
   int32_t bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, err, sizeof bad, hipMemcpyDeviceToHost, S(stream)));
-  HIP_TRY(hipStreamSynchronize(S(stream)));
+  const int rd = flag_read(h->dev, stream, &bad);
+  if (rd != PGM_OK) return rd;
   if (bad) return pgmi_fail(PGM_EINVAL, "sample_cdf: a CPD column's total is not finite or not > 0");
   return PGM_OK;
 }
@@ -228,24 +192,17 @@ int pgm_sample_forward(void *plan, const double *values, const double *cdf, cons
   const int st = sample_forward_check(h, values, cdf, modes, codes, n_cols, ld, row0, n_rows, first_row, weights, &blocks);
   if (st != PGM_OK) return st;
   if (blocks == 0) return PGM_OK;
-  const int up = sample_upload(h);
-  if (up != PGM_OK) return up;
-  int32_t *err = static_cast<int32_t *>(h->d_err);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), S(stream)));
   const int32_t nf = (int32_t)h->p.fit.fams.size();
-  const uint8_t *d_modes = nullptr;
-  if (modes && memchr(modes, PGM_SAMPLE_GIVEN, (size_t)nf) == nullptr && memchr(modes, PGM_SAMPLE_OBSERVED, (size_t)nf) == nullptr)
-    modes = nullptr;  // all free
-  if (modes) {  // pageable source: staged before the call returns, ordered with the launch on the stream
-    HIP_TRY(hipMemcpyAsync(h->d_modes, modes, (size_t)nf, hipMemcpyHostToDevice, S(stream)));
-    d_modes = static_cast<const uint8_t *>(h->d_modes);
-  }
-  const FitFam *fams = static_cast<const FitFam *>(h->d_fams);
+  const uint8_t *d_modes = nullptr;  // FREE is 0: a call whose modes are all free passes none
+  int up = sample_use(h);
+  if (up == PGM_OK) up = flag_reset(h->dev, stream);
+  if (up == PGM_OK) up = stage_bytes(h->d_modes, modes, (size_t)nf, stream, &d_modes);
+  if (up != PGM_OK) return up;
   const dim3 grid((unsigned)blocks), wg(kSampleBlock);
-  const bool v4 = sample_vec4(codes, ld, row0);
+  const bool v4 = codes_vec4(codes, ld, row0);
 #define SAMPLE_LAUNCH(V4, W, U)                                                                                  \
-  hipLaunchKernelGGL((k_sample_forward<V4, W, U>), grid, wg, 0, S(stream), fams, nf, d_modes, values, cdf, codes, \
-                     ld, row0, n_rows, first_row, seed, weights, uniforms, err)
+  hipLaunchKernelGGL((k_sample_forward<V4, W, U>), grid, wg, 0, S(stream), h->d_fams, nf, d_modes, values, cdf, \
+                     codes, ld, row0, n_rows, first_row, seed, weights, uniforms, h->dev.flag())
 #define SAMPLE_LAUNCH_WU(V4)               \
   do {                                     \
     if (weights && uniforms) SAMPLE_LAUNCH(V4, true, true);   \
@@ -257,11 +214,10 @@ int pgm_sample_forward(void *plan, const double *values, const double *cdf, cons
   else SAMPLE_LAUNCH_WU(false);
 #undef SAMPLE_LAUNCH_WU
 #undef SAMPLE_LAUNCH
-  HIP_TRY(hipGetLastError());
   // PGM_EINDEX is this call's status: the flag is read back after the launch (synchronises the stream)
   int32_t bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, err, sizeof bad, hipMemcpyDeviceToHost, S(stream)));
-  HIP_TRY(hipStreamSynchronize(S(stream)));
+  const int rd = flag_read(h->dev, stream, &bad);
+  if (rd != PGM_OK) return rd;
   if (bad) return pgmi_fail(PGM_EINDEX, "sample_forward: a given state code is >= its variable's cardinality");
   return PGM_OK;
 }

@@ -5,7 +5,6 @@
 // pgmsample.hip.
 #include <cstring>
 #include <map>
-#include <new>
 
 #include "pgm_internal.h"
 #include "pgm_sample.h"
@@ -44,10 +43,6 @@ int sample_plan_build(const pgm_fit_family *fams, int32_t n, SamplePlan &out) {
   return fit_plan_build(fams, n, out.fit);  // the flat table layout (and the table size limit)
 }
 
-bool sample_vec4(const void *codes, int64_t ld, int64_t row0) {
-  return ((uintptr_t)codes & 3) == 0 && (ld & 3) == 0 && (row0 & 3) == 0;
-}
-
 int sample_cdf_check(const SampleHandle *h, const double *values, const double *cdf) {
   if (!h) return pgmi_fail(PGM_EINVAL, "sample_cdf: null plan");
   if (!values) return pgmi_fail(PGM_EINVAL, "sample_cdf: null values");
@@ -64,13 +59,8 @@ int sample_forward_check(const SampleHandle *h, const double *values, const doub
   if (!cdf) return pgmi_fail(PGM_EINVAL, "sample_forward: null cdf");
   if (!codes) return pgmi_fail(PGM_EINVAL, "sample_forward: null codes");
   if (weights && !values) return pgmi_fail(PGM_EINVAL, "sample_forward: weights need the values");
-  if (n_rows < 0 || row0 < 0)
-    return pgmi_failf(PGM_EINVAL, "sample_forward: n_rows %lld row0 %lld", (long long)n_rows, (long long)row0);
-  if (ld < n_rows || row0 > ld - n_rows)
-    return pgmi_failf(PGM_EINVAL, "sample_forward: rows [%lld, %lld) outside ld %lld", (long long)row0,
-                      (long long)(row0 + n_rows), (long long)ld);
-  if (first_row < 0 || first_row > INT64_MAX - n_rows)
-    return pgmi_failf(PGM_EINVAL, "sample_forward: stream rows [%lld, + %lld)", (long long)first_row, (long long)n_rows);
+  const int st = window_check("sample_forward", "rows", ld, row0, n_rows, first_row);
+  if (st != PGM_OK) return st;
   if (n_cols < h->p.fit.n_cols)
     return pgmi_failf(PGM_EINVAL, "sample_forward: the plan writes column %d, codes has %d columns", h->p.fit.n_cols - 1,
                       n_cols);
@@ -88,17 +78,7 @@ int sample_forward_check(const SampleHandle *h, const double *values, const doub
 extern "C" {
 
 int pgm_sample_plan_create(const pgm_fit_family *fams, int32_t n, void **plan) {
-  if (!plan) return pgmi_fail(PGM_EINVAL, "sample_plan_create: null plan");
-  *plan = nullptr;
-  SampleHandle *h = new (std::nothrow) SampleHandle();
-  if (!h) return pgmi_fail(PGM_ENOMEM, "sample_plan_create: out of memory");
-  const int st = sample_plan_build(fams, n, h->p);
-  if (st != PGM_OK) {
-    delete h;
-    return st;
-  }
-  *plan = h;
-  return PGM_OK;
+  return plan_create<SampleHandle>("sample_plan_create", plan, [&](SamplePlan &p) { return sample_plan_build(fams, n, p); });
 }
 
 int pgm_sample_plan_info(void *plan, const void *codes, int64_t ld, int64_t row0, const void *weights,
@@ -113,14 +93,11 @@ int pgm_sample_plan_info(void *plan, const void *codes, int64_t ld, int64_t row0
     info->rows_per_block = kSampleRowsPerBlock;
     info->total_bins = p.total_bins;
     info->total_columns = p.col_off.back();
-    info->vec4 = codes && sample_vec4(codes, ld, row0) ? 1 : 0;
+    info->vec4 = codes && codes_vec4(codes, ld, row0) ? 1 : 0;
     info->weighted = weights ? 1 : 0;
     info->explicit_uniforms = uniforms ? 1 : 0;
   }
-  for (size_t f = 0; f < p.fams.size(); ++f) {
-    if (offsets) offsets[f] = p.fams[f].off;
-    if (sizes) sizes[f] = p.fams[f].size;
-  }
+  plan_info_layout(p, offsets, sizes);
   return PGM_OK;
 }
 }

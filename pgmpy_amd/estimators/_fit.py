@@ -8,24 +8,16 @@ C order.
 """
 import ctypes
 
-import numpy as np
-
 from .. import _native as N
+from .._plan import Plan, codes_window, family_array, flat_tensor
 
 
-class FitPlan:
+class FitPlan(Plan):
+    _destroy = "pgm_fit_plan_destroy"
+
     def __init__(self, families):
         L = N.load_library()  # building and inspecting a plan needs no device
-        families = [(list(cols), list(cards)) for cols, cards in families]
-        fams = (N.FitFamily * max(len(families), 1))()
-        for f, (cols, cards) in enumerate(families):
-            if len(cols) != len(cards):
-                raise ValueError(f"family {f}: {len(cols)} columns, {len(cards)} cardinalities")
-            if not 1 <= len(cols) <= N.PGM_MAX_DIMS:
-                raise ValueError(f"family {f} has {len(cols) - 1} parents; at most {N.PGM_MAX_DIMS - 1} are supported")
-            fams[f].n_vars = len(cols)
-            for v, (c, k) in enumerate(zip(cols, cards)):
-                fams[f].col[v], fams[f].card[v] = int(c), int(k)
+        families, fams = family_array(families)
         self._h = ctypes.c_void_p()
         N.check(L.pgm_fit_plan_create(fams, len(families), ctypes.byref(self._h)), "fit_plan_create")
         n = len(families)
@@ -38,19 +30,10 @@ class FitPlan:
         self.strides = [list(strides[f * N.PGM_MAX_DIMS:f * N.PGM_MAX_DIMS + len(families[f][0])]) for f in range(n)]
         self.total_bins = int(self.info.total_bins)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                N.load_library().pgm_fit_plan_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+    def _int64_counts(self, counts, note=""):
+        import torch
 
-    def table(self, flat, f):
-        """Family f's [node_card, columns] view of a flat buffer (device tensor or ndarray)."""
-        card = self.families[f][1][0]
-        return flat[self.offsets[f]:self.offsets[f] + self.sizes[f]].reshape(card, self.sizes[f] // card)
+        flat_tensor("counts", counts, self.total_bins, torch.int64, "int64", f"of {self.total_bins} entries{note}")
 
     def count(self, codes, n_rows=None, row0=0, weights=None, tables=None):
         """Add the rows [row0, row0 + n_rows) of the device codes [n_cols, ld] (uint8) to `tables` (a
@@ -59,18 +42,14 @@ class FitPlan:
         import torch
 
         L = N.lib()
-        if codes.dtype != torch.uint8 or codes.dim() != 2 or not codes.is_contiguous():
-            raise ValueError("codes must be a contiguous [n_cols, ld] uint8 device tensor")
-        n_cols, ld = int(codes.shape[0]), int(codes.shape[1])
-        n_rows = ld - row0 if n_rows is None else int(n_rows)
+        n_cols, ld, n_rows = codes_window(codes, n_rows, row0)
         dtype = torch.int64 if weights is None else torch.float64
-        if weights is not None and (weights.dtype != torch.float64 or weights.numel() < ld
-                                    or not weights.is_contiguous()):
-            raise ValueError("weights must be a contiguous fp64 device tensor with one entry per row of codes")
+        if weights is not None:
+            flat_tensor("weights", weights, ld, entries="with one entry per row of codes")
         if tables is None:
             tables = torch.zeros(self.total_bins, dtype=dtype, device=codes.device)
-        elif tables.dtype != dtype or tables.numel() < self.total_bins or not tables.is_contiguous():
-            raise ValueError(f"tables must be a contiguous {dtype} device tensor of {self.total_bins} entries")
+        else:
+            flat_tensor("tables", tables, self.total_bins, dtype, str(dtype))
         N.check(L.pgm_fit_count(self._h, N.ptr(codes), n_cols, ld, int(row0), n_rows, N.ptr(weights), N.ptr(tables),
                                 N.stream_handle()), "fit_count")
         return tables
@@ -100,16 +79,12 @@ class FitPlan:
         import torch
 
         L = N.lib()
-        if codes.dtype != torch.uint8 or codes.dim() != 2 or not codes.is_contiguous():
-            raise ValueError("codes must be a contiguous [n_cols, ld] uint8 device tensor")
-        n_cols, ld = int(codes.shape[0]), int(codes.shape[1])
-        n_rows = ld - row0 if n_rows is None else int(n_rows)
-        if values.dtype != torch.float64 or values.numel() < self.total_bins or not values.is_contiguous():
-            raise ValueError(f"values must be a contiguous fp64 device tensor of {self.total_bins} entries")
+        n_cols, ld, n_rows = codes_window(codes, n_rows, row0)
+        flat_tensor("values", values, self.total_bins)
         if tables is None:
             tables = torch.zeros(self.total_bins, dtype=torch.float64, device=codes.device)
-        elif tables.dtype != torch.float64 or tables.numel() < self.total_bins or not tables.is_contiguous():
-            raise ValueError(f"tables must be a contiguous torch.float64 device tensor of {self.total_bins} entries")
+        else:
+            flat_tensor("tables", tables, self.total_bins, label="torch.float64")
         arr, n = self._latent_array(latent_cols)
         loglik = torch.zeros(ld, dtype=torch.float64, device=codes.device) if want_loglik else None
         N.check(L.pgm_fit_estep(self._h, arr, n, N.ptr(values), N.ptr(codes), n_cols, ld, int(row0), n_rows,
@@ -143,12 +118,10 @@ class FitPlan:
 
         L = N.lib()
         n = len(self.families)
-        if counts.dtype != torch.int64 or counts.numel() < self.total_bins or not counts.is_contiguous():
-            raise ValueError(f"counts must be a contiguous int64 device tensor of {self.total_bins} entries "
-                             "(weighted tables have no structure score)")
+        self._int64_counts(counts, " (weighted tables have no structure score)")
         for name, t in (("alpha", alpha), ("beta", beta)):
-            if t is not None and (t.dtype != torch.float64 or t.numel() < n or not t.is_contiguous()):
-                raise ValueError(f"{name} must be a contiguous fp64 device tensor with one entry per family")
+            if t is not None:
+                flat_tensor(name, t, n, entries="with one entry per family")
         scores = torch.empty(n, dtype=torch.float64, device=counts.device)
         observed = torch.empty(n, dtype=torch.int64, device=counts.device) if want_observed else None
         N.check(L.pgm_fit_score(self._h, N.ptr(counts), int(mode), N.ptr(alpha), N.ptr(beta), N.ptr(scores),
@@ -163,9 +136,7 @@ class FitPlan:
 
         L = N.lib()
         n = len(self.families)
-        if counts.dtype != torch.int64 or counts.numel() < self.total_bins or not counts.is_contiguous():
-            raise ValueError(f"counts must be a contiguous int64 device tensor of {self.total_bins} entries "
-                             "(weighted tables have no CI test)")
+        self._int64_counts(counts, " (weighted tables have no CI test)")
         stat = torch.empty(n, dtype=torch.float64, device=counts.device)
         dof = torch.empty(n, dtype=torch.int64, device=counts.device)
         pvalue = torch.empty(n, dtype=torch.float64, device=counts.device)
@@ -179,8 +150,7 @@ class FitPlan:
         import torch
 
         L = N.lib()
-        if counts.dtype != torch.int64 or counts.numel() < self.total_bins or not counts.is_contiguous():
-            raise ValueError(f"counts must be a contiguous int64 device tensor of {self.total_bins} entries")
+        self._int64_counts(counts)
         out = torch.empty(len(self.families), dtype=torch.int64, device=counts.device)
         N.check(L.pgm_fit_states_observed(self._h, N.ptr(counts), N.ptr(out), N.stream_handle()), "fit_states_observed")
         return out

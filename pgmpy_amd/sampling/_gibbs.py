@@ -10,17 +10,20 @@ import ctypes
 import numpy as np
 
 from .. import _native as N
-from ._sample import MASK64, family_array
+from .._plan import MASK64, Plan, codes_window, family_array, flat_tensor
 
 LDS, GLOBAL = N.GIBBS_LDS, N.GIBBS_GLOBAL
 PATH_NAMES = {LDS: "LDS", GLOBAL: "GLOBAL"}
 MAX_SWEEP = (1 << 32) - 1
 
 
-class GibbsPlan:
+class GibbsPlan(Plan):
+    _destroy = "pgm_gibbs_plan_destroy"
+
     def __init__(self, factors, card):
         L = N.load_library()  # building and inspecting a plan needs no device
         self.factors, fams = family_array(factors)
+        self.families = self.factors  # table(): a factor's [first column, the others] view
         self.card = [int(k) for k in card]
         self.n_cols = len(self.card)
         self._h = ctypes.c_void_p()
@@ -40,15 +43,6 @@ class GibbsPlan:
                          for c in range(self.n_cols)]
         self.total_entries = int(self.info.total_entries)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                N.load_library().pgm_gibbs_plan_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
     def launch_info(self, n_chains, offsets=None, sizes=None, inc_off=None, inc=None):
         """GibbsInfo of a launch with n_chains chains (pgm_gibbs_plan_info; no device)."""
         info = N.GibbsInfo()
@@ -56,18 +50,10 @@ class GibbsPlan:
                                                      inc), "gibbs_plan_info")
         return info
 
-    def _window(self, codes, n_chains, row0):
-        import torch
-
-        if codes.dtype != torch.uint8 or codes.dim() != 2 or not codes.is_contiguous():
-            raise ValueError("codes must be a contiguous [n_cols, ld] uint8 device tensor")
-        n_cols, ld = int(codes.shape[0]), int(codes.shape[1])
-        return n_cols, ld, (ld - row0 if n_chains is None else int(n_chains))
-
     def start(self, codes, n_chains=None, row0=0, first_chain=0, seed=0):
         """Column c of every chain becomes floor(u * card[c]) from the sweep-0 uniform of (seed, chain, c)."""
         L = N.lib()
-        n_cols, ld, n_chains = self._window(codes, n_chains, row0)
+        n_cols, ld, n_chains = codes_window(codes, n_chains, row0)
         N.check(L.pgm_gibbs_start(self._h, N.ptr(codes), n_cols, ld, int(row0), n_chains, int(first_chain),
                                   int(seed) & MASK64, N.stream_handle()), "gibbs_start")
         return codes
@@ -84,10 +70,9 @@ class GibbsPlan:
         import torch
 
         L = N.lib()
-        n_cols, ld, n_chains = self._window(codes, n_chains, row0)
+        n_cols, ld, n_chains = codes_window(codes, n_chains, row0)
         n_sweeps = int(n_sweeps)
-        if values.dtype != torch.float64 or values.numel() < self.total_entries or not values.is_contiguous():
-            raise ValueError(f"values must be a contiguous fp64 device tensor of {self.total_entries} entries")
+        flat_tensor("values", values, self.total_entries)
         ld_trace = 0
         if trace is not None:
             if trace.dtype != torch.uint8 or trace.dim() != 2 or trace.shape[0] != n_cols or not trace.is_contiguous():

@@ -169,8 +169,8 @@ static int test_argument_checks() {
   const int64_t huge = (int64_t)kFitRowsPerBlock * ((int64_t)INT32_MAX + 1);  // more workgroups than one launch takes
   CHECK(fit_count_check(&h, codes, 3, huge, 0, huge, tables, &blocks) == PGM_EINVAL);
   // four rows per lane only where every column's dword loads are aligned
-  CHECK(fit_count_vec4(codes, 100, 0) && fit_count_vec4(codes, 4096, 132) && fit_count_vec4(codes + 4, 8, 4));
-  CHECK(!fit_count_vec4(codes, 101, 0) && !fit_count_vec4(codes, 100, 131) && !fit_count_vec4(codes + 2, 100, 0));
+  CHECK(codes_vec4(codes, 100, 0) && codes_vec4(codes, 4096, 132) && codes_vec4(codes + 4, 8, 4));
+  CHECK(!codes_vec4(codes, 101, 0) && !codes_vec4(codes, 100, 131) && !codes_vec4(codes + 2, 100, 0));
   const double *values = (const double *)0x30000;
   CHECK(fit_finish_check(&h, tables, PGM_FIT_MLE, values) == PGM_OK);
   CHECK(fit_finish_check(&h, tables, PGM_FIT_BAYES | PGM_FIT_WEIGHTED, values) == PGM_OK);

@@ -192,8 +192,8 @@ static int test_argument_checks() {
   const int64_t huge = (int64_t)kSampleRowsPerBlock * ((int64_t)INT32_MAX + 1);
   CHECK(sample_forward_check(&h, values, cdf, nullptr, codes, 3, huge, 0, huge, 0, nullptr, &blocks) == PGM_EINVAL);
   // four rows per lane only where every column's dwords are aligned
-  CHECK(sample_vec4(codes, 100, 0) && sample_vec4(codes, 4096, 132) && sample_vec4(codes + 4, 8, 4));
-  CHECK(!sample_vec4(codes, 101, 0) && !sample_vec4(codes, 100, 131) && !sample_vec4(codes + 2, 100, 0));
+  CHECK(codes_vec4(codes, 100, 0) && codes_vec4(codes, 4096, 132) && codes_vec4(codes + 4, 8, 4));
+  CHECK(!codes_vec4(codes, 101, 0) && !codes_vec4(codes, 100, 131) && !codes_vec4(codes + 2, 100, 0));
   CHECK(sample_cdf_check(&h, values, (double *)cdf) == PGM_OK);
   CHECK(sample_cdf_check(nullptr, values, cdf) == PGM_EINVAL && g_last_err == "sample_cdf: null plan");
   CHECK(sample_cdf_check(&h, nullptr, cdf) == PGM_EINVAL && g_last_err == "sample_cdf: null values");
