@@ -24,7 +24,8 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmgibbs.hip",      # Gibbs sampling: the fused sweep kernel, its C-ABI
     "pgmgibbs_plan.cpp",  # Gibbs sampling: factor validation, incidence lists, argument checks (host only)
     "pgmdq.cpp",         # direct AQL dispatch (host code, HSA runtime)
-    "pgmpm.cpp",         # plan-specialised batched-BP steps (host code, hipRTC)
+    "pgmpm.cpp",         # plan-specialised batched-BP steps: hipRTC, code-object cache, bound launches (host code)
+    "pgmpm_gen.cpp",     # plan-specialised batched-BP steps: planner + generators of the specialised sources (host only)
     "pgmhost.cpp",       # DataFrame ingestion helpers (host threads only)
 )]
 INC = os.path.join(ROOT, "include")

@@ -1,5 +1,5 @@
-// pgm_hip_common.h — what the HIP units (pgmhip.hip, pgmrows.hip, pgmfit.hip, pgmsample.hip, pgmgibbs.hip)
-// share: the HIP error check of a C-ABI entry point and the stream cast; and for the plan handles of the
+// pgm_hip_common.h — what the HIP units (pgmhip.hip, pgmrows.hip, pgmfit.hip, pgmsample.hip, pgmgibbs.hip,
+// pgmpm.cpp) share: the HIP error check of a C-ABI entry point and the stream cast; and for the plan handles of the
 // last three the HIP side of pgm_plan_dev.h and the flagged launch.  The one error string lives in
 // pgmhip.hip (pgmi_failf).
 #pragma once

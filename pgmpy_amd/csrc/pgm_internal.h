@@ -1,6 +1,6 @@
 // pgm_internal.h — private interface between pgmhip.hip / pgmrows.hip (kernels, C-ABI), pgmdq.cpp (direct AQL
-// dispatch) and pgmpm.cpp (plan-specialised batched-BP steps).  Not part of the C-ABI of
-// include/pgmhip.h.
+// dispatch), pgmpm.cpp (plan-specialised batched-BP steps: hipRTC, bound launches) and pgmpm_gen.cpp (their
+// planner and source generators, host only).  Not part of the C-ABI of include/pgmhip.h.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -39,6 +39,12 @@ int pgmi_failf(int code, const char *fmt, ...);  // printf-style pgmi_fail
 struct FDiv {
   uint32_t d, m, s;
 };
+inline FDiv make_fdiv(uint32_t d) {
+  uint32_t l = 0;
+  while ((1ull << l) < d) ++l;
+  uint64_t m = ((1ull << 32) * ((1ull << l) - d)) / d + 1;
+  return FDiv{d, (uint32_t)m, l};
+}
 
 // a planned contraction (pgmhip.hip plan_contract; the generic kernels read it, pgmpm.cpp compiles a
 // batch of them into a specialised kernel)
@@ -92,12 +98,15 @@ struct pgmi_cs_job {
   const double *ops[MOPS];
 };
 
-// a plan-specialised kernel for a batch of contraction jobs (pgmpm.cpp): one_wg = 0: one launch of
+// a plan-specialised kernel for a batch of contraction jobs (pgmpm.cpp; its source: pgmpm_gen.cpp): one_wg = 0: one launch of
 // the batch's blocks (one level); 1: the single-workgroup levelled form (level_off: first block of
 // each level + the end).  *bound = NULL when a job is not one it takes (the generic kernel runs).
 int pgmi_cs_bind(const pgmi_cs_job *jobs, int n, const uint32_t *level_off, int n_levels, int one_wg, void **bound);
 
-// the fused product + marginal step's plan (pgmhip.hip plans it and runs the generic kernels;
+#define PMAX PGM_PRODN_MAX_OPS  // operands of an n-ary product
+#define RMAX_MARG 512           // reduced entries of a fused step (the generic kernel's LDS offset tables)
+
+// the fused product + marginal step's plan (pgmpm_gen.cpp plans it, pgmhip.hip runs the generic kernels,
 // pgmpm.cpp compiles it into specialised kernels)
 struct ProdMK {
   int32_t n_ops, nk, nr, n_red;  // nk: kept outer dims + the row dim (last); nr: reduced dims
@@ -113,9 +122,10 @@ struct ProdMK {
   const double *ops[MOPS];
 };
 
-struct dim3;
+// 1 = the fused kernel applies (k filled; grid: the generic kernel's x, y, z), 0 = it does not (use
+// product_n + contract), < 0 error
 int pgmi_plan_product_marg(const pgm_productn_desc *d, const double *const *ops, const double *C,
-                           const int64_t *marg_s, const double *M, ProdMK &k, dim3 &grid);
+                           const int64_t *marg_s, const double *M, ProdMK &k, uint32_t grid[3]);
 void pgmi_appendf(std::string &o, const char *fmt, ...);  // printf into a growing source string
 void pgmi_stale_probe(const char *fn);                   // PGM_STALE_PROBE=1 debugging aid
 // gfx950 code object of a generated kernel source: the on-disk cache, else hipRTC (then cached)

@@ -53,13 +53,8 @@ void pgmi_stale_probe(const char *fn) {
 }
 
 // ----------------------------------------------------------------------------- fast division
-// n / d for n < 2^31 with one mul-hi and one shift (Granlund-Montgomery round-up method).
-static FDiv make_fdiv(uint32_t d) {
-  uint32_t l = 0;
-  while ((1ull << l) < d) ++l;
-  uint64_t m = ((1ull << 32) * ((1ull << l) - d)) / d + 1;
-  return FDiv{d, (uint32_t)m, l};
-}
+// n / d for n < 2^31 with one mul-hi and one shift (Granlund-Montgomery round-up method; make_fdiv:
+// pgm_internal.h).
 
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FDiv &f) {
   uint32_t t = __umulhi(n, f.m);
@@ -756,7 +751,6 @@ static void launch_contract_c(int red, const ContractLaunch &L, const double *A,
 }
 
 // ----------------------------------------------------------------------------- n-ary product
-#define PMAX PGM_PRODN_MAX_OPS
 struct ProdNK {
   int32_t n_ops, nk;
   int32_t kind[PMAX];
@@ -972,7 +966,6 @@ __global__ __launch_bounds__(256) void k_productn_rows2(const ProdNK p, double *
 // k_productn_rows2.  A block owns one kept outer index (separator state); the reduction (the
 // clique's other states) is walked from an LDS offset table with the next entry's operands in
 // flight while the current product is stored and accumulated.
-#define RMAX_MARG 512
 
 template <int NOPS>
 __device__ __forceinline__ double prodm_combine(const ProdMK &p, const double (&v)[NOPS]) {
@@ -1106,124 +1099,7 @@ __global__ __launch_bounds__(256) void k_productn_marg_jx(const ProdMK p, double
   }
 }
 
-// 1 = the fused kernel applies (k filled), 0 = it does not (use product_n + contract), < 0 error
-int pgmi_plan_product_marg(const pgm_productn_desc *d, const double *const *ops, const double *C,
-                             const int64_t *marg_s, const double *M, ProdMK &k, dim3 &grid) {
-  if (!d || !ops || !marg_s || !M) return fail(PGM_EINVAL, "product_n_marginal: null argument");
-  if (d->n_ops < 1 || d->n_ops > PMAX || d->n_keep < 1 || d->n_keep > PGM_MAX_DIMS)
-    return fail(PGM_EINVAL, "product_n_marginal: n_ops %d / n_keep %d out of range", d->n_ops, d->n_keep);
-  if (d->n_ops > MOPS || d->n_keep < 2) return 0;
-  memset(&k, 0, sizeof k);
-  const int last = d->n_keep - 1;
-  const int64_t NX = d->keep_card[last];
-  if (NX < 64 || NX % 2 || d->keep_sc[last] != 1 || marg_s[last] != 1) return 0;
-  if (((uintptr_t)C & 15) || ((uintptr_t)M & 15)) return 0;
-  k.n_ops = d->n_ops;
-  k.mdiv = -1;
-  for (int t = 0; t < MOPS; ++t) {
-    const bool real = t < d->n_ops;
-    k.ops[t] = real ? ops[t] : ops[0];
-    k.kind[t] = real ? d->op_kind[t] : PGM_PRODN_MUL;
-    if (real && (!ops[t] || d->op_kind[t] < 0 || d->op_kind[t] > PGM_PRODN_MDIV))
-      return fail(PGM_EINVAL, "product_n_marginal: operand %d", t);
-    if (real && d->op_kind[t] == PGM_PRODN_MDIV) {  // a factor of the product, and the marginal's divisor
-      if (k.mdiv >= 0) return fail(PGM_EINVAL, "product_n_marginal: more than one PGM_PRODN_MDIV operand");
-      k.mdiv = t;
-      k.kind[t] = PGM_PRODN_MUL;
-    }
-    const int64_t sx = real ? d->keep_s[t][last] : 0;
-    if (sx != 0 && sx != 1) return 0;
-    if (sx == 1 && ((uintptr_t)ops[t] & 15)) return 0;
-    k.vec[t] = sx == 1;
-  }
-  uint64_t n_outer = 1, n_red = 1;
-  for (int i = 0; i < last; ++i) {
-    const int64_t c = d->keep_card[i];
-    if (c <= 0) return fail(PGM_EINVAL, "product_n_marginal: keep_card[%d] <= 0", i);
-    if (c == 1) continue;
-    const bool kept = marg_s[i] != 0;
-    if (d->keep_sc[i] % 2 || (kept && marg_s[i] % 2)) return 0;
-    for (int t = 0; t < d->n_ops; ++t)
-      if (k.vec[t] && d->keep_s[t][i] % 2) return 0;
-    if (kept) {
-      if (k.nk >= KMAX - 1) return 0;
-      k.kdiv[k.nk] = make_fdiv((uint32_t)c);
-      k.ksc[k.nk] = d->keep_sc[i];
-      k.ksm[k.nk] = marg_s[i];
-      for (int t = 0; t < d->n_ops; ++t) k.ks[t][k.nk] = d->keep_s[t][i];
-      ++k.nk;
-      n_outer *= (uint64_t)c;
-    } else {
-      if (k.nr >= KMAX) return 0;
-      k.rdiv[k.nr] = make_fdiv((uint32_t)c);
-      k.rsc[k.nr] = d->keep_sc[i];
-      for (int t = 0; t < d->n_ops; ++t) k.rs[t][k.nr] = d->keep_s[t][i];
-      ++k.nr;
-      n_red *= (uint64_t)c;
-    }
-  }
-  if (n_red > RMAX_MARG || n_outer >= (1ull << 31)) return 0;
-  // kept-dim order of the block schedule: blocks are dispatched with the LAST kept dim fastest.  A
-  // row-dim operand that lacks a kept dim is read again by every block along that dim, so the dims
-  // lacked by the largest such operands go innermost: the blocks sharing an operand slice then run
-  // back to back and find it in L2 (pathfinder's root: 129-258 MB separator aggregates broadcast over
-  // its other variables).
-  if (k.nk > 1) {
-    double score[KMAX];
-    for (int i = 0; i < k.nk; ++i) {
-      score[i] = 0.0;
-      for (int t = 0; t < d->n_ops; ++t) {
-        if (!k.vec[t] || k.ks[t][i] != 0) continue;
-        double size = 1.0;  // the operand's elements per row
-        for (int q = 0; q < k.nk; ++q)
-          if (k.ks[t][q] != 0) size *= (double)k.kdiv[q].d;
-        for (int r = 0; r < k.nr; ++r)
-          if (k.rs[t][r] != 0) size *= (double)k.rdiv[r].d;
-        score[i] += size;
-      }
-    }
-    int ord[KMAX];
-    for (int i = 0; i < k.nk; ++i) ord[i] = i;
-    std::stable_sort(ord, ord + k.nk, [&](int a, int b) { return score[a] < score[b]; });
-    ProdMK k2 = k;
-    for (int i = 0; i < k.nk; ++i) {
-      const int o = ord[i];
-      k2.kdiv[i] = k.kdiv[o];
-      k2.ksc[i] = k.ksc[o];
-      k2.ksm[i] = k.ksm[o];
-      for (int t = 0; t < MOPS; ++t) k2.ks[t][i] = k.ks[t][o];
-    }
-    k = k2;
-  }
-  for (int t = 0; t < MOPS; ++t) {
-    k.jvar[t] = 0;
-    for (int r = 0; t < d->n_ops && r < k.nr; ++r) k.jvar[t] |= k.rs[t][r] != 0;
-  }
-  if (k.mdiv >= 0 && k.jvar[k.mdiv]) return 0;  // the divisor varies over the summed entries: not this kernel
-  k.kdiv[k.nk] = make_fdiv((uint32_t)NX);  // the row dim, last
-  ++k.nk;
-  k.n_red = (int32_t)n_red;
-  k.n_outer = (uint32_t)n_outer;
-  k.NP = (uint32_t)(NX / 2);
-  const uint64_t xb = (k.NP + 255) / 256;
-  const uint64_t gy = std::min<uint64_t>(n_outer, 65535);
-  // target block count
-  static constexpr uint64_t target = 2048;
-  const uint64_t gx = std::min<uint64_t>(xb, std::max<uint64_t>(1, target / gy));
-  // too few blocks to fill the chip: the two-kernel path (product_n + contract) was faster for a lone
-  // launch below 512 blocks, but inside a levelled schedule it costs a second dependency level.  C4
-  // (r03ae, two runs each): floor 512 / 256 / 128 / 64 -> 0.87-0.88 / 0.92 / 0.95 / 0.85 M
-  // calibrations/s at 1,000 rows, 1.20-1.21 / 1.25 / 1.24-1.25 / 1.24-1.25 M at 4,000.  Once small steps are specialised and merged into their level's launch
-  // (PGM_PM_JIT_MIN 2^14, r03ag) a small fused pass costs no launch of its own: floor 128 -> 32 gives
-  // 1.03 -> 1.09 M at 1,000 rows, 4,000 rows unchanged at 1.29-1.30 M (r03ah); 32 / 8 / 2 -> 1.08 / 1.08
-  // / 1.09-1.10 M (r03ai): no floor by default.
-  static constexpr uint64_t min_blocks = 1;
-  // (also accepting short reductions on 16+ blocks was slower at 1,000 rows, 0.95 -> 0.87 M: each such
-  // pass is a launch of its own, where the two-kernel path's jobs join the level's batch launch; r03af)
-  if (gx * gy < min_blocks) return 0;
-  grid = dim3((unsigned)gx, (unsigned)gy, 1);
-  return 1;
-}
+// its plan: pgmi_plan_product_marg (pgmpm_gen.cpp)
 
 // ----------------------------------------------------------------------------- gather
 // GatherK (a planned per-row evidence gather): pgm_internal.h
@@ -2222,7 +2098,7 @@ int pgm_product_n_marginal_ok(const pgm_productn_desc *d, const double *const *o
                               const int64_t *marg_s, const double *M) {
   STALE_PROBE();
   ProdMK k;
-  dim3 g;
+  uint32_t g[3];
   return pgmi_plan_product_marg(d, ops, C, marg_s, M, k, g) == 1 ? 1 : 0;
 }
 
@@ -2232,7 +2108,7 @@ int pgm_product_n_marginal(const pgm_productn_desc *d, const double *const *ops,
   if (reduce != PGM_RED_SUM && reduce != PGM_RED_MAX)
     return fail(PGM_EINVAL, "product_n_marginal: reduce must be PGM_RED_SUM or PGM_RED_MAX");
   ProdMK k;
-  dim3 g;
+  uint32_t g[3];
   const int r = pgmi_plan_product_marg(d, ops, C, marg_s, M, k, g);
   if (r < 0) return r;
   if (r == 0)
@@ -2244,7 +2120,7 @@ int pgm_product_n_marginal(const pgm_productn_desc *d, const double *const *ops,
   // clique: collect 413 -> 272 us at 4,000 rows, 94 -> 80 us at 1,000, against r02's j-inner kernel)
   const int XI = k.NP >= 1024 ? 2 : 1;
   const uint64_t gxj = (k.NP + 256ull * XI - 1) / (256ull * XI);
-  const dim3 gj((unsigned)gxj, g.y, 1);
+  const dim3 gj((unsigned)gxj, g[1], 1);
 #define PGM_MARGJ_NOPS(NO, XX)                                                                               \
   if (reduce == PGM_RED_SUM) hipLaunchKernelGGL((k_productn_marg_jx<NO, PGM_RED_SUM, XX>), gj, dim3(256), 0, s, k, C, M); \
   else hipLaunchKernelGGL((k_productn_marg_jx<NO, PGM_RED_MAX, XX>), gj, dim3(256), 0, s, k, C, M);
