@@ -869,6 +869,65 @@ int pgm_fit_estep(void *plan, const int32_t *latent_cols, int32_t n_latent, cons
                   const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
                   double *tables, double *loglik, void *stream);
 
+/* ---------------------------------------------------------------- per-row log-probability
+ * (an extension of ABI 25.)  The log-density of complete rows under a Bayesian network, for the reference's
+ * BayesianModelProbability (metrics/bn_inference.py:23-148: per node, np.unique(axis=0) over the parent
+ * codes and a Python loop over the rows), in one streaming pass over the column-major uint8 codes that
+ * pgm_fit_count reads and pgm_sample_forward / pgm_gibbs_sweep write.
+ *
+ * plan is an ordinary fit plan: one family per node.  values and logv (device, fp64) have the plan's flat
+ * layout, so values may be the buffer pgm_fit_finish wrote.
+ *
+ * pgm_fit_log_values: logv[i] = log(values[i]) over the flat layout in one launch; values[i] == 0 gives
+ * -inf.  logv may alias values.  A negative or NaN value returns PGM_EINVAL (a device flag read back after
+ * the launch: the call synchronises the stream).
+ *
+ * pgm_fit_logprob covers the rows [row0, row0 + n_rows) of codes[col * ld + row].  For such a row
+ *   logp[row] = sum over the families f, in plan order, of
+ *               logv[offsets[f] + x_node * stride_0 + sum_v x_parent_v * stride_v]
+ * in fp64, starting from +0.0, each addition separately rounded (logp: optional, device, fp64, ld entries
+ * indexed by buffer row; rows outside the window are not touched).  A row's value depends on its own codes
+ * and logv only: its bits are the same whatever the launch geometry, the alignment path, row0, ld or the
+ * other rows.  A row with a zero-probability cell is -inf.
+ *
+ * A row that holds PGM_EV_MISSING in any column a family reads is skipped: its logp is NaN and it is left
+ * out of total.  A code that is neither PGM_EV_MISSING nor a state never indexes a table: its row is skipped
+ * in the same way and the call returns PGM_EINDEX, through the device flag of pgm_fit_count (so the call
+ * synchronises the stream).  n_skipped (optional, device, one int64) receives the number of skipped rows.
+ *
+ * total (optional, device, one fp64) receives the sum of the window's row values that are not skipped,
+ * added without floating-point atomics in an order that is a function of n_rows alone.  With
+ * R = PGM_LOGP_ROWS_PER_BLOCK and B = PGM_LOGP_BLOCK: workgroup b takes the window's rows [b R, (b + 1) R),
+ * a skipped row or a row past the window counting +0.0; work-item t adds the rows t, t + B, t + 2 B, ... of
+ * the workgroup in that order, a tree adds the work-items' sums (step w = B / 2, B / 4 .. 1: item t < w
+ * adds item t + w), giving one partial per workgroup; a second launch of one workgroup adds the partials
+ * the same way (work-item t takes the partials t, t + B, ... in index order, then the tree).  So total is
+ * bit-identical from run to run and between the four-rows-per-lane and one-row paths.  The partials belong
+ * to the handle: calls on one plan must not overlap, and a call covers at most PGM_LOGP_MAX_BLOCKS * R rows.
+ *
+ * Every argument is checked on the host before any HIP call: PGM_EINVAL for a null plan / values / logv /
+ * codes, an fp64 or int64 pointer that is not 8-byte aligned, n_cols smaller than the plan's columns,
+ * negative counts, a window outside ld, and more rows than one call covers.  n_rows == 0 is PGM_OK with
+ * total = 0 and n_skipped = 0 and launches no kernel.  pgm_fit_logprob_info needs no device. */
+#define PGM_LOGP_BLOCK 256            /* work-items per workgroup */
+#define PGM_LOGP_ROWS_PER_BLOCK 1024  /* consecutive rows one workgroup takes: one dword of codes per lane and column */
+#define PGM_LOGP_MAX_BLOCKS 65536     /* block partials a handle keeps: 64 Mi rows per call */
+typedef struct {
+  int32_t block;          /* work-items per workgroup */
+  int32_t rows_per_block; /* rows one workgroup takes */
+  int32_t vec4;           /* the launch takes the four-rows-per-lane path (codes, ld, row0 multiples of 4) */
+  int32_t n_families;
+  int64_t n_partials;     /* block partials of a launch over n_rows rows = its workgroups */
+} pgm_logp_info_t;
+/* launch geometry and the kernel path of a call with these (codes, ld, row0, n_rows): only the alignment of
+ * the pointer matters */
+int pgm_fit_logprob_info(void *plan, const void *codes, int64_t ld, int64_t row0, int64_t n_rows,
+                         pgm_logp_info_t *info);
+int pgm_fit_log_values(void *plan, const double *values, double *logv, void *stream);
+int pgm_fit_logprob(void *plan, const double *logv, const uint8_t *codes, int32_t n_cols, int64_t ld,
+                    int64_t row0, int64_t n_rows, double *logp, double *total, int64_t *n_skipped,
+                    void *stream);
+
 /* ---------------------------------------------------------------- forward sampling
  * BayesianModelSampling.forward_sample / likelihood_weighted_sample / rejection_sample and
  * DiscreteBayesianNetwork.simulate (sampling/Sampling.py:30-406, DiscreteBayesianNetwork.py:1400-1704)

@@ -213,6 +213,15 @@ class EmInfo(ctypes.Structure):
                 ("lds_bytes", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class LogpInfo(ctypes.Structure):
+    """pgm_logp_info_t: launch geometry and kernel path of a pgm_fit_logprob call (host-only query)."""
+    _fields_ = [("block", ctypes.c_int32), ("rows_per_block", ctypes.c_int32), ("vec4", ctypes.c_int32),
+                ("n_families", ctypes.c_int32), ("n_partials", ctypes.c_int64)]
+
+
+LOGP_BLOCK, LOGP_ROWS_PER_BLOCK, LOGP_MAX_BLOCKS = 256, 1024, 65536  # PGM_LOGP_*
+
+
 class SampleInfo(ctypes.Structure):
     """pgm_sample_info_t: layout, launch geometry and kernel path of a pgm_sample plan (host-only query)."""
     _fields_ = [("n_families", ctypes.c_int32), ("n_cols", ctypes.c_int32), ("block", ctypes.c_int32),
@@ -417,6 +426,11 @@ _SIGS = {
     "pgm_fit_estep_info": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(EmInfo)], ctypes.c_int),
     "pgm_fit_estep": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_int64,
                        ctypes.c_int64, ctypes.c_int64, _P, _P, _P], ctypes.c_int),
+    "pgm_fit_logprob_info": ([_P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(LogpInfo)],
+                             ctypes.c_int),
+    "pgm_fit_log_values": ([_P, _P, _P, _P], ctypes.c_int),
+    "pgm_fit_logprob": ([_P, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P],
+                        ctypes.c_int),
     "pgm_sample_plan_create": ([ctypes.POINTER(FitFamily), ctypes.c_int32, ctypes.POINTER(_P)], ctypes.c_int),
     "pgm_sample_plan_destroy": ([_P], ctypes.c_int),
     "pgm_sample_plan_info": ([_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, ctypes.POINTER(SampleInfo),

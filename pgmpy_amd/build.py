@@ -19,6 +19,7 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmrows_plan.cpp",  # fused row plan: plan compiler + generator of the specialised source (host only)
     "pgmfit.hip",        # parameter learning: family-count + CPD finishing kernels, their C-ABI
     "pgmfit_plan.cpp",   # parameter learning: family validation, table layout, argument checks (host only)
+    "pgmlogp.hip",       # per-row log-probability: log-table + row-sum kernels, their C-ABI (on the fit plan)
     "pgmsample.hip",     # forward sampling: running-sum + sampling kernels, their C-ABI
     "pgmsample_plan.cpp",  # forward sampling: family validation, argument checks, host-only queries (host only)
     "pgmgibbs.hip",      # Gibbs sampling: the fused sweep kernel, its C-ABI

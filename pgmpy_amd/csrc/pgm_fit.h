@@ -1,7 +1,7 @@
 // pgm_fit.h — private interface between the two units of parameter learning: pgmfit_plan.cpp (host only:
 // family validation, table layout, grouping of families per workgroup, the argument checks of the
-// pgm_fit_* entry points) and pgmfit.hip (the counting and finishing kernels, the device side of the
-// handle, the launches); at the end, the host checks the sampling units share with it.  Not part of
+// pgm_fit_* entry points), pgmfit.hip (the counting and finishing kernels, the device side of the
+// handle, the launches) and pgmlogp.hip (the per-row log-probability kernels); at the end, the host checks the sampling units share with it.  Not part of
 // include/pgmhip.h.
 #pragma once
 #include <cstdint>
@@ -36,6 +36,14 @@ static constexpr int kScoreSumBlock = 64;
 // Small tests without Z (one stratum) are packed kCiChunk to a workgroup instead of one workgroup each.
 static constexpr int kCiChunk = PGM_CI_CHUNK;
 static constexpr int kCiSmall = 16;
+// The log-probability kernel (pgm_fit_logprob): a workgroup of kLogpBlock work-items takes kLogpRowsPerBlock
+// consecutive rows, one dword of four codes per lane and column on the four-rows-per-lane path, and leaves
+// one fp64 partial and one int32 count of skipped rows; the second launch adds the partials with one
+// workgroup of kLogpBlock.  The handle keeps kLogpMaxBlocks partials (768 KiB), built by the first call.
+static constexpr int kLogpBlock = PGM_LOGP_BLOCK;
+static constexpr int kLogpRowsPerBlock = PGM_LOGP_ROWS_PER_BLOCK;
+static constexpr int kLogpMaxBlocks = PGM_LOGP_MAX_BLOCKS;
+static_assert(kLogpRowsPerBlock == 4 * kLogpBlock, "a lane owns four rows of its workgroup");
 
 // one family as the kernels read it (device memory; every field is workgroup-uniform: scalar loads)
 struct FitFam {
@@ -87,7 +95,15 @@ struct PGM_FIT_LOCAL FitHandle {
   const int32_t *d_ci_single = nullptr;
   double *d_ci_part = nullptr;
   int64_t *d_ci_dof = nullptr;
+  // the log-probability stage: one fp64 partial + one int32 count of skipped rows per workgroup
+  double *d_logp_part = nullptr;
+  int32_t *d_logp_skip = nullptr;
 };
+
+// The descriptors on the current device, and with a stage what only the score / CI / log-probability
+// launches need (pgmfit.hip; pgmlogp.hip shares it).
+enum { kFitNoStage = -1, kFitScore = 0, kFitCi = 1, kFitLogp = 2 };
+PGM_FIT_LOCAL int fit_use(FitHandle *h, int stage = kFitNoStage);
 
 // validate the families and lay the tables out; PGM_OK, or PGM_EINVAL with pgm_last_error set
 PGM_FIT_LOCAL int fit_plan_build(const pgm_fit_family *fams, int32_t n, FitPlan &out);
@@ -123,6 +139,12 @@ PGM_FIT_LOCAL int fit_estep_check(const FitHandle *h, const int32_t *latent_cols
                                   const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
                                   const double *tables, EmSpec *spec, int64_t *blocks);
 PGM_FIT_LOCAL int fit_states_check(const FitHandle *h, const int64_t *counts, const int64_t *n_states);
+// the argument checks of pgm_fit_log_values (no HIP call); *blocks: workgroups of the launch
+PGM_FIT_LOCAL int fit_log_values_check(const FitHandle *h, const double *values, const double *logv, int64_t *blocks);
+// the argument checks of pgm_fit_logprob (no HIP call); *blocks: workgroups of the row launch = block partials
+PGM_FIT_LOCAL int fit_logprob_check(const FitHandle *h, const double *logv, const uint8_t *codes, int32_t n_cols,
+                                    int64_t ld, int64_t row0, int64_t n_rows, const double *logp, const double *total,
+                                    const int64_t *n_skipped, int64_t *blocks);
 
 // ---------------------------------------------------------------------------- shared with the other plan units
 // (pgmsample_plan.cpp, pgmgibbs_plan.cpp and their .hip units; defined in pgmfit_plan.cpp, which they link)

@@ -56,7 +56,7 @@ struct Slots {
 // on the owned list from the moment it exists, so release() reaches it whatever happened since.
 class PlanDev {
  public:
-  static constexpr int kStages = 2;
+  static constexpr int kStages = 3;
 
   // the base, and stage k of it when k >= 0, on the current device; 0, or the failed operation's status
   int use(const DevOps &ops, Slots base, int k = -1, Slots stage = Slots()) {
@@ -140,7 +140,7 @@ class PlanDev {
   std::mutex mu_;
   int device_ = -1;
   int32_t *flag_ = nullptr;
-  bool built_[kStages] = {false, false};
+  bool built_[kStages] = {};
   std::vector<Owned> owned_;
 };
 

@@ -612,10 +612,9 @@ __global__ __launch_bounds__(kCiChunk) void k_fit_ci_finish(const FitFam *__rest
 
 // ---------------------------------------------------------------------------- the handle's device side
 // The descriptors on the current device, and with a stage what only the score / CI launches need: the work
-// lists, and per chunk one fp64 partial and one int64 count (part_obs / dof).
-enum { kFitNoStage = -1, kFitScore = 0, kFitCi = 1 };
-
-static int fit_use(FitHandle *h, int stage = kFitNoStage) {
+// lists, and per chunk one fp64 partial and one int64 count (part_obs / dof); the log-probability stage
+// (pgmlogp.hip) is its block partials.
+int fit_use(FitHandle *h, int stage) {
   using pgmdev::scratch;
   using pgmdev::upload;
   const FitPlan &p = h->p;
@@ -632,6 +631,10 @@ static int fit_use(FitHandle *h, int stage = kFitNoStage) {
                                upload(h->d_ci_single, p.ci_single), scratch(h->d_ci_part, chunks),
                                scratch(h->d_ci_dof, chunks)};
     return h->dev.use(kHipDevOps, base, stage, ci);
+  }
+  if (stage == kFitLogp) {
+    const pgmdev::Slot logp[] = {scratch(h->d_logp_part, (size_t)kLogpMaxBlocks), scratch(h->d_logp_skip, (size_t)kLogpMaxBlocks)};
+    return h->dev.use(kHipDevOps, base, stage, logp);
   }
   return h->dev.use(kHipDevOps, base);
 }

@@ -251,7 +251,56 @@ int fit_states_check(const FitHandle *h, const int64_t *counts, const int64_t *n
   return PGM_OK;
 }
 
+static bool aligned8(const void *p) { return ((uintptr_t)p & 7) == 0; }
+
+int fit_log_values_check(const FitHandle *h, const double *values, const double *logv, int64_t *blocks) {
+  if (!h) return pgmi_fail(PGM_EINVAL, "fit_log_values: null plan");
+  if (!values) return pgmi_fail(PGM_EINVAL, "fit_log_values: null values");
+  if (!logv) return pgmi_fail(PGM_EINVAL, "fit_log_values: null logv");
+  if (!aligned8(values) || !aligned8(logv))
+    return pgmi_fail(PGM_EINVAL, "fit_log_values: values and logv must be 8-byte aligned");
+  const int64_t nb = (h->p.total_bins + kLogpBlock - 1) / kLogpBlock;
+  if (nb > INT32_MAX) return pgmi_fail(PGM_EINVAL, "fit_log_values: too many table entries for one launch");
+  if (blocks) *blocks = nb;
+  return PGM_OK;
+}
+
+int fit_logprob_check(const FitHandle *h, const double *logv, const uint8_t *codes, int32_t n_cols, int64_t ld,
+                      int64_t row0, int64_t n_rows, const double *logp, const double *total, const int64_t *n_skipped,
+                      int64_t *blocks) {
+  if (!h) return pgmi_fail(PGM_EINVAL, "fit_logprob: null plan");
+  if (!logv) return pgmi_fail(PGM_EINVAL, "fit_logprob: null logv");
+  if (!codes) return pgmi_fail(PGM_EINVAL, "fit_logprob: null codes");
+  if (!aligned8(logv) || !aligned8(logp) || !aligned8(total) || !aligned8(n_skipped))
+    return pgmi_fail(PGM_EINVAL, "fit_logprob: logv, logp, total and n_skipped must be 8-byte aligned");
+  const int st = window_check("fit_logprob", "rows", ld, row0, n_rows, 0);
+  if (st != PGM_OK) return st;
+  if (n_cols < h->p.n_cols)
+    return pgmi_failf(PGM_EINVAL, "fit_logprob: the plan reads column %d, codes has %d columns", h->p.n_cols - 1, n_cols);
+  const int64_t nb = (n_rows + kLogpRowsPerBlock - 1) / kLogpRowsPerBlock;
+  if (nb > kLogpMaxBlocks)
+    return pgmi_failf(PGM_EINVAL, "fit_logprob: %lld workgroups, a call covers %d (score the rows in several calls)",
+                      (long long)nb, kLogpMaxBlocks);
+  if (blocks) *blocks = nb;
+  return PGM_OK;
+}
+
 extern "C" {
+
+int pgm_fit_logprob_info(void *plan, const void *codes, int64_t ld, int64_t row0, int64_t n_rows,
+                         pgm_logp_info_t *info) {
+  if (!plan) return pgmi_fail(PGM_EINVAL, "fit_logprob_info: null plan");
+  if (!info) return pgmi_fail(PGM_EINVAL, "fit_logprob_info: null info");
+  const int st = window_check("fit_logprob_info", "rows", ld, row0, n_rows, 0);
+  if (st != PGM_OK) return st;
+  memset(info, 0, sizeof *info);
+  info->block = kLogpBlock;
+  info->rows_per_block = kLogpRowsPerBlock;
+  info->vec4 = codes && codes_vec4(codes, ld, row0) ? 1 : 0;
+  info->n_families = (int32_t)static_cast<const FitHandle *>(plan)->p.fams.size();
+  info->n_partials = (n_rows + kLogpRowsPerBlock - 1) / kLogpRowsPerBlock;
+  return PGM_OK;
+}
 
 int pgm_fit_plan_create(const pgm_fit_family *fams, int32_t n, void **plan) {
   return plan_create<FitHandle>("fit_plan_create", plan, [&](FitPlan &p) { return fit_plan_build(fams, n, p); });

@@ -109,6 +109,54 @@ class FitPlan(Plan):
                 "fit_finish")
         return out
 
+    def logprob_info(self, codes_ptr, ld, row0=0, n_rows=None):
+        """pgm_logp_info_t of a logprob call over the rows [row0, row0 + n_rows) of codes at address
+        `codes_ptr` with `ld` rows per column: block, rows per block, whether the launch takes the
+        four-rows-per-lane path, and the number of block partials.  Needs no device."""
+        L = N.load_library()
+        info = N.LogpInfo()
+        n_rows = int(ld) - int(row0) if n_rows is None else int(n_rows)
+        N.check(L.pgm_fit_logprob_info(self._h, ctypes.c_void_p(codes_ptr), int(ld), int(row0), n_rows,
+                                       ctypes.byref(info)), "fit_logprob_info")
+        return info
+
+    def log_values(self, values, out=None):
+        """log(values) over the flat layout in one launch (pgm_fit_log_values): 0 gives -inf; `out` may be
+        `values` itself.  Raises ValueError when a value is negative or NaN."""
+        import torch
+
+        L = N.lib()
+        flat_tensor("values", values, self.total_bins)
+        if out is None:
+            out = torch.empty(self.total_bins, dtype=torch.float64, device=values.device)
+        else:
+            flat_tensor("out", out, self.total_bins)
+        N.check(L.pgm_fit_log_values(self._h, N.ptr(values), N.ptr(out), N.stream_handle()), "fit_log_values")
+        return out
+
+    def logprob(self, logv, codes, n_rows=None, row0=0, logp=None, total=False):
+        """The log-probability of the rows [row0, row0 + n_rows) of the device codes [n_cols, ld] (uint8)
+        under the log tables `logv` (log_values' flat fp64 device tensor), one family per node
+        (pgm_fit_logprob).  Returns (logp, total, n_skipped): `logp` the fp64 device tensor [ld] indexed by
+        buffer row (a new one filled with NaN when None; rows outside the window are not touched), `total`
+        a one-element fp64 device tensor with the sum over the rows that are not skipped (None unless
+        asked for), n_skipped the number of rows that hold 255 in a column a family reads (their logp is
+        NaN), downloaded with the status.  Raises IndexError when a code is neither 255 nor a state."""
+        import torch
+
+        L = N.lib()
+        n_cols, ld, n_rows = codes_window(codes, n_rows, row0)
+        flat_tensor("logv", logv, self.total_bins)
+        if logp is None:
+            logp = torch.full((ld,), float("nan"), dtype=torch.float64, device=codes.device)
+        else:
+            flat_tensor("logp", logp, ld, entries="with one entry per row of codes")
+        tot = torch.empty(1, dtype=torch.float64, device=codes.device) if total else None
+        skipped = torch.empty(1, dtype=torch.int64, device=codes.device)
+        N.check(L.pgm_fit_logprob(self._h, N.ptr(logv), N.ptr(codes), n_cols, ld, int(row0), n_rows, N.ptr(logp),
+                                  N.ptr(tot), N.ptr(skipped), N.stream_handle()), "fit_logprob")
+        return logp, tot, int(skipped.item())
+
     def score(self, counts, mode, alpha=None, beta=None, want_observed=False):
         """The data-dependent sum of a structure score per family (pgm_fit_score) from the int64 count
         tables: `mode` is N.SCORE_BD (alpha, beta: fp64 device tensors, one entry per family) or

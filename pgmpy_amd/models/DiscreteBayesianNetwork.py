@@ -235,6 +235,10 @@ class DiscreteBayesianNetwork(nx.DiGraph):
         starts = variables if isinstance(variables, (list, tuple, set)) else [variables]
         return active_trails(self, list(starts), list(observed), include_latents=include_latents)
 
+    def is_dconnected(self, start, end, observed=None, include_latents=False):
+        """Whether an active trail joins `start` and `end` given `observed` (DAG.py is_dconnected)."""
+        return end in self.active_trail_nodes(start, observed, include_latents=include_latents)[start]
+
     def get_ancestral_graph(self, nodes):
         anc = self._get_ancestors_of(list(nodes))
         g = DiscreteBayesianNetwork()
