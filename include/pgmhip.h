@@ -990,6 +990,78 @@ int pgm_sample_forward(void *plan, const double *values, const double *cdf, cons
                        int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, int64_t first_row, uint64_t seed,
                        double *weights, const double *uniforms, void *stream);
 
+/* ---------------------------------------------------------------- likelihood-weighted posteriors
+ * (an extension of ABI 25.)  The reference's ApproxInference (inference/ApproxInference.py) for a batch of
+ * evidence rows: every row draws n_samples samples, weights them and adds them to its own histograms in
+ * one fused kernel.  No sampled code is written to memory.
+ *
+ * plan, values, cdf and modes are pgm_sample_forward's.  evidence[col * ld + row0 + r] (device, uint8,
+ * read only) is evidence row r of n_rows: in a PGM_SAMPLE_GIVEN or PGM_SAMPLE_OBSERVED family the node
+ * takes that code, PGM_EV_MISSING means it is drawn; a PGM_SAMPLE_FREE family never reads its column.
+ * Sample s of row r is stream row first_row + r * n_samples + s of `seed`, with pgm_sample_forward's
+ * uniforms and selection rule: the codes are the ones pgm_sample_forward writes for the evidence row
+ * replicated n_samples times.  Its log-weight is lw = sum log(value / column total) over the
+ * PGM_SAMPLE_OBSERVED families whose given code is a state, in plan order, in fp64 from +0.0 (one
+ * division, one log and one addition per term; a value of 0 gives -inf).  The weight is never a product.
+ *
+ * targets is an ordinary fit plan.  Family (cols, cards) is one table over those columns in the fit
+ * layout (the first column slowest): one column is a marginal, several are a joint.  The tables lie end
+ * to end, total_bins entries per evidence row.  A sample adds its weight to one bin of every family.
+ *
+ * The sums are integers.  With M_r the largest lw of row r, K = min(52, 62 - ceil(log2 n_samples)):
+ * a sample adds q = llrint(ldexp(exp(lw - M_r), K)) (0 when M_r = -inf) as uint64, first into an LDS tile
+ * and from there with global integer atomics.  So every output of a row is bit-identical whatever the
+ * workgroup size, the split of the samples over workgroups and the other rows of the batch.
+ *   acc [n_rows, total_bins] uint64   the sums (written, not added to)
+ *   scale [n_rows] fp64               M_r
+ *   post [n_rows, total_bins] fp64    optional: acc / sum q, per family (all weights 0: 0/0 = NaN)
+ *   log_evidence [n_rows] fp64        optional: M_r + log(sum q * 2^-K / n_samples); all weights 0: -inf
+ *   ess [n_rows] fp64                 optional: (sum q')^2 / sum q'^2, q' = q >> max(K - 20, 0), integer
+ *                                     sums; all weights 0: 0
+ * All device memory, indexed by r, 8-byte aligned.  A row with an evidence code that is neither
+ * PGM_EV_MISSING nor a state in a GIVEN / OBSERVED family indexes nothing: its acc is 0, its post, scale
+ * and log_evidence are NaN, its ess 0, the other rows are not affected and the call returns PGM_EINDEX
+ * (a device flag read back after the launches: the call synchronises the stream).
+ *
+ * A workgroup of `block` work-items takes PGM_LW_CHUNK samples of one row; a lane owns a sample at a time
+ * and keeps its codes in LDS as [column][lane] bytes.  First every (row, chunk) finds its largest lw;
+ * then the same samples are drawn again from the counter, quantised against M_r and added; a last launch
+ * divides.  LDS: 8 * total_bins + n_cols * block + 2 KiB for the reductions, n_cols the sample plan's.
+ * block 0 takes the largest of 256 / 128 / 64 that fits PGM_LW_LDS_BUDGET; 64, 128 or 256 forces it (the
+ * test hook).  When none fits the call returns PGM_EINVAL.  The chunk maxima and row sums belong to the
+ * sample plan's handle (plan handles, above): a launch covers PGM_LW_MAX_GROUPS (row, chunk) pairs and a
+ * call makes as many as its rows need.
+ *
+ * Every argument is checked on the host before any HIP call: PGM_EINVAL for a null plan / targets /
+ * values / cdf / evidence / acc / scale, an fp64 or uint64 pointer that is not 8-byte aligned, n_cols
+ * smaller than either plan's columns, a window outside ld, n_samples outside 1 .. PGM_LW_MAX_SAMPLES, a
+ * stream range past 2^63, a target column that is the node of no family of the sample plan or whose
+ * cardinality differs from that node's, an unknown mode and a block other than 0 / 64 / 128 / 256.
+ * n_rows == 0 is PGM_OK and launches nothing.  pgm_sample_posterior_info needs no device. */
+#define PGM_LW_CHUNK 1024            /* samples of one row a workgroup takes */
+#define PGM_LW_MAX_SAMPLES (1 << 20) /* samples per evidence row */
+#define PGM_LW_LDS_BUDGET 163840     /* bytes of LDS a workgroup may take: the CU's 160 KiB */
+#define PGM_LW_MAX_GROUPS 65536      /* (row, chunk) workgroups of one launch */
+typedef struct {
+  int32_t block;         /* work-items per workgroup */
+  int32_t chunk;         /* samples per workgroup */
+  int32_t k;             /* K: a weight of 1 (the row's largest) is 2^K */
+  int32_t lds_bytes;     /* dynamic LDS of the accumulating launch */
+  int32_t lds_budget;
+  int32_t n_cols;        /* code columns a lane keeps: the sample plan's */
+  int64_t total_bins;    /* bins per evidence row: the target plan's */
+  int64_t chunks_per_row;
+  int64_t workgroups;      /* n_rows * chunks_per_row */
+  int64_t rows_per_launch; /* rows one launch covers */
+} pgm_lw_info_t;
+int pgm_sample_posterior_info(void *plan, void *targets, int64_t n_rows, int64_t n_samples, int32_t block,
+                              pgm_lw_info_t *info);
+int pgm_sample_posterior(void *plan, void *targets, const double *values, const double *cdf, const uint8_t *modes,
+                         const uint8_t *evidence, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
+                         int64_t n_samples, int64_t first_row, uint64_t seed, int32_t block,
+                         unsigned long long *acc, double *scale, double *post, double *log_evidence, double *ess,
+                         void *stream);
+
 /* ---------------------------------------------------------------- Gibbs sampling
  * GibbsSampling (sampling/Sampling.py:409-631) on the device: many chains per launch, one per lane, in
  * the column-major uint8 codes that pgm_fit_count and the fused row plan read.  An extension of ABI 25.

@@ -233,6 +233,18 @@ class SampleInfo(ctypes.Structure):
 SAMPLE_FREE, SAMPLE_GIVEN, SAMPLE_OBSERVED = 0, 1, 2
 
 
+class LwInfo(ctypes.Structure):
+    """pgm_lw_info_t: launch geometry, fixed-point exponent and LDS of a pgm_sample_posterior call (host-only
+    query)."""
+    _fields_ = [("block", ctypes.c_int32), ("chunk", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("lds_bytes", ctypes.c_int32), ("lds_budget", ctypes.c_int32), ("n_cols", ctypes.c_int32),
+                ("total_bins", ctypes.c_int64), ("chunks_per_row", ctypes.c_int64), ("workgroups", ctypes.c_int64),
+                ("rows_per_launch", ctypes.c_int64)]
+
+
+LW_CHUNK, LW_MAX_SAMPLES, LW_LDS_BUDGET, LW_MAX_GROUPS = 1024, 1 << 20, 163840, 65536  # PGM_LW_*
+
+
 class GibbsInfo(ctypes.Structure):
     """pgm_gibbs_info_t: layout, launch geometry and kernel path of a pgm_gibbs plan (host-only query)."""
     _fields_ = [("n_factors", ctypes.c_int32), ("n_cols", ctypes.c_int32), ("total_entries", ctypes.c_int64),
@@ -438,6 +450,11 @@ _SIGS = {
     "pgm_sample_cdf": ([_P, _P, _P, _P], ctypes.c_int),
     "pgm_sample_forward": ([_P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                             ctypes.c_int64, ctypes.c_uint64, _P, _P, _P], ctypes.c_int),
+    "pgm_sample_posterior_info": ([_P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(LwInfo)],
+                                  ctypes.c_int),
+    "pgm_sample_posterior": ([_P, _P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                              ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32, _P, _P, _P, _P, _P, _P],
+                             ctypes.c_int),
     "pgm_gibbs_plan_create": ([ctypes.POINTER(FitFamily), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
                                ctypes.POINTER(_P)], ctypes.c_int),
     "pgm_gibbs_plan_destroy": ([_P], ctypes.c_int),

@@ -22,6 +22,8 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmlogp.hip",       # per-row log-probability: log-table + row-sum kernels, their C-ABI (on the fit plan)
     "pgmsample.hip",     # forward sampling: running-sum + sampling kernels, their C-ABI
     "pgmsample_plan.cpp",  # forward sampling: family validation, argument checks, host-only queries (host only)
+    "pgmlw.hip",         # likelihood-weighted posteriors: the fused sample / weight / histogram kernels, their C-ABI
+    "pgmlw_plan.cpp",    # likelihood-weighted posteriors: launch geometry, argument checks, host-only query (host only)
     "pgmgibbs.hip",      # Gibbs sampling: the fused sweep kernel, its C-ABI
     "pgmgibbs_plan.cpp",  # Gibbs sampling: factor validation, incidence lists, argument checks (host only)
     "pgmdq.cpp",         # direct AQL dispatch (host code, HSA runtime)

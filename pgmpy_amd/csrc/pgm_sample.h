@@ -46,6 +46,21 @@ PGM_HD double sample_uniform3(uint64_t seed, uint64_t chain, uint32_t col, uint3
 }
 PGM_HD double sample_uniform(uint64_t seed, uint64_t row, uint32_t col) { return sample_uniform3(seed, row, col, 0u); }
 
+// The state a uniform selects in one CPD column: c is the column's running sums (entry k at c[k * ncol]).
+// With t = u * total the state is min{k : c_k > t}; if u * total rounded up to the total there is none, and
+// it is the first state that reaches the total.  Shared by pgm_sample_forward and pgm_sample_posterior.
+PGM_HD int32_t sample_select(const double *c, int32_t card, int64_t ncol, double u) {
+  const double total = c[(int64_t)(card - 1) * ncol];
+  const double t = u * total;
+  int32_t k = 0;
+  while (k < card && !(c[(int64_t)k * ncol] > t)) ++k;
+  if (k == card) {  // u * total rounded up to the total: the first state that reaches it
+    k = 0;
+    while (k < card - 1 && !(c[(int64_t)k * ncol] == total)) ++k;
+  }
+  return k;
+}
+
 // ---------------------------------------------------------------------------- the plan
 // the families of a fit plan (same descriptors, same flat table layout) given in a topological order
 struct PGM_FIT_LOCAL SamplePlan {
@@ -60,7 +75,15 @@ struct PGM_FIT_LOCAL SampleHandle {
   const FitFam *d_fams = nullptr;
   const int64_t *d_col_off = nullptr;
   uint8_t *d_modes = nullptr;  // the staging buffer of a call's modes: one byte per family
+  // the posterior stage (pgmlw.hip): one fp64 maximum per (row, chunk) workgroup, three uint64 sums per row
+  double *d_lw_max = nullptr;
+  unsigned long long *d_lw_sums = nullptr;
 };
+
+// The descriptors and the modes' staging buffer on the current device, and with kSamplePosterior what only
+// pgm_sample_posterior needs (pgmsample.hip; pgmlw.hip shares it).
+enum { kSampleNoStage = -1, kSamplePosterior = 0 };
+PGM_FIT_LOCAL int sample_use(SampleHandle *h, int stage = kSampleNoStage);
 
 // validate the families (fit_plan_build's layout + the sampler's ordering rules); PGM_OK, or PGM_EINVAL
 // with pgm_last_error set

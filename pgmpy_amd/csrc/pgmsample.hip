@@ -81,16 +81,7 @@ __device__ __forceinline__ bool sample_walk(const FitFam *__restrict__ fams, int
         double u;
         if constexpr (U) u = uniforms[(int64_t)F.col[0] * ld + at + j];
         else u = sample_uniform(seed, srow + (uint64_t)j, (uint32_t)F.col[0]);
-        const double *c = cc + col[j];
-        const double total = c[(int64_t)(card - 1) * ncol];
-        const double t = u * total;
-        int32_t k = 0;
-        while (k < card && !(c[(int64_t)k * ncol] > t)) ++k;
-        if (k == card) {  // u * total rounded up to the total: the first state that reaches it
-          k = 0;
-          while (k < card - 1 && !(c[(int64_t)k * ncol] == total)) ++k;
-        }
-        s = (uint32_t)k;
+        s = (uint32_t)sample_select(cc + col[j], card, ncol, u);
       } else if (g >= (uint32_t)card) {
         s = g;  // stays as given; never an index
         dead |= 1u << j;
@@ -155,10 +146,15 @@ __global__ __launch_bounds__(kSampleBlock) void k_sample_forward(const FitFam *_
 
 // ---------------------------------------------------------------------------- the handle's device side
 // the descriptors and the staging buffer of a call's modes on the current device
-static int sample_use(SampleHandle *h) {
+int sample_use(SampleHandle *h, int stage) {
   const FitPlan &p = h->p.fit;
   const pgmdev::Slot base[] = {pgmdev::upload(h->d_fams, p.fams), pgmdev::upload(h->d_col_off, p.col_off),
                                pgmdev::scratch(h->d_modes, p.fams.size())};
+  if (stage == kSamplePosterior) {
+    const pgmdev::Slot lw[] = {pgmdev::scratch(h->d_lw_max, (size_t)PGM_LW_MAX_GROUPS),
+                               pgmdev::scratch(h->d_lw_sums, (size_t)3 * PGM_LW_MAX_GROUPS)};
+    return h->dev.use(kHipDevOps, base, stage, lw);
+  }
   return h->dev.use(kHipDevOps, base);
 }
 

@@ -454,13 +454,26 @@ class DiscreteBayesianNetwork(nx.DiGraph):
 
         Rows are grouped by evidence pattern; each pattern is one compiled device plan
         (fused one-lane-per-row kernel).  The output frame matches the reference:
-        columns data.columns + missing variables, rows in index order, state names."""
+        columns data.columns + missing variables, rows in index order, state names.
+
+        algo=ApproxInference (with n_samples=..., seed=...): the joint MAP by likelihood weighting, one
+        fused launch sequence for all rows (inference/ApproxInference.py); ValueError when the joint table
+        of the missing variables exceeds the kernel's bin budget."""
         from ..inference.batch import column_checks, predict_frame
 
-        column_checks(self, data)  # the reference's ValueErrors (cached per columns object)
+        order = column_checks(self, data)  # the reference's ValueErrors (cached per columns object)
         if algo is not None:
-            from ..inference import Inference
+            from ..inference import ApproxInference, Inference
 
+            if algo is ApproxInference:  # likelihood weighting: the joint MAP of each row's missing variables
+                if stochastic:
+                    raise NotImplementedError("predict(algo=ApproxInference, stochastic=True) is not built")
+                n_samples = kwargs.pop("n_samples", int(1e4))
+                if kwargs:
+                    raise TypeError(f"predict(algo=ApproxInference) got unexpected arguments: {sorted(kwargs)}")
+                if len(data) == 0:
+                    raise IndexError("list index out of range (predict on an empty DataFrame)")
+                return ApproxInference(self).predict_frame(data, order, n_samples=n_samples, seed=seed)
             if not (isinstance(algo, type) and issubclass(algo, Inference)):
                 raise TypeError(f"Algorithm should be a valid pgmpy inference method. Got {type(algo)} instead.")
         if stochastic:

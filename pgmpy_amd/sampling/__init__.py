@@ -71,6 +71,25 @@ class _Compiled:
         self.plan = SamplePlan([([self.col[u] for u in c.variables], [int(k) for k in c.cardinality])
                                 for c in self.cpds])
         self.values = self.cdf = None
+        self._targets = {}  # target variable lists -> the FitPlan of their tables (posterior_codes)
+
+    def target_plan(self, targets):
+        """The FitPlan whose families are the tables of `targets` (a tuple of tuples of variables), cached."""
+        from ..estimators._fit import FitPlan
+
+        plan = self._targets.get(targets)
+        if plan is None:
+            if len(self._targets) >= 64:
+                self._targets.clear()
+            plan = self._targets[targets] = FitPlan([([self.col[v] for v in t], [self.card[v] for v in t])
+                                                     for t in targets])
+        return plan
+
+    def posterior_bin_budget(self):
+        """The most target bins a posterior call can take: the LDS budget less the smallest workgroup's codes."""
+        from .. import _native as N
+
+        return max((N.LW_LDS_BUDGET - 2048 - 64 * self.plan.n_cols) // 8, 0)
 
     def tables(self):
         """(values, running sums) on the device; CPDs that are already there (fit) are not copied to
@@ -160,6 +179,48 @@ class BayesianModelSampling:
                 c.plan.forward(cdf, codes, first_row=first_row, seed=seed, modes=fmodes if partial_codes else None,
                                values=values if weights else None, weights=w)
         return (codes, c.nodes, w) if weights else (codes, c.nodes)
+
+    @E.serialized
+    def posterior_codes(self, evidence_codes, targets, n_samples, seed=None, first_row=0, modes=None, block=0):
+        """Likelihood weighting for a batch of evidence rows in one fused launch sequence
+        (pgm_sample_posterior): no sampled code is written to memory.
+
+        evidence_codes: uint8 device codes [n_nodes, R], columns in sorted(model.nodes()) order, 255 = not
+        observed.  targets: a list whose entries are a variable (its marginal) or a list of variables (one
+        joint table over them in C order, the first variable slowest).  modes: {node: GIVEN | OBSERVED} for the nodes whose
+        evidence counts (default: every node OBSERVED; a 255 cell is drawn whatever the mode).  Sample s of
+        row r is stream row first_row + r * n_samples + s of `seed` (None: fresh entropy).
+
+        Returns (Posterior, layout): the Posterior's device tensors are indexed by evidence row, layout is
+        [(variables, offset, shape)] per target into the bins axis."""
+        n_samples, first_row = int(n_samples), int(first_row)
+        c = compiled(self.model)
+        targets = [tuple(t) if isinstance(t, list) else (t,) for t in targets]
+        if not targets:
+            raise ValueError("posterior_codes needs at least one target")
+        for t in targets:
+            for v in t:
+                if v not in c.col:
+                    raise ValueError(f"Node {v} not in the model")
+            if len(set(t)) != len(t):
+                raise ValueError(f"a target lists a variable twice: {list(t)}")
+        fmodes = np.full(len(c.order), OBSERVED, dtype=np.uint8)
+        if modes is not None:
+            fmodes[:] = FREE
+            for v, m in dict(modes).items():
+                if v not in c.col:
+                    raise ValueError(f"Node {v} not in the model")
+                if m not in (FREE, GIVEN, OBSERVED):
+                    raise ValueError(f"mode of {v} must be FREE (0), GIVEN (1) or OBSERVED (2). Got {m}")
+                fmodes[c.family_of[v]] = m
+        plan = c.target_plan(tuple(targets))
+        seed = fresh_seed() if seed is None else int(seed) & MASK64
+        values, cdf = c.tables()
+        with c.lock:  # the call returns after the launches have finished (it reads the bad-code flag back)
+            out = c.plan.posterior(plan, values, cdf, evidence_codes, n_samples, first_row=first_row, seed=seed,
+                                   modes=fmodes, block=block)
+        layout = [(list(t), plan.offsets[i], tuple(c.card[v] for v in t)) for i, t in enumerate(targets)]
+        return out, layout
 
     # ------------------------------------------------------------------ helpers
     def _partial(self, partial_samples, size):

@@ -7,6 +7,7 @@ share the fit plan's flat layout: family f occupies ``[offsets[f], offsets[f] + 
 ``[node_card, prod(parent_card)]`` in C order.
 """
 import ctypes
+from collections import namedtuple
 
 import numpy as np
 
@@ -14,6 +15,10 @@ from .. import _native as N
 from .._plan import MASK64, Plan, codes_window, family_array, flat_tensor
 
 FREE, GIVEN, OBSERVED = N.SAMPLE_FREE, N.SAMPLE_GIVEN, N.SAMPLE_OBSERVED
+
+# what SamplePlan.posterior returns: device tensors indexed by evidence row (post, log_evidence, ess: None
+# when not asked for); acc holds the uint64 sums as int64 (they stay below 2^62)
+Posterior = namedtuple("Posterior", ["acc", "scale", "post", "log_evidence", "ess"])
 
 
 class SamplePlan(Plan):
@@ -81,3 +86,49 @@ class SamplePlan(Plan):
                                      int(row0), n_rows, int(first_row), int(seed) & MASK64, N.ptr(weights),
                                      N.ptr(uniforms), N.stream_handle()), "sample_forward")
         return codes
+
+    def posterior_info(self, targets, n_rows, n_samples, block=0):
+        """LwInfo of a posterior call with the FitPlan `targets` (pgm_sample_posterior_info; no device):
+        workgroup size, K, LDS bytes, workgroups.  Raises ValueError when no workgroup size fits the LDS
+        budget."""
+        info = N.LwInfo()
+        N.check(N.load_library().pgm_sample_posterior_info(self._h, targets._h, int(n_rows), int(n_samples), int(block),
+                                                           ctypes.byref(info)), "sample_posterior_info")
+        return info
+
+    def posterior(self, targets, values, cdf, evidence, n_samples, n_rows=None, row0=0, first_row=0, seed=0,
+                  modes=None, block=0, post=True, log_evidence=True, ess=True):
+        """Likelihood weighting for the evidence rows [row0, row0 + n_rows) of the device codes `evidence`
+        [n_cols, ld] (uint8, 255: not observed): n_samples samples per row, histogrammed into the tables of
+        the FitPlan `targets` (pgm_sample_posterior).  Sample s of row r is stream row
+        first_row + r * n_samples + s of `seed`.  modes as in forward.  block: 0 automatic, 64 / 128 / 256
+        forces the workgroup size.  Returns a Posterior of device tensors [n_rows, total_bins] / [n_rows].
+        Raises IndexError when an evidence code is neither 255 nor a state (that row's post is NaN)."""
+        import torch
+
+        L = N.lib()
+        n_cols, ld, n_rows = codes_window(evidence, n_rows, row0)
+        flat_tensor("cdf", cdf, self.total_bins)
+        flat_tensor("values", values, self.total_bins)
+        m = None
+        if modes is not None:
+            m = np.ascontiguousarray(modes, dtype=np.uint8)
+            if m.shape != (len(self.families),):
+                raise ValueError(f"modes must have one entry per family ({len(self.families)})")
+        rows, bins, dev = max(n_rows, 0), targets.total_bins, evidence.device
+        acc = torch.empty((rows, bins), dtype=torch.int64, device=dev)
+        scale = torch.empty(rows, dtype=torch.float64, device=dev)
+        out_post = torch.empty((rows, bins), dtype=torch.float64, device=dev) if post else None
+        out_le = torch.empty(rows, dtype=torch.float64, device=dev) if log_evidence else None
+        out_ess = torch.empty(rows, dtype=torch.float64, device=dev) if ess else None
+        out = Posterior(acc, scale, out_post, out_le, out_ess)
+        try:
+            N.check(L.pgm_sample_posterior(self._h, targets._h, N.ptr(values), N.ptr(cdf),
+                                           None if m is None else m.ctypes.data_as(ctypes.c_void_p), N.ptr(evidence),
+                                           n_cols, ld, int(row0), n_rows, int(n_samples), int(first_row),
+                                           int(seed) & MASK64, int(block), N.ptr(acc), N.ptr(scale), N.ptr(out_post),
+                                           N.ptr(out_le), N.ptr(out_ess), N.stream_handle()), "sample_posterior")
+        except IndexError as e:
+            e.posterior = out  # the other rows are complete
+            raise
+        return out
