@@ -1135,6 +1135,83 @@ int pgm_gibbs_sweep(void *plan, const double *values, uint8_t *codes, int32_t n_
                     const uint8_t *clamp, uint8_t *trace, int64_t ld_trace, int64_t thin, const double *uniforms,
                     void *stream);
 
+/* ---------------------------------------------------------------- pairwise counts
+ * The contingency table of EVERY pair of columns, optionally per state of a stratum (class) column, in
+ * one launch, and the statistics the tree learners weigh their edges with (estimators/TreeSearch.py:
+ * mutual information, normalised and adjusted mutual information; the reference calls scikit-learn once
+ * per pair, TreeSearch.py:196-356).  An extension of ABI 25.
+ *
+ * Variable v reads code column cols[v] (each column at most once) and has cards[v] states, 1 .. 254;
+ * code PGM_EV_MISSING means missing.  The states of all variables are laid end to end: variable v owns
+ * the states [offsets[v], offsets[v] + cards[v]), S = sum of the cardinalities = offsets[n_vars], and
+ * Sp = S rounded up to 16.  `counts` is an int64 device array [n_strata][Sp][Sp] (table_size = Sp * Sp
+ * entries per stratum): for u < v in the order given,
+ *   counts[c][offsets[u] + a][offsets[v] + b]
+ * is the number of rows with u = a, v = b and stratum code c, none of the three missing (without a stratum
+ * column: none of the two).  With O the rows x S one-hot matrix this is the block (u, v) of O^T O, which
+ * one int8 MFMA kernel computes exactly (0/1 operands, int32 accumulators per row slice, int64 atomics).
+ * ONLY these blocks are specified: the cells of a variable against itself, the lower triangle (v before
+ * u) and the padding rows and columns past S hold unspecified values.
+ *
+ * pgm_pair_count ADDS to `counts` (the caller zeroes them; several calls may count several row windows)
+ * the rows [row0, row0 + n_rows) of codes[col * ld + row] (n_cols columns of ld rows).  strat_col = -1:
+ * one stratum (n_strata = 1); else stratum c takes the rows whose code in column strat_col is c <
+ * n_strata, and rows with any other code there (PGM_EV_MISSING included) are counted nowhere; the stratum
+ * column may also be one of the variables.  A row with PGM_EV_MISSING in a column is left out of exactly
+ * the pairs with that column (per-pair complete cases).  A code of a variable that takes part in a pair
+ * and is neither PGM_EV_MISSING nor < its cardinality is counted nowhere, and the call returns PGM_EINDEX
+ * (a device flag the call reads back after the launch, so the call synchronises the stream).  The rows
+ * are cut into slices of slice_rows rows (chosen on the host so that a small input still fills the
+ * device; at most 2^30, so an int32 accumulator cannot wrap); pgm_pair_plan_set_slice forces a slice
+ * length (0: back to the automatic choice), which changes the launch and none of the integers.  Operands
+ * are loaded 16 aligned bytes at a time when codes, ld and row0 are multiples of 16, else byte by byte;
+ * no load leaves [row0, row0 + n_rows) of a column the plan names.
+ *
+ * pgm_pair_mi writes, for stratum c and pair p (u < v, u-major: (0,1), (0,2), ..., (1,2), ...) at
+ * [c * n_pairs + p]: from the block's own row sums a, column sums b and total N (so missing cells are
+ * handled per pair),
+ *   mi = max(0, sum over n_ab > 0 of (n_ab / N) (log n_ab + log N - log a_a - log b_b)),
+ *   hu = sum over a_a > 0 of (a_a / N) (log N - log a_a), hv likewise over b, and n = N;
+ * N = 0 gives mi = hu = hv = 0.  pgm_pair_emi writes the expected mutual information of the block's
+ * marginals under the hypergeometric model (scikit-learn's expected_mutual_information): the sum over
+ * a, b and n = max(1, a_a + b_b - N) .. min(a_a, b_b) of (n / N) log(N n / (a_a b_b)) times the
+ * hypergeometric probability, the exponential of nine lgamma terms; 0 when N = 0.
+ * Both are fp64 with one workgroup of PGM_PAIR_STAT_BLOCK work-items per (stratum, pair), every addition
+ * in an order fixed by the pair's shape alone and no floating-point atomics: a pair's numbers are
+ * bit-identical whatever else is in the plan.  mi, hu, hv, emi (fp64) and n (int64) are device arrays of
+ * n_strata * n_pairs entries.
+ *
+ * Every argument is checked on the host before any HIP call; pgm_pair_plan_create, pgm_pair_plan_info,
+ * pgm_pair_plan_set_slice and pgm_pair_count_info need no device.  The handle follows the rules of the
+ * plan handles (parameter learning, above). */
+#define PGM_PAIR_STAT_BLOCK 64 /* work-items per (stratum, pair) of the statistic kernels */
+typedef struct {
+  int32_t n_vars;
+  int32_t n_cols;          /* 1 + the largest code column read */
+  int64_t S;               /* states of all variables */
+  int64_t Sp;              /* S rounded up to 16: the side of a stratum's table */
+  int64_t table_size;      /* Sp * Sp: int64 entries of one stratum */
+  int64_t n_pairs;         /* n_vars (n_vars - 1) / 2 */
+  int64_t n_tile_pairs;    /* 16 x 16 tile pairs (ti <= tj) that touch a block of two variables */
+  int64_t n_groups;        /* 64 x 64 super-tile pairs that hold one of them: grid.x of the count launch */
+  int64_t n_state_entries; /* entries of the state table: S rounded up to 64 */
+  int64_t slice_rows;      /* the forced slice length, 0: automatic */
+} pgm_pair_info_t;
+int pgm_pair_plan_create(const int32_t *cols, const int32_t *cards, int32_t n_vars, void **plan);
+int pgm_pair_plan_destroy(void *plan);
+/* offsets: n_vars + 1 entries; tile_pairs: 2 * n_tile_pairs entries (ti, tj); groups: 3 * n_groups entries
+ * (I, J, check: bit 0 the A side, bit 1 the B side verifies its codes); any output may be NULL */
+int pgm_pair_plan_info(void *plan, pgm_pair_info_t *info, int64_t *offsets, int32_t *tile_pairs, int32_t *groups);
+int pgm_pair_plan_set_slice(void *plan, int64_t slice_rows);
+/* the launch a count over this window makes: rows per slice, slices, and whether the 16-byte loads apply */
+int pgm_pair_count_info(void *plan, const void *codes, int64_t ld, int64_t row0, int64_t n_rows, int32_t n_strata,
+                        int64_t *slice_rows, int64_t *n_slices, int32_t *vec16);
+int pgm_pair_count(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
+                   int32_t strat_col, int32_t n_strata, int64_t *counts, void *stream);
+int pgm_pair_mi(void *plan, const int64_t *counts, int32_t n_strata, double *mi, double *hu, double *hv, int64_t *n,
+                void *stream);
+int pgm_pair_emi(void *plan, const int64_t *counts, int32_t n_strata, double *emi, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -256,6 +256,16 @@ class GibbsInfo(ctypes.Structure):
 
 GIBBS_LDS, GIBBS_GLOBAL = 0, 1  # PGM_GIBBS_*
 
+
+class PairInfo(ctypes.Structure):
+    """pgm_pair_info_t: the state layout and launch lists of a pgm_pair plan (host-only query)."""
+    _fields_ = [("n_vars", ctypes.c_int32), ("n_cols", ctypes.c_int32), ("S", ctypes.c_int64), ("Sp", ctypes.c_int64),
+                ("table_size", ctypes.c_int64), ("n_pairs", ctypes.c_int64), ("n_tile_pairs", ctypes.c_int64),
+                ("n_groups", ctypes.c_int64), ("n_state_entries", ctypes.c_int64), ("slice_rows", ctypes.c_int64)]
+
+
+PAIR_STAT_BLOCK, PAIR_MAX_CARD = 64, 254  # PGM_PAIR_STAT_BLOCK; the largest cardinality of a pair plan
+
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
 RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
@@ -466,6 +476,19 @@ _SIGS = {
     "pgm_gibbs_sweep": ([_P, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                          ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, _P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P],
                         ctypes.c_int),
+    "pgm_pair_plan_create": ([ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                              ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_pair_plan_destroy": ([_P], ctypes.c_int),
+    "pgm_pair_plan_info": ([_P, ctypes.POINTER(PairInfo), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32),
+                            ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "pgm_pair_plan_set_slice": ([_P, ctypes.c_int64], ctypes.c_int),
+    "pgm_pair_count_info": ([_P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                             ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "pgm_pair_count": ([_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                        ctypes.c_int32, _P, _P], ctypes.c_int),
+    "pgm_pair_mi": ([_P, _P, ctypes.c_int32, _P, _P, _P, _P, _P], ctypes.c_int),
+    "pgm_pair_emi": ([_P, _P, ctypes.c_int32, _P, _P], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -26,7 +26,9 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmlw_plan.cpp",    # likelihood-weighted posteriors: launch geometry, argument checks, host-only query (host only)
     "pgmgibbs.hip",      # Gibbs sampling: the fused sweep kernel, its C-ABI
     "pgmgibbs_plan.cpp",  # Gibbs sampling: factor validation, incidence lists, argument checks (host only)
-    "pgmdq.cpp",         # direct AQL dispatch (host code, HSA runtime)
+    "pgmpair.hip",       # pairwise counts: the int8 MFMA count kernel, the pair statistic kernels, their C-ABI
+    "pgmpair_plan.cpp",  # pairwise counts: validation, state table, tile groups, slice choice, argument checks (host only)
+    "pgmdq.cpp",        # direct AQL dispatch (host code, HSA runtime)
     "pgmpm.cpp",         # plan-specialised batched-BP steps: hipRTC, code-object cache, bound launches (host code)
     "pgmpm_gen.cpp",     # plan-specialised batched-BP steps: planner + generators of the specialised sources (host only)
     "pgmhost.cpp",       # DataFrame ingestion helpers (host threads only)

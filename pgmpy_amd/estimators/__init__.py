@@ -10,8 +10,10 @@ Built: BaseEstimator, ParameterEstimator, MaximumLikelihoodEstimator, BayesianEs
 K2, BDeu, BDs, LogLikeliHood, BIC, AIC, get_scoring_method; HillClimbSearch, ExpertKnowledge (required and
 forbidden edges); CITests (chi_square, g_sq, log_likelihood, modified_log_likelihood, power_divergence,
 get_callable_ci_test, CITester) and PC (orig / stable / parallel; a PDAG from pgmpy_amd.base);
-ExpectationMaximization (every row complete in its observed columns).  Not built: MarginalEstimator / IPF
-(MaximumLikelihoodEstimator on a JunctionTree), GES, MMHC, TreeSearch, ExhaustiveSearch, the Gaussian and conditional-Gaussian scores, the continuous and mixed CI
+ExpectationMaximization (every row complete in its observed columns); TreeSearch (Chow-Liu and TAN: the
+tables of every pair of columns from one int8 MFMA launch, pgm_pair_count, and the pair statistics from
+pgm_pair_mi / pgm_pair_emi).  Not built: MarginalEstimator / IPF
+(MaximumLikelihoodEstimator on a JunctionTree), GES, MMHC, ExhaustiveSearch, the Gaussian and conditional-Gaussian scores, the continuous and mixed CI
 tests (pearsonr, gcm, pillai) and independence_match (DESIGN.md).
 """
 from .base import BaseEstimator, ParameterEstimator
@@ -23,7 +25,8 @@ from . import CITests
 from .CITests import CITester
 from .PC import PC
 from .EM import ExpectationMaximization
+from .TreeSearch import TreeSearch
 
 __all__ = ["BaseEstimator", "ParameterEstimator", "MaximumLikelihoodEstimator", "BayesianEstimator",
            "StructureScore", "K2", "BDeu", "BDs", "LogLikeliHood", "BIC", "AIC", "get_scoring_method",
-           "HillClimbSearch", "ExpertKnowledge", "CITests", "CITester", "PC", "ExpectationMaximization"]
+           "HillClimbSearch", "ExpertKnowledge", "CITests", "CITester", "PC", "ExpectationMaximization", "TreeSearch"]

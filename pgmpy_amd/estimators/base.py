@@ -102,6 +102,80 @@ class BaseEstimator(object):
         return out
 
 
+    # ------------------------------------------------------------------ every pair of columns at once
+    def _pair_plan(self, variables, given):
+        codes, col_of = self._codes()
+        variables = [v for v in self.variables if v != WEIGHT] if variables is None else list(variables)
+        for v in variables + ([] if given is None else [given]):
+            if v not in col_of:
+                raise KeyError(v)
+        from ._pairs import PairPlan
+
+        plan = PairPlan([col_of[v] for v in variables], [len(self.state_names[v]) for v in variables])
+        stratum = None if given is None else col_of[given]
+        n_strata = 1 if given is None else len(self.state_names[given])
+        return plan, codes, variables, stratum, n_strata
+
+    @E.serialized
+    def pairwise_counts(self, variables=None, given=None):
+        """{(u, v): DataFrame} of the contingency table of every pair of `variables` (all columns when
+        None; u before v in that order), from one launch of the pairwise-count kernel (pgm_pair_count):
+        index = u's states, columns = v's states, and with `given` a MultiIndex (v, given) of columns, as
+        state_counts(u, [v, given]) has.  A row with NaN in u, v or `given` is not counted.  Downloads every
+        table: meant for small inputs."""
+        import pandas as pd
+
+        from ..inference.batch import download
+
+        plan, codes, variables, stratum, n_strata = self._pair_plan(variables, given)
+        counts = download(plan.count(codes, stratum=stratum, n_strata=n_strata)).reshape(n_strata, plan.Sp, plan.Sp)
+        out = {}
+        for i, u in enumerate(variables):
+            for j in range(i + 1, len(variables)):
+                v = variables[j]
+                block = np.asarray(plan.block(counts, i, j, slice(None)))  # [strata, ru, rv]
+                index = pd.Index(list(self.state_names[u]), name=u)
+                if given is None:
+                    out[(u, v)] = pd.DataFrame(block[0], index=index, columns=pd.Index(list(self.state_names[v]), name=v))
+                else:
+                    columns = pd.MultiIndex.from_product([list(self.state_names[v]), list(self.state_names[given])],
+                                                         names=[v, given])
+                    out[(u, v)] = pd.DataFrame(block.transpose(1, 2, 0).reshape(block.shape[1], -1), index=index,
+                                               columns=columns)
+        return out
+
+    @E.serialized
+    def pairwise_mutual_information(self, variables=None, given=None, kind="mutual_info"):
+        """The symmetric [n, n] matrix (numpy, zero diagonal) of the `kind` of mutual information of every
+        pair of `variables` (all columns when None): "mutual_info", "normalized_mutual_info" or
+        "adjusted_mutual_info", scikit-learn's definitions.  With `given`, the weight of a pair is
+        sum_c p_c w_c over the states c of that column (the TAN weight).  One count launch, one or two
+        statistic launches (the expected mutual information only for the adjusted kind) and one download.
+        A row with NaN is left out per pair."""
+        from ..inference.batch import download
+        from . import _pairs as P
+
+        if kind not in P.KINDS:
+            P.pair_weights(kind, 0.0, 0.0, 0.0, 0)  # the reference's ValueError
+        plan, codes, variables, stratum, n_strata = self._pair_plan(variables, given)
+        if plan.n_pairs == 0:
+            return np.zeros((len(variables), len(variables)))
+        counts = plan.count(codes, stratum=stratum, n_strata=n_strata)
+        stats = list(plan.mi(counts))
+        if kind == "adjusted_mutual_info":
+            stats.append(plan.emi(counts))
+        import torch
+
+        flat = download(torch.cat([s.view(torch.int64).reshape(-1) for s in stats]))  # one copy: raw 64-bit words
+        parts = flat.reshape(len(stats), n_strata, plan.n_pairs)
+        mi, hu, hv = (parts[k].view(np.float64) for k in range(3))
+        n = parts[3]
+        emi = parts[4].view(np.float64) if len(stats) == 5 else None
+        w = P.pair_weights(kind, mi, hu, hv, n, emi)
+        values = w[0] if given is None else P.stratified_weight(w, n)
+        return P.weight_matrix(len(variables), values)
+
+
 class ParameterEstimator(BaseEstimator):
     def __init__(self, model, data, **kwargs):
         self.model = model
