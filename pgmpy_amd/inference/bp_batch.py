@@ -86,17 +86,20 @@ RATIO_PREMARG = os.environ.get("PGM_BP_RATIO", "1") != "0"
 
 
 class _SepFromRatio:
-    """A sepset belief sigma' the schedule did not store: the child's update ratio r = sigma'/mu and its
-    message mu; sigma' = r x mu (exact where mu = 0: the parent's belief then holds the factor mu, so
-    sigma' = 0 = r x mu), made on first use (outside the compiled program)."""
+    """A sepset belief sigma' the schedule did not store: the child's update ratio r = sigma'/mu (axes `rl`:
+    the parent's order of the separator) and its message mu (axes `sl`: the child's); sigma' = r x mu (exact
+    where mu = 0: the parent's belief then holds the factor mu, so sigma' = 0 = r x mu), made on first use
+    (outside the compiled program) and again after every later run of the schedule (`runs`: its run counter),
+    which overwrites r and mu."""
 
-    def __init__(self, ratio, mu, sl):
-        self.ratio, self.mu, self.sl = ratio, mu, sl
-        self._t = None
+    def __init__(self, ratio, rl, mu, sl, runs):
+        self.ratio, self.rl, self.mu, self.sl, self.runs = ratio, rl, mu, sl, runs
+        self._t, self._run = None, -1
 
     def __getitem__(self, i):
-        if self._t is None:
-            self._t = E.product_n([(self.ratio, self.sl), (self.mu, self.sl)], self.sl)
+        if self._run != self.runs[0]:
+            self._t = E.product_n([(self.ratio, self.rl), (self.mu, self.sl)], self.sl)
+            self._run = self.runs[0]
         return (self._t, self.sl[:-1])[i]
 
     def __iter__(self):
@@ -149,6 +152,10 @@ class BPSchedule:
         dev = E.device()
         self.codes = torch.empty((max(1, len(self.ev_vars)), n_rows), dtype=torch.uint8, device=dev)
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        # (clique, branch name) at every decision of the schedule below, in build order: read by the tests
+        # only (tests/test_bp_paths_gpu.py asserts which branches a tree reaches), never by the package
+        self.trace = trace = []
+        self._runs = [0]  # [runs so far]
         ev_by_clique = {}
         for j, v in enumerate(self.ev_vars):
             ev_by_clique.setdefault(bjt.var_clique[v], []).append((j, v))
@@ -184,18 +191,29 @@ class BPSchedule:
             base = list(kinds) if kinds is not None else [N.PRODN_MUL] * len(ops)
             ks = [k for k in kids[c] if set(msgs[k][1][:-1]) == set(sc)]
             idx = None
-            if RATIO_PREMARG and len(ks) == 1:
+            if not RATIO_PREMARG:
+                trace.append((c, "ratio_knob_off"))
+            elif len(ks) != 1:
+                trace.append((c, "ratio_not_single_child"))
+            else:
                 idx = next((i for i, (t_, _) in enumerate(ops) if t_ is msgs[ks[0]][0] and base[i] == N.PRODN_MUL), None)
+                if idx is None:  # the child's message went into an aggregate: no operand to divide by
+                    trace.append((c, "ratio_message_aggregated"))
                 other = {frozenset(msgs[q][1][:-1]) for q in kids[c]} - {frozenset(sc)}
                 for s_ in other:  # every other child scope inside S still finds a sigma' to come from
                     if s_ <= set(sc) and not any(s_ < t_ for t_ in other):
+                        if idx is not None:
+                            trace.append((c, "ratio_blocked_nested_scope"))
                         idx = None
                 if idx is not None:
                     if out is None:
                         out = E.empty([bjt.card[v] for v in labels] + [n_rows])
                     mk = list(base)
                     mk[idx] = N.PRODN_MDIV
-                    ok = E.prepare_product_n_marginal(ops, labels + [R], list(sc) + [R], out, mk)[5]
+                    # (a pass folded to more operands than the fused kernel takes is declined like any other)
+                    ok = len(ops) <= N.PM_MAX_OPS and \
+                        E.prepare_product_n_marginal(ops, labels + [R], list(sc) + [R], out, mk)[5]
+                    trace.append((c, "ratio_stored" if ok else "ratio_declined_by_kernel"))
                     if ok:
                         bt, m, _ = prog.product_n_marginal(ops, labels + [R], list(sc) + [R], out=out, kinds=mk,
                                                            reduce=red)
@@ -224,8 +242,10 @@ class BPSchedule:
             # over their scopes first (_aggregate)
             direct = 1 + len(small) + (2 if c in parent else 0) <= N.PM_MAX_OPS
             ops = [(t, ls)] + (list(small) if direct else _aggregate(prog, small, ls, scope_size))
+            trace.append((c, "ops_direct" if direct else "ops_aggregated"))
             if len(ops) == 1:
                 ops.append((E.to_device(np.ones(n_rows)), [R]))  # broadcast psi over the rows
+                trace.append((c, "ops_ones"))
             operands[c] = ops
             if c in parent:
                 sep = [v for v in ls if v in parent[c]]
@@ -235,13 +255,17 @@ class BPSchedule:
                 mops = ops
                 if len(ops) - 1 < len(small) and 1 + len(small) <= N.PM_MAX_OPS:
                     mops = [(t, ls)] + list(small)
+                    trace.append((c, "msg_from_inputs"))
+                trace.append((c, "inner" if c in kids else "leaf"))
                 bt, m, _ = prog.product_n_marginal(mops, ls + [R], sep + [R], reduce=red, store=False)
                 beliefs[c] = (bt, ls)  # the buffer distribute writes (the fallback path filled it already)
                 msgs[c] = (m, sep + [R])
             elif c in kids:
+                trace.append((c, "root_premarginal"))
                 bt, premarg[c] = premarginal(c, ops, ls)
                 beliefs[c] = (bt, ls)
             else:
+                trace.append((c, "single_clique"))
                 beliefs[c] = (prog.product_n(ops, ls + [R]), ls)
         # distribute: root -> leaves; one sigma' per distinct separator scope of a parent, each
         # marginalised from the smallest already-computed containing scope (or the belief).  A child's
@@ -253,19 +277,24 @@ class BPSchedule:
 
         def finalise(p, c, sigma=None, ratio=None):
             """c's final belief psi_c x operands x sigma'/mu_c in one pass (with its own premarginal when it
-            has children); `ratio` = sigma'/mu_c already made by the parent's pass."""
+            has children); `ratio` = (sigma'/mu_c, its labels) already made by the parent's pass: the
+            separator in the parent's variable order, which need not be the child's (`sl`)."""
             tc, lc = beliefs[c]
             mu, sl = msgs[c]
             if ratio is not None and len(operands[c]) + 1 <= N.PM_MAX_OPS:
-                ops_c = operands[c] + [(ratio, sl)]
+                ops_c = operands[c] + [ratio]
                 kinds = None
+                trace.append((c, "fin_ratio_operand"))
             elif ratio is not None:  # folded into the aggregates
-                ops_c = [operands[c][0]] + _aggregate(prog, operands[c][1:] + [(ratio, sl)], lc, scope_size)
+                trace.append((c, "fin_ratio_folded"))
+                ops_c = [operands[c][0]] + _aggregate(prog, operands[c][1:] + [ratio], lc, scope_size)
                 kinds = None
             elif len(operands[c]) + 2 <= N.PM_MAX_OPS:  # sigma' / mu as a ratio operand pair (0/0 -> 0)
                 ops_c = operands[c] + [(sigma, sl), (mu, sl)]
                 kinds = [N.PRODN_MUL] * len(operands[c]) + [N.PRODN_RATIO, N.PRODN_DEN]
+                trace.append((c, "fin_sigma_mu_pair"))
             else:  # the separator-sized ratio folded into the aggregates
+                trace.append((c, "fin_sigma_mu_folded"))
                 r_ = prog.product_n([(sigma, sl), (mu, sl)], sl, kinds=[N.PRODN_RATIO, N.PRODN_DEN])
                 ops_c = [operands[c][0]] + _aggregate(prog, operands[c][1:] + [(r_, sl)], lc, scope_size)
                 kinds = None
@@ -274,7 +303,7 @@ class BPSchedule:
                 _, premarg[c] = premarginal(c, ops_c, lc, out=tc, kinds=kinds)
             else:
                 prog.product_n(ops_c, lc + [R], out=tc, kinds=kinds)
-            seps[(p, c)] = (sigma, sl[:-1]) if ratio is None else _SepFromRatio(ratio, mu, sl)
+            seps[(p, c)] = (sigma, sl[:-1]) if ratio is None else _SepFromRatio(*ratio, mu, sl, self._runs)
         for p in [bjt.root] + [c for _, c in bjt.order]:
             if p not in kids:
                 continue
@@ -291,10 +320,13 @@ class BPSchedule:
             ordered = sorted(scopes, key=lambda x: -scope_size(x))
             for si, sc in enumerate(ordered):
                 if ratio_kid is not None and scopes[sc] == [ratio_kid]:
-                    finalise(p, ratio_kid, ratio=premarg[p][1])
+                    trace.append((p, "sigma_via_ratio"))
+                    finalise(p, ratio_kid, ratio=(premarg[p][1], list(premarg[p][0]) + [R]))
                     continue
                 if sc in have:
                     sigma = have[sc]
+                    if sigma is premarg.get(p, (None, None))[1]:  # else: the second of a pair made above
+                        trace.append((p, "sigma_from_premarginal"))
                 else:
                     src = min((h for h in have if set(sc) <= set(h)), key=scope_size)
                     sigma = None
@@ -309,12 +341,14 @@ class BPSchedule:
                                                            out=tp, kinds=fk, reduce=red)
                         if two is not None:
                             sigma, have[partner] = two
+                            trace.append((p, "sigma_pair_from_operands"))
                         else:
-                            d_, p_, o_, ms_, M_, ok = E.prepare_product_n_marginal(fops, lp + [R], list(sc) + [R],
-                                                                                   tp, fk, store=False)
+                            ok = len(fops) <= N.PM_MAX_OPS and \
+                                E.prepare_product_n_marginal(fops, lp + [R], list(sc) + [R], tp, fk, store=False)[5]
                             if ok:
                                 _, sigma, _ = prog.product_n_marginal(fops, lp + [R], list(sc) + [R], out=tp,
                                                                       kinds=fk, reduce=red, store=False)
+                                trace.append((p, "sigma_from_operands"))
                     if sigma is None and src != tuple(lp):
                         # a second scope whose smallest computed container is the same source: both marginals
                         # in one read of it (C4's root child scopes, 129 / 64 MB sources read once, not twice:
@@ -328,7 +362,10 @@ class BPSchedule:
                                                            reduce=red)
                             if two is not None:
                                 sigma, have[partner] = two
+                                trace.append((p, "sigma_pair_from_container"))
                     if sigma is None:
+                        trace.append((p, "sigma_contract_from_belief" if src == tuple(lp)
+                                      else "sigma_contract_from_container"))
                         sigma = prog.contract(have[src], list(src) + [R], None, None, list(sc) + [R], reduce=red,
                                               combine="copy")
                     have[sc] = sigma
@@ -361,6 +398,7 @@ class BPSchedule:
                 raise ValueError(f"codes must be a contiguous uint8 [{len(self.ev_vars)}, {self.n_rows}] tensor")
             N.check(L.pgm_memcpy_d2d(N.ptr(self.codes), N.ptr(codes), codes.numel(), s), "memcpy_d2d")
         self.prog.run()
+        self._runs[0] += 1  # sepset beliefs rebuilt from a ratio (_SepFromRatio) are made again for this run
         return BatchedCalibration(self.bjt, self.beliefs, self.seps, self.n_rows, self.marg)
 
 

@@ -668,8 +668,12 @@ class Program:
             m = N.PRODN_MAX_OPS
             n_groups = -(-len(ops) // m)
             size = -(-len(ops) // n_groups)
-            partials = [(self.product_n(ops[i:i + size], out_labels), list(out_labels))
-                        for i in range(0, len(ops), size)]
+            # (a group's partial product is over the labels its own operands carry: all of out_labels when
+            # the operands share one scope, fewer when a clique's pass multiplies operands of different scopes)
+            partials = []
+            for i in range(0, len(ops), size):
+                ls = [l for l in out_labels if any(l in gl for _, gl in ops[i:i + size])]
+                partials.append((self.product_n(ops[i:i + size], ls), ls))
             return self.product_n(partials, out_labels, out)
         while len(ops) > N.PRODN_MAX_OPS:  # fold the surplus (plain MUL operands) into the output first
             cut = N.PRODN_MAX_OPS if kinds[N.PRODN_MAX_OPS - 1] != N.PRODN_RATIO else N.PRODN_MAX_OPS - 1
