@@ -1212,6 +1212,128 @@ int pgm_pair_mi(void *plan, const int64_t *counts, int32_t n_strata, double *mi,
                 void *stream);
 int pgm_pair_emi(void *plan, const int64_t *counts, int32_t n_strata, double *emi, void *stream);
 
+/* ---------------------------------------------------------------- linear-Gaussian networks
+ * LinearGaussianBayesianNetwork (models/LinearGaussianBayesianNetwork.py) on a resident fp64 value
+ * matrix X[col * ld + row] (n_cols columns of ld rows, column-major like the codes; a call works on the
+ * rows [row0, row0 + n_rows)).  An extension of ABI 25.
+ *
+ * THE GRAM HANDLE (pgm_lg_gram_plan_*, pgm_lg_colsum, pgm_lg_gram) is made over d distinct columns
+ * cols[0 .. d).  The OLS fit of every node of any DAG over them is a function of the centred Gram matrix
+ * S = (X - mu)^T (X - mu), which two passes give:
+ *   pgm_lg_colsum writes sums[j] = the fp64 sum of column cols[j] over the window and counts[j] = n_rows.
+ *     A workgroup adds PGM_LG_COLSUM_CHUNK-row pieces (its work-items stride the piece, then a fixed
+ *     tree); a second kernel adds the pieces of a column in index order.  No floating-point atomics.
+ *   pgm_lg_gram takes a shift c[0 .. d) (device; the caller divides the sums, so c is within rounding of
+ *     the mean) and writes the symmetric (d + 1) x (d + 1) matrix `out` (device, row-major) of the columns
+ *     x_j - c_j with a column of ones appended at index d:
+ *       out[j][k] = sum (x_j - c_j)(x_k - c_k),  out[j][d] = sum (x_j - c_j),  out[d][d] = n_rows.
+ *     S_jk = out[j][k] - out[j][d] out[k][d] / n is exact algebra whatever c is, and harmless numerically
+ *     because c is the mean up to rounding; raw moments (c = 0) or a shift by the first row lose every
+ *     digit when |mu| >> sigma.  The upper triangle is computed, the lower one mirrored from it.
+ * The d + 1 columns are cut into tiles of PGM_LG_TILE = 16 and super-tiles of PGM_LG_SUPER = 4 tiles; a
+ * group is super-tile I against super-tile J (I <= J): up to 4 x 4 accumulators of 16 x 16 fp64 fed by
+ * v_mfma_f64_16x16x4_f64, one wave per (group, row slice).  A diagonal group forms one fragment per tile
+ * and uses it on both sides (10 accumulators); with d + 1 <= 64 it is the only group, so the data is
+ * read from memory exactly once.  Lane (i = lane & 15, q = lane >> 4) loads the PGM_LG_ROWS_PER_LANE = 4
+ * consecutive rows r + 4 q .. r + 4 q + 3 of its column of a PGM_LG_STEP = 16-row step, and MFMA s of the
+ * step uses the s-th of them on both sides: a sum over rows does not depend on which k slot a row takes
+ * as long as both operands agree, and a lane then reads 32 contiguous bytes (two 16-byte loads) instead
+ * of 8.  The 16-byte loads need X, ld * 8 and row0 * 8 to be multiples of 16; any other window takes
+ * 8-byte loads (pgm_lg_gram_info tells which).  The shift is subtracted in registers; a row at or past
+ * the window's end contributes zero AFTER the shift; the ones column is a constant, not a load; no load
+ * leaves the window of a column the plan names.
+ * Rows are cut into slices of slice_rows rows (a multiple of PGM_LG_STEP, chosen so that a launch has
+ * about PGM_LG_TARGET_BLOCKS waves and a slice at least PGM_LG_SLICE_MIN rows; pgm_lg_gram_plan_set_slice
+ * forces a length, 0: automatic).  The handle keeps max_slices = max(4, PGM_LG_TARGET_BLOCKS / n_groups)
+ * slice partials; a forced length that would need more is raised to ceil(n_rows / max_slices) rounded up.
+ * Each (slice, group) writes its partial with plain stores and a second kernel adds the slices in slice
+ * order: an entry is bit-identical from run to run and, for a fixed slice length, whatever other columns
+ * the handle has and wherever its own two columns stand in it.
+ * A NaN or Inf cell makes the entries of its column's row and column of `out` non-finite (the pair with
+ * the ones column included) and no other; no bit pattern is used as an index.
+ * pgm_lg_colsum and pgm_lg_gram with n_rows == 0 return PGM_OK, launch nothing and write nothing.
+ *
+ * THE NETWORK HANDLE (pgm_lg_net_*) is made over families in a topological order: family f owns
+ * fam_cols[fam_off[f] .. fam_off[f + 1]), the node's column first, then its parents' in the CPD's order.
+ * Refused (PGM_EINVAL): a parent that is not the node of an earlier family, a column that is the node
+ * of two families or listed twice in one, more than PGM_LG_MAX_PARENTS parents.  The coefficients of a
+ * call are a device array `coef` of n_coef = fam_off[n] + n entries: family f at fam_off[f] + f holds
+ * beta_0, beta_1 .. beta_p (the parents' order) and sigma.  They are read with wave-uniform (scalar)
+ * loads, so the limit on p is a bound on a kernel's loop, not on a register or LDS array.
+ *   pgm_lg_sample: one lane per row, families in order, x_v = beta_0 + sum_i beta_i x_{p_i} + sigma_v z.
+ *     z is the normal of stream row first_row + r and COLUMN col_v: columns 2 k and 2 k + 1 share the
+ *     Philox4x32-10 call of forward sampling (counter (row lo, row hi, k, 0), key = seed); with u0 the
+ *     53-bit uniform of words (x0, x1) and u1 that of (x2, x3), rho = sqrt(-2 log(1 - u0)),
+ *     z_{2k} = rho cospi(2 u1), z_{2k+1} = rho sinpi(2 u1).  A row depends on (seed, stream row) alone,
+ *     not on the window, the batch or the launch geometry.  A lane re-reads only what it wrote itself.
+ *   pgm_lg_logpdf: logp[r] (n_rows entries, r counted from row0) = sum over f in order of konst[f] - 0.5 ((x_v - m_f) / sigma_f)^2, m_f
+ *     = beta_0 + sum_i beta_i x_{p_i} added in the parents' order; konst[f] = -log sigma_f - 0.5 log 2 pi
+ *     comes from the host (device array, n entries).  total = the sum of the window's logp: per workgroup
+ *     of PGM_LG_BLOCK rows a fixed tree, then one workgroup adds the partials in a fixed order (as
+ *     pgm_fit_logprob).  logp or total may be NULL, not both.  At most PGM_LG_MAX_BLOCKS * PGM_LG_BLOCK
+ *     rows per call.  A non-finite cell gives a non-finite logp for its row only (and total).
+ *   pgm_lg_affine needs no handle: out[j * ld_out + r] = c[j] + sum_i W[j * n_in + i] X[in_cols[i] * ld +
+ *     row0 + r], i ascending; W, c device, in_cols a HOST array that travels in the kernel arguments,
+ *     PGM_LG_AFFINE_CHUNK columns per launch (later launches add to out in the same order).
+ *
+ * Every argument is checked on the host before any HIP call; the plan create / info / set_slice calls
+ * and pgm_lg_gram_info need no device.  The handles follow the rules of the plan handles (parameter
+ * learning, above). */
+#define PGM_LG_TILE 16
+#define PGM_LG_SUPER 4
+#define PGM_LG_ROWS_PER_LANE 4
+#define PGM_LG_STEP 16            /* rows of one step: 4 k slots x PGM_LG_ROWS_PER_LANE */
+#define PGM_LG_TARGET_BLOCKS 1024 /* waves a Gram launch aims at: four per CU of a 256-CU device */
+#define PGM_LG_SLICE_MIN 1024     /* rows of the shortest automatic slice of a window longer than that */
+#define PGM_LG_COLSUM_CHUNK 4096  /* rows of one piece of a column sum (more when a column has > 1024 pieces) */
+#define PGM_LG_COLSUM_MAX_CHUNKS 1024
+#define PGM_LG_MAX_PARENTS 4096
+#define PGM_LG_BLOCK 256          /* rows (and work-items) per workgroup of sample / logpdf / affine */
+#define PGM_LG_MAX_BLOCKS 65536   /* workgroups of one pgm_lg_logpdf call */
+#define PGM_LG_AFFINE_CHUNK 256
+typedef struct {
+  int32_t d;           /* columns of the handle */
+  int32_t n_cols;      /* 1 + the largest column read */
+  int32_t n_tiles;     /* ceil((d + 1) / 16) */
+  int32_t n_super;     /* ceil(n_tiles / 4) */
+  int32_t single_wave; /* 1: d + 1 <= 64, one diagonal group reads the data once */
+  int32_t reserved;
+  int64_t n_groups;    /* super-tile pairs I <= J: grid.x of the Gram launch */
+  int64_t n_tile_pairs; /* 16 x 16 accumulators (ti <= tj) that hold part of the upper triangle */
+  int64_t out_size;    /* (d + 1)^2 doubles */
+  int64_t max_slices;  /* slice partials the handle keeps */
+  int64_t slice_rows;  /* the forced slice length, 0: automatic */
+} pgm_lg_gram_info_t;
+int pgm_lg_gram_plan_create(const int32_t *cols, int32_t d, void **plan);
+int pgm_lg_gram_plan_destroy(void *plan);
+/* groups: 2 * n_groups entries (I, J); any output may be NULL */
+int pgm_lg_gram_plan_info(void *plan, pgm_lg_gram_info_t *info, int32_t *groups);
+int pgm_lg_gram_plan_set_slice(void *plan, int64_t slice_rows);
+/* the launch a Gram over this window makes: rows per slice, slices, and whether the 16-byte loads apply */
+int pgm_lg_gram_info(void *plan, const void *X, int64_t ld, int64_t row0, int64_t n_rows, int64_t *slice_rows,
+                     int64_t *n_slices, int32_t *vec16);
+int pgm_lg_colsum(void *plan, const double *X, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, double *sums,
+                  int64_t *counts, void *stream);
+int pgm_lg_gram(void *plan, const double *X, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
+                const double *shift, double *out, void *stream);
+typedef struct {
+  int32_t n_families;
+  int32_t n_cols;      /* 1 + the largest column read or written */
+  int32_t max_parents; /* of the plan's families */
+  int32_t reserved;
+  int64_t n_coef;      /* fam_off[n] + n entries of coef */
+} pgm_lg_net_info_t;
+int pgm_lg_net_create(const int32_t *fam_off, const int32_t *fam_cols, int32_t n_families, void **plan);
+int pgm_lg_net_destroy(void *plan);
+/* coef_off: n_families entries, where a family's beta_0 stands in coef; may be NULL */
+int pgm_lg_net_info(void *plan, pgm_lg_net_info_t *info, int64_t *coef_off);
+int pgm_lg_sample(void *plan, const double *coef, double *X, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
+                  int64_t first_row, uint64_t seed, void *stream);
+int pgm_lg_logpdf(void *plan, const double *coef, const double *konst, const double *X, int32_t n_cols, int64_t ld,
+                  int64_t row0, int64_t n_rows, double *logp, double *total, void *stream);
+int pgm_lg_affine(const double *W, const double *c, const int32_t *in_cols, int32_t n_in, int32_t n_out, const double *X,
+                  int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, double *out, int64_t ld_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

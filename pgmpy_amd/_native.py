@@ -266,6 +266,27 @@ class PairInfo(ctypes.Structure):
 
 PAIR_STAT_BLOCK, PAIR_MAX_CARD = 64, 254  # PGM_PAIR_STAT_BLOCK; the largest cardinality of a pair plan
 
+
+class LgGramInfo(ctypes.Structure):
+    """pgm_lg_gram_info_t: the tile layout and launch lists of a pgm_lg_gram plan (host-only query)."""
+    _fields_ = [("d", ctypes.c_int32), ("n_cols", ctypes.c_int32), ("n_tiles", ctypes.c_int32), ("n_super", ctypes.c_int32),
+                ("single_wave", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_groups", ctypes.c_int64),
+                ("n_tile_pairs", ctypes.c_int64), ("out_size", ctypes.c_int64), ("max_slices", ctypes.c_int64),
+                ("slice_rows", ctypes.c_int64)]
+
+
+class LgNetInfo(ctypes.Structure):
+    """pgm_lg_net_info_t: the families of a pgm_lg_net plan (host-only query)."""
+    _fields_ = [("n_families", ctypes.c_int32), ("n_cols", ctypes.c_int32), ("max_parents", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("n_coef", ctypes.c_int64)]
+
+
+# PGM_LG_*: the geometry of the linear-Gaussian kernels
+LG_TILE, LG_SUPER, LG_ROWS_PER_LANE, LG_STEP = 16, 4, 4, 16
+LG_TARGET_BLOCKS, LG_SLICE_MIN = 1024, 1024
+LG_COLSUM_CHUNK, LG_COLSUM_MAX_CHUNKS = 4096, 1024
+LG_MAX_PARENTS, LG_BLOCK, LG_MAX_BLOCKS, LG_AFFINE_CHUNK = 4096, 256, 65536, 256
+
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
 RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
@@ -489,6 +510,24 @@ _SIGS = {
                         ctypes.c_int32, _P, _P], ctypes.c_int),
     "pgm_pair_mi": ([_P, _P, ctypes.c_int32, _P, _P, _P, _P, _P], ctypes.c_int),
     "pgm_pair_emi": ([_P, _P, ctypes.c_int32, _P, _P], ctypes.c_int),
+    "pgm_lg_gram_plan_create": ([ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_lg_gram_plan_destroy": ([_P], ctypes.c_int),
+    "pgm_lg_gram_plan_info": ([_P, ctypes.POINTER(LgGramInfo), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "pgm_lg_gram_plan_set_slice": ([_P, ctypes.c_int64], ctypes.c_int),
+    "pgm_lg_gram_info": ([_P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "pgm_lg_colsum": ([_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, _P, _P], ctypes.c_int),
+    "pgm_lg_gram": ([_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, _P, _P], ctypes.c_int),
+    "pgm_lg_net_create": ([ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                           ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_lg_net_destroy": ([_P], ctypes.c_int),
+    "pgm_lg_net_info": ([_P, ctypes.POINTER(LgNetInfo), ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
+    "pgm_lg_sample": ([_P, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                       ctypes.c_uint64, _P], ctypes.c_int),
+    "pgm_lg_logpdf": ([_P, _P, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, _P, _P],
+                      ctypes.c_int),
+    "pgm_lg_affine": ([_P, _P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32,
+                       ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, _P], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

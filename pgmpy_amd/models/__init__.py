@@ -3,6 +3,7 @@ from .DiscreteBayesianNetwork import DiscreteBayesianNetwork
 from .DiscreteMarkovNetwork import DiscreteMarkovNetwork
 from .FactorGraph import FactorGraph
 from .JunctionTree import JunctionTree
+from .LinearGaussianBayesianNetwork import LinearGaussianBayesianNetwork
 from .NaiveBayes import NaiveBayes
 
 # pgmpy < 1.0 names
@@ -10,4 +11,4 @@ BayesianNetwork = DiscreteBayesianNetwork
 MarkovNetwork = DiscreteMarkovNetwork
 
 __all__ = ["ClusterGraph", "DiscreteBayesianNetwork", "BayesianNetwork", "DiscreteMarkovNetwork", "MarkovNetwork",
-           "FactorGraph", "JunctionTree", "NaiveBayes"]
+           "FactorGraph", "JunctionTree", "LinearGaussianBayesianNetwork", "NaiveBayes"]
