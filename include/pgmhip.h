@@ -1334,6 +1334,87 @@ int pgm_lg_logpdf(void *plan, const double *coef, const double *konst, const dou
 int pgm_lg_affine(const double *W, const double *c, const int32_t *in_cols, int32_t n_in, int32_t n_out, const double *X,
                   int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, double *out, int64_t ld_out, void *stream);
 
+/* ---------------------------------------------------------------- Gaussian structure learning
+ * Partial correlations (estimators/CITests.py pearsonr, GaussCITester) and the Gaussian structure scores
+ * (estimators/StructureScore.py LogLikelihoodGauss, BICGauss, AICGauss) from the moment matrix pgm_lg_gram
+ * leaves on the device: G [(d + 1) x (d + 1)], the ones column at index d, and its shift c[0 .. d).  Nothing
+ * reads the n rows again.  An extension of ABI 25.
+ *
+ * A JOB is a conditioning set K and 1 .. PGM_LGS_MAX_TARGETS targets T, all indices 0 .. d into G; its
+ * result is a function of the Schur complement T|K = M_TT - M_TK M_KK^-1 M_KT, the residual cross-products
+ * of the targets after least squares on K (which does not depend on the least-squares solution taken, so
+ * a collinear K only needs dropped pivots).  Conditioning on column d is "with an intercept".
+ *
+ * THE JOB BATCH HANDLE (pgm_lgs_jobs_*) is made once per batch from HOST arrays: job j owns
+ * job_cols[job_off[j] .. job_off[j + 1]), its K first, then its n_targets[j] targets.  Refused
+ * (PGM_EINVAL) before any HIP call: an index outside 0 .. d, a column listed twice in a job, a target
+ * that is also in K, n_targets outside 1 .. 3, more than PGM_LGS_MAX_COND conditioning columns.  The
+ * handle sorts the jobs into buckets by (|K|, n_targets), each in the batch's own order, so a launch has
+ * uniform trip counts: one launch per bucket, the outputs in the batch's order.  An empty batch
+ * (n_jobs = 0) is a valid handle whose calls return PGM_OK and launch nothing.
+ *
+ * The two calls read G, shift (device) and n = G[d][d], and write device arrays of n_jobs entries:
+ *   pgm_lgs_pcorr: with intercept = 0 every job is (K without column d; X, Y, d): the reference regresses X
+ *     and Y on Z WITHOUT an intercept and centres the residuals afterwards, so with R = T|K,
+ *     cov_ab = R_ab - R_a1 R_b1 / n.  With intercept = 1 every job is (K with column d; X, Y) and cov = R.
+ *     A batch whose jobs have another shape is refused.  coef = cov_XY / sqrt(cov_XX cov_YY) clipped to
+ *     [-1, 1]; pvalue = I_{1 - coef^2}((n - 2) / 2, 1 / 2) (csrc/pgm_ibeta.h), the two-sided Student t with
+ *     n - 2 degrees of freedom, NOT reduced by |K|, as the reference.
+ *     NaN coef and pvalue, for that job only: n <= 2; a non-finite entry of G among the job's columns; a
+ *     target without residual variance, that is one constant to rounding (centred variance at or below
+ *     n (64 u c)^2, u = 2^-53) or whose own pivot would be dropped (cov_aa <= RCOND times its centred
+ *     variance).  rank is still written.
+ *   pgm_lgs_score: every job is (K with column d; v).  rss = T|K, df = the kept pivots among K's columns other
+ *     than d, llf = -n/2 (log(2 pi rss / n) + 1) (statsmodels' Gaussian GLM llf), and score = llf
+ *     (PGM_LGS_LL), llf - (df + 2) / 2 log n (PGM_LGS_BIC) or llf - (df + 2) (PGM_LGS_AIC).  rss <= 0:
+ *     score +inf, as the closed form gives.  A non-finite entry: score and rss NaN.
+ *   rank: the pivots kept among K (the ones column counts).
+ * One device routine serves both: gather the lower triangle of the (|K| + t)^2 block; when K is not empty
+ * and has no ones column turn it into raw moments, M_uv = G_uv + c_u G_v1 + c_v G_u1 + n c_u c_v (c_d = 0;
+ * the cancellation this brings when |mean| >> sd is a property of what the reference computes); scale K
+ * to unit diagonal, a column whose diagonal is not positive being dropped; Cholesky in outer-product form
+ * WITHOUT pivoting, in K's order, where a pivot at or below RCOND = 1e-11 drops its column; the trailing
+ * t x t block is T|K.
+ * Two paths, chosen by a job's own |K| alone:
+ *   lane path, |K| <= PGM_LGS_LANE_MAX: one job per lane, |K| and t template parameters, every loop
+ *     unrolled, the packed triangle in registers (no scratch; DESIGN.md has the register counts);
+ *   wave path, up to PGM_LGS_MAX_COND: one wave (a 64-lane workgroup) per job, the triangle in LDS with an
+ *     odd row length, one lane per row of an elimination step, a barrier between steps.  (|K| + t)
+ *     ((|K| + t) | 1) + 3 (|K| + t) doubles: 37,520 bytes at the cap, four workgroups per CU.  The cap of 64
+ *     is one row per lane; the LDS budget would allow more.
+ * The order of a job's arithmetic is fixed by its own columns, every store is a plain store and there are
+ * no atomics: a job's outputs are bit-identical whatever else is in the batch, wherever it stands in it
+ * and from run to run (not across permutations of its columns).
+ * pgm_lgs_jobs_create, pgm_lgs_jobs_info and pgm_lgs_ibeta_half (the host build of the p-value's
+ * I_{1 - y}(a, 1/2)) need no device.  The handle follows the rules of the plan handles. */
+#define PGM_LGS_MAX_COND 64
+#define PGM_LGS_LANE_MAX 7
+#define PGM_LGS_MAX_TARGETS 3
+#define PGM_LGS_LL 0
+#define PGM_LGS_BIC 1
+#define PGM_LGS_AIC 2
+typedef struct {
+  int32_t n_jobs;
+  int32_t d;
+  int32_t n_buckets;      /* distinct (|K|, n_targets): launches of one call */
+  int32_t max_cond;       /* the largest |K| */
+  int64_t n_lane_jobs;    /* jobs with |K| <= PGM_LGS_LANE_MAX */
+  int64_t n_wave_jobs;
+  int64_t wave_lds_bytes; /* LDS of a workgroup of the largest wave-path bucket, 0: none */
+} pgm_lgs_info_t;
+int pgm_lgs_jobs_create(const int32_t *job_off, const int32_t *job_cols, const int32_t *n_targets, int32_t n_jobs, int32_t d,
+                        void **handle);
+int pgm_lgs_jobs_destroy(void *handle);
+/* buckets: 4 * n_buckets entries (|K|, n_targets, first, count); order: n_jobs job indices, bucket by bucket;
+ * any output may be NULL */
+int pgm_lgs_jobs_info(void *handle, pgm_lgs_info_t *info, int32_t *buckets, int32_t *order);
+int pgm_lgs_pcorr(void *handle, const double *G, const double *shift, int32_t d, int32_t intercept, double *coef, double *pvalue,
+                  int32_t *rank, void *stream);
+int pgm_lgs_score(void *handle, const double *G, const double *shift, int32_t d, int32_t kind, double *score, double *rss,
+                  int32_t *rank, void *stream);
+/* *out = I_{1 - y}(a, 1/2) by the host build of the device's function (csrc/pgm_ibeta.h) */
+int pgm_lgs_ibeta_half(double a, double y, double *out);
+
 #ifdef __cplusplus
 }
 #endif

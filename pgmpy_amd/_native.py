@@ -287,6 +287,17 @@ LG_TARGET_BLOCKS, LG_SLICE_MIN = 1024, 1024
 LG_COLSUM_CHUNK, LG_COLSUM_MAX_CHUNKS = 4096, 1024
 LG_MAX_PARENTS, LG_BLOCK, LG_MAX_BLOCKS, LG_AFFINE_CHUNK = 4096, 256, 65536, 256
 
+
+class LgsInfo(ctypes.Structure):
+    """pgm_lgs_info_t: the buckets of a pgm_lgs job batch (host-only query)."""
+    _fields_ = [("n_jobs", ctypes.c_int32), ("d", ctypes.c_int32), ("n_buckets", ctypes.c_int32), ("max_cond", ctypes.c_int32),
+                ("n_lane_jobs", ctypes.c_int64), ("n_wave_jobs", ctypes.c_int64), ("wave_lds_bytes", ctypes.c_int64)]
+
+
+# PGM_LGS_*: the limits and score kinds of the Gaussian structure learning calls
+LGS_MAX_COND, LGS_LANE_MAX, LGS_MAX_TARGETS = 64, 7, 3
+LGS_LL, LGS_BIC, LGS_AIC = 0, 1, 2
+
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
 RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
@@ -528,6 +539,14 @@ _SIGS = {
                       ctypes.c_int),
     "pgm_lg_affine": ([_P, _P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32,
                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, _P], ctypes.c_int),
+    "pgm_lgs_jobs_create": ([ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                             ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_lgs_jobs_destroy": ([_P], ctypes.c_int),
+    "pgm_lgs_jobs_info": ([_P, ctypes.POINTER(LgsInfo), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)],
+                          ctypes.c_int),
+    "pgm_lgs_pcorr": ([_P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
+    "pgm_lgs_score": ([_P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
+    "pgm_lgs_ibeta_half": ([ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

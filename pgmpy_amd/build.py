@@ -30,6 +30,8 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmpair_plan.cpp",  # pairwise counts: validation, state table, tile groups, slice choice, argument checks (host only)
     "pgmlg.hip",         # linear-Gaussian networks: the fp64 MFMA Gram kernel, sampling, log-density, affine map, their C-ABI
     "pgmlg_plan.cpp",    # linear-Gaussian networks: column / family validation, tile groups, slice choice, argument checks (host only)
+    "pgmlgs.hip",        # Gaussian structure learning: partial correlations and Gaussian scores from the Gram matrix, their C-ABI
+    "pgmlgs_plan.cpp",   # Gaussian structure learning: job validation, buckets, argument checks, the host p-value (host only)
     "pgmdq.cpp",        # direct AQL dispatch (host code, HSA runtime)
     "pgmpm.cpp",         # plan-specialised batched-BP steps: hipRTC, code-object cache, bound launches (host code)
     "pgmpm_gen.cpp",     # plan-specialised batched-BP steps: planner + generators of the specialised sources (host only)

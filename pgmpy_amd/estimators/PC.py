@@ -5,7 +5,9 @@ The reference runs one CI test per call: a pandas groupby and one scipy.stats.ch
 stratum, thousands of tests per level, fanned out over joblib.  Here every level enumerates the candidate
 separating sets of all its remaining edges and hands them to the tester in rounds of up to
 MAX_TESTS_PER_ROUND tests: one count launch and one CI launch per round (estimators/CITests.py,
-pgm_fit_citest), one download of the p-values.
+pgm_fit_citest), one download of the p-values.  On continuous data, `ci_test=pearsonr` (the function) or
+a `tester=GaussCITester(...)` hands a level to the partial-correlation kernel: no counting, one launch per
+level on the moment matrix (pgm_lgs_pcorr).
 
 `pc_skeleton` is the loop itself; it takes its tester as any object with
 `independent(triples, significance_level)`, so it runs without a device under a host tester.
@@ -25,7 +27,7 @@ import networkx as nx
 
 from ..base import PDAG
 from .base import BaseEstimator
-from .CITests import BUILTIN_LAMBDA, CITester, get_callable_ci_test, lambda_value
+from .CITests import BUILTIN_LAMBDA, CITester, GaussCITester, get_callable_ci_test, lambda_value, pearsonr
 from .HillClimbSearch import ExpertKnowledge
 
 # Most tests one round hands to the tester.  A level with more runs in several rounds; an edge separated in
@@ -124,6 +126,16 @@ class _BatchTester:
         return self.tester.independent(triples, significance_level, self.lambda_)
 
 
+class _GaussTester:
+    """A GaussCITester with its intercept option bound: a level's partial correlations in one launch."""
+
+    def __init__(self, tester, intercept):
+        self.tester, self.intercept = tester, bool(intercept)
+
+    def independent(self, triples, significance_level):
+        return self.tester.independent(triples, significance_level, intercept=self.intercept)
+
+
 class _CallableTester:
     """A user's test function, called one test at a time with the reference's keyword arguments."""
 
@@ -138,16 +150,32 @@ class _CallableTester:
 class PC(BaseEstimator):
     def __init__(self, data=None, independencies=None, tester=None, **kwargs):
         """`tester`: a CITester over the same variables to run the named tests with (one built over
-        resident device codes by CITester.from_codes, say); by default one is built from `data`."""
+        resident device codes by CITester.from_codes, say); by default one is built from `data`.  A
+        GaussCITester runs partial correlations on continuous data; with one, `data` may be None (its
+        variables are the tester's) and no state names are collected."""
         if independencies is not None:
             raise NotImplementedError("PC: independence assertions instead of data are not built")
+        self._ci = tester
+        if isinstance(tester, GaussCITester):
+            self.data, self._encoded, self.state_names = data, None, {}
+            self.variables = list(tester.variables)
+            if data is not None and list(data.columns.values) != self.variables:
+                raise ValueError("the tester's variables are not the data's columns")
+            return
         if data is None:
             raise ValueError("PC needs data")
-        self._ci = tester
         super(PC, self).__init__(data, **kwargs)
 
     def _tester(self, ci_test, kwargs):
+        if isinstance(self._ci, GaussCITester):
+            if ci_test is not None and ci_test is not pearsonr:
+                raise ValueError("a GaussCITester runs pearsonr: leave ci_test out or pass CITests.pearsonr")
+            return _GaussTester(self._ci, kwargs.get("intercept", False))
         fn = get_callable_ci_test(ci_test, data=self.data)
+        if fn is pearsonr:  # one launch per level instead of one call per test
+            if getattr(self, "_gauss", None) is None:
+                self._gauss = GaussCITester(self.data)
+            return _GaussTester(self._gauss, kwargs.get("intercept", False))
         if fn not in BUILTIN_LAMBDA:
             return _CallableTester(fn, self.data, kwargs)
         lam = BUILTIN_LAMBDA[fn]

@@ -1,5 +1,5 @@
-"""Structure scores for discrete data (mirror of pgmpy/estimators/StructureScore.py:15-916, the discrete
-classes): K2, BDeu, BDs, LogLikeliHood, BIC, AIC and get_scoring_method.
+"""Structure scores (mirror of pgmpy/estimators/StructureScore.py:15-1189, the discrete and the Gaussian
+classes): K2, BDeu, BDs, LogLikeliHood, BIC, AIC, LogLikelihoodGauss, BICGauss, AICGauss and get_scoring_method.
 
 The reference scores one family per call from a pandas groupby.  Here `local_scores(families)` scores
 any number of families at once: one FitPlan, one fused count launch over the estimator's device codes
@@ -10,7 +10,13 @@ the equivalent sample size are added on the host with math.lgamma, as the refere
 is `local_scores` of one family.
 
 Deviations: every column is discrete whatever its dtype; a variable with 255 or more states
-raises the encoders' ValueError; the Gaussian and conditional-Gaussian scores are not built.
+raises the encoders' ValueError; the conditional-Gaussian scores are not built.
+
+The Gaussian scores (LogLikelihoodGauss, BICGauss, AICGauss) score any number of families in one launch from
+the moment matrix of the continuous columns, computed once per scorer by the fp64 Gram kernel and left on
+the device (pgm_lgs_score): the concentrated log-likelihood -n/2 (log(2 pi rss / n) + 1) that the reference
+reads from statsmodels' Gaussian GLM as `llf`, with df_model the rank of the parents.  Their NAMES ("ll-g",
+"bic-g", "aic-g") stay closed in get_scoring_method: pass an instance.
 """
 from math import lgamma, log
 
@@ -19,6 +25,7 @@ import numpy as np
 from .. import _native as N
 from .. import engine as E
 from ._fit import FitPlan
+from ._gauss import GaussData, cap_error
 from ._rounds import SCORE_BIN_BUDGET, rounds as _rounds  # noqa: F401  (module attributes the tests patch)
 from .base import BaseEstimator
 
@@ -36,7 +43,8 @@ def get_scoring_method(scoring_method, data, use_cache=True):
         if name in _OLD_NAMES:
             raise ValueError("The scoring method names have been changed. Please refer the documentation.")
         if name in _NOT_BUILT:
-            raise ValueError(f"The Gaussian and conditional-Gaussian scores are not built: {scoring_method}. "
+            raise ValueError(f"The Gaussian and conditional-Gaussian scores are not built as names: {scoring_method} "
+                             f"(Gaussian: pass an instance of LogLikelihoodGauss, BICGauss or AICGauss). "
                              f"scoring_method should be one of {list(_DISCRETE)}")
         if name not in names:
             raise ValueError("Unknown scoring method. Please refer documentation for a list of supported score metrics.")
@@ -208,3 +216,44 @@ class AIC(LogLikeliHood):
     def _score_round(self, plan, counts, shapes):
         ll = self._log_likelihoods(plan, counts)
         return [ll[f] - q * (r - 1) for f, (r, q, _) in enumerate(shapes)]
+
+
+class LogLikelihoodGauss(GaussData, StructureScore):
+    """The Gaussian log-likelihood of `variable ~ parents` with an intercept (:919-1019): one pgm_lgs_score job
+    per family, K = (ones column, parents), target = variable."""
+    _kind = "ll"
+
+    def __init__(self, data, **kwargs):
+        GaussData.__init__(self, data)  # no state names: the columns are continuous
+
+    def _jobs(self, families):
+        from .. import _native as N
+
+        room = N.LGS_MAX_COND - 1
+        jobs = []
+        for variable, parents in families:
+            parents = list(parents)
+            v, *P = self.columns([variable] + parents)
+            if len(set(P)) != len(P) or v in P:
+                raise ValueError(f"a family names a variable twice: {variable}, {parents}")
+            if len(P) > room:
+                raise cap_error("parents", len(P), room)
+            jobs.append(([self.d] + P, [v]))
+        return jobs
+
+    @E.serialized
+    def local_scores(self, families):
+        """The local score of every (variable, parents) family, as a list of floats: one launch per distinct
+        number of parents, one download."""
+        jobs = self._jobs([(v, list(ps)) for v, ps in families])
+        return [float(s) for s in self.run(jobs, lambda batch, G, shift: batch.score(G, shift, self._kind))[0]]
+
+
+class BICGauss(LogLikelihoodGauss):
+    """llf - (df_model + 2) / 2 log n (:1022-1104)."""
+    _kind = "bic"
+
+
+class AICGauss(LogLikelihoodGauss):
+    """llf - (df_model + 2) (:1107-1189)."""
+    _kind = "aic"

@@ -13,20 +13,28 @@ get_callable_ci_test, CITester) and PC (orig / stable / parallel; a PDAG from pg
 ExpectationMaximization (every row complete in its observed columns); TreeSearch (Chow-Liu and TAN: the
 tables of every pair of columns from one int8 MFMA launch, pgm_pair_count, and the pair statistics from
 pgm_pair_mi / pgm_pair_emi).  Not built: MarginalEstimator / IPF
-(MaximumLikelihoodEstimator on a JunctionTree), GES, MMHC, ExhaustiveSearch, the Gaussian and conditional-Gaussian scores, the continuous and mixed CI
-tests (pearsonr, gcm, pillai) and independence_match (DESIGN.md).
+(MaximumLikelihoodEstimator on a JunctionTree), GES, MMHC, ExhaustiveSearch, the conditional-Gaussian scores, the mixed CI
+tests (gcm, pillai) and independence_match (DESIGN.md).
+
+Continuous data: CITests.pearsonr / GaussCITester (partial correlations) and LogLikelihoodGauss, BICGauss,
+AICGauss score all the tests of a PC level or all the families of a hill-climb step in one launch from the
+moment matrix the fp64 Gram kernel leaves on the device (pgm_lgs_pcorr, pgm_lgs_score); PC takes
+`ci_test=pearsonr` or `tester=GaussCITester(...)`, HillClimbSearch an instance of a Gaussian score.  The
+string names "pearsonr", "ll-g", "bic-g", "aic-g" stay closed.
 """
 from .base import BaseEstimator, ParameterEstimator
 from .MLE import MaximumLikelihoodEstimator
 from .BayesianEstimator import BayesianEstimator
-from .StructureScore import AIC, BIC, K2, BDeu, BDs, LogLikeliHood, StructureScore, get_scoring_method
+from .StructureScore import (AIC, BIC, K2, AICGauss, BDeu, BDs, BICGauss, LogLikeliHood, LogLikelihoodGauss, StructureScore,
+                             get_scoring_method)
 from .HillClimbSearch import ExpertKnowledge, HillClimbSearch
 from . import CITests
-from .CITests import CITester
+from .CITests import CITester, GaussCITester
 from .PC import PC
 from .EM import ExpectationMaximization
 from .TreeSearch import TreeSearch
 
 __all__ = ["BaseEstimator", "ParameterEstimator", "MaximumLikelihoodEstimator", "BayesianEstimator",
            "StructureScore", "K2", "BDeu", "BDs", "LogLikeliHood", "BIC", "AIC", "get_scoring_method",
-           "HillClimbSearch", "ExpertKnowledge", "CITests", "CITester", "PC", "ExpectationMaximization", "TreeSearch"]
+           "LogLikelihoodGauss", "BICGauss", "AICGauss", "HillClimbSearch", "ExpertKnowledge", "CITests", "CITester",
+           "GaussCITester", "PC", "ExpectationMaximization", "TreeSearch"]

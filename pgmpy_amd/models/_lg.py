@@ -5,6 +5,8 @@ The data is a resident fp64 value matrix: a contiguous ``torch.float64`` device 
 (column-major like the codes: ``X[col, row]``); a call works on the rows ``[row0, row0 + n_rows)``.
 
 ``GramPlan`` (columns) gives the column sums and the shifted Gram matrix of pgm_lg_colsum / pgm_lg_gram;
+``SchurJobs`` runs batches of partial correlations and Gaussian family scores on that matrix where it lies
+(pgm_lgs_pcorr / pgm_lgs_score, pgmpy_amd/csrc/pgmlgs.hip);
 ``moments`` turns the downloaded matrix into (n, mean, S) in np.longdouble and ``ols`` into one node's
 regression.  ``NetPlan`` (families in topological order) samples and scores; ``affine`` is predict's row map.
 The host functions take numpy arrays only: the restatement of the tests calls them with its own Gram matrix.
@@ -96,8 +98,8 @@ class GramPlan(Plan):
                 "lg_gram")
         return out
 
-    def moments_on_device(self, X, n_rows=None, row0=0):
-        """One colsum, one Gram, ONE download: (G [d + 1, d + 1], shift [d]) as fp64 ndarrays."""
+    def moments_device(self, X, n_rows=None, row0=0):
+        """One colsum, one Gram, nothing downloaded: (G [d + 1, d + 1], shift [d]) as fp64 device tensors."""
         import torch
 
         n_cols, ld, n_rows = values_window(X, n_rows, row0)
@@ -105,10 +107,82 @@ class GramPlan(Plan):
             raise ValueError("no rows")
         sums, counts = self.colsum(X, n_rows, row0)
         shift = (sums / counts.to(torch.float64)).contiguous()
-        G = self.gram(X, shift, n_rows, row0)
+        return self.gram(X, shift, n_rows, row0), shift
+
+    def moments_on_device(self, X, n_rows=None, row0=0):
+        """One colsum, one Gram, ONE download: (G [d + 1, d + 1], shift [d]) as fp64 ndarrays."""
+        import torch
+
+        G, shift = self.moments_device(X, n_rows, row0)
         host = torch.cat([G.reshape(-1), shift]).cpu().numpy()
         d1 = self.d + 1
         return host[:d1 * d1].reshape(d1, d1), host[d1 * d1:]
+
+
+class SchurJobs(Plan):
+    """A job batch of pgm_lgs_pcorr / pgm_lgs_score over a Gram plan's matrix: jobs are (K, targets) pairs of
+    positions 0 .. d in the plan's columns, d being the ones column.  Built and validated on the host."""
+    _destroy = "pgm_lgs_jobs_destroy"
+    KINDS = {"ll": N.LGS_LL, "bic": N.LGS_BIC, "aic": N.LGS_AIC}
+
+    def __init__(self, gram_plan, jobs):
+        L = N.load_library()
+        self.d = int(gram_plan.d if hasattr(gram_plan, "d") else gram_plan)
+        self.jobs = [([int(c) for c in K], [int(c) for c in T]) for K, T in jobs]
+        self.n = len(self.jobs)
+        off, flat = [0], []
+        for K, T in self.jobs:
+            flat.extend(K)
+            flat.extend(T)
+            off.append(len(flat))
+        self._h = ctypes.c_void_p()
+        N.check(L.pgm_lgs_jobs_create(_i32(off), _i32(flat), _i32([len(T) for _, T in self.jobs]), self.n, self.d,
+                                      ctypes.byref(self._h)), "lgs_jobs_create")
+        self.info = N.LgsInfo()
+        N.check(L.pgm_lgs_jobs_info(self._h, ctypes.byref(self.info), None, None), "lgs_jobs_info")
+
+    def buckets(self):
+        """([(|K|, targets, first, count)], order): the launches of a call and the jobs bucket by bucket."""
+        b = (ctypes.c_int32 * max(4 * int(self.info.n_buckets), 1))()
+        o = (ctypes.c_int32 * max(self.n, 1))()
+        N.check(N.load_library().pgm_lgs_jobs_info(self._h, ctypes.byref(self.info), b, o), "lgs_jobs_info")
+        return [tuple(b[4 * i:4 * i + 4]) for i in range(int(self.info.n_buckets))], list(o)[:self.n]
+
+    def _outputs(self, G):
+        import torch
+
+        flat_tensor("G", G, (self.d + 1) * (self.d + 1))
+        out = torch.empty((2, max(self.n, 1)), dtype=torch.float64, device=G.device)
+        rank = torch.empty(max(self.n, 1), dtype=torch.int32, device=G.device)
+        return out, rank
+
+    def _shift(self, G, shift):
+        import torch
+
+        if self.d == 0:  # the kernel takes the pointer
+            return torch.zeros(1, dtype=torch.float64, device=G.device)
+        flat_tensor("shift", shift, self.d)
+        return shift
+
+    def pcorr(self, G, shift, intercept=False):
+        """(coef, pvalue fp64 [n], rank int32 [n]) device tensors of the batch's partial correlations."""
+        L = N.lib()
+        out, rank = self._outputs(G)
+        shift = self._shift(G, shift)
+        N.check(L.pgm_lgs_pcorr(self._h, N.ptr(G), N.ptr(shift), self.d, 1 if intercept else 0, N.ptr(out[0]), N.ptr(out[1]),
+                                N.ptr(rank), N.stream_handle()), "lgs_pcorr")
+        return out[0, :self.n], out[1, :self.n], rank[:self.n]
+
+    def score(self, G, shift, kind):
+        """(score, rss fp64 [n], rank int32 [n]) device tensors of the batch's families; kind 'll', 'bic', 'aic'."""
+        if kind not in self.KINDS:
+            raise ValueError(f"kind must be one of {sorted(self.KINDS)}, got {kind!r}")
+        L = N.lib()
+        out, rank = self._outputs(G)
+        shift = self._shift(G, shift)
+        N.check(L.pgm_lgs_score(self._h, N.ptr(G), N.ptr(shift), self.d, self.KINDS[kind], N.ptr(out[0]), N.ptr(out[1]),
+                                N.ptr(rank), N.stream_handle()), "lgs_score")
+        return out[0, :self.n], out[1, :self.n], rank[:self.n]
 
 
 class NetPlan(Plan):
