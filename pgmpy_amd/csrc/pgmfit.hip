@@ -88,10 +88,10 @@ __global__ __launch_bounds__(kFitBlock) void k_fit_count(const FitFam *__restric
         bool skip = false;
         for (int32_t v = 0; v < nv; ++v) {
           const uint32_t c = codes[(int64_t)F.col[v] * ld + row0 + rr];
-          if (c >= (uint32_t)F.card[v]) {  // missing, or not a state
+          if (c >= (uint32_t)F.card[v]) {  // missing, or not a state: the later columns are still checked
             bad |= c != PGM_EV_MISSING;
             skip = true;
-            break;
+            continue;
           }
           idx += (int32_t)c * F.stride[v];
         }

@@ -15,7 +15,11 @@ of the ratio, one of log / pow (device log 0.503 ulp, pow under 2), the Yates sh
 counted with the sensitivity factor <= 2 above, rounded up to a power of two.  The reference (scipy, fp64)
 and the device differ from the long-double value by that much each, so the restatement is compared with
 either under the same bound.  The bound on the p-value is the change of Q over stat +- that bound plus
-Q's own relative error Q_REL (tools/ci_selftest.cpp measures it, DESIGN.md records it).
+Q_REL of the value.  Q_REL is 10 x the error tools/ci_selftest.cpp measures on the recorded grid, which ends at
+dof 5,000 (DESIGN.md records it); it is NOT the function's error at any dof: the prefactor's exponent a ln x -
+x - lgamma(a) cancels, so the error grows with the dof (2.6e-10 at dof 10^6).  The cases of this module stay
+at a dof of a few thousand, where the statistic's slack dominates; tests/crafted_cases.py q_tol is the bound of Q itself
+at any dof, and tests/test_crafted_gpu.py holds the device to it.
 """
 import ctypes
 import ctypes.util

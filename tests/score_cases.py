@@ -33,6 +33,9 @@ CHUNK = 128  # PGM_SCORE_CHUNK (include/pgmhip.h): CPD columns per workgroup of 
 # Largest error, in fp64 ulps of the exact value, of the device's lgamma / log against lgammal / logl
 # over the arguments the cases produce (tools/lgamma_ulp.hip on an MI355X; DESIGN.md "Structure scores").
 U_DEVICE = 1.538  # lgamma(4357 + 10/1260); log: 0.503
+# The same over the distinct arguments of the large-count cases of tests/crafted_cases.py (counts up to 2^40;
+# crafted_cases.write_ulp_arguments, tools/lgamma_ulp.hip --args on an MI355X, 2026-10-21).
+U_DEVICE_LARGE = 1.355  # lgamma(9), of 1,182 arguments; log: 0.498 at 586, of 561
 # The same for scipy.special.gammaln / numpy.log on the host that recorded the goldens, measured by
 # host_ulp() below (+ 1/2 for ctypes' rounding of the long-double value).
 U_HOST = 905.5

@@ -8,6 +8,9 @@
 // The grid file holds lines "k x sf" (hexadecimal floats); tests/test_ci_cpu.py writes it from the recorded grid.  Prints "max_rel_err <e>" over the points with
 // sf >= 1e-300, and "ci_selftest ok" with exit status 0 when every check holds; the error's bound is the
 // caller's (tests/test_ci_cpu.py).
+//   ./ci_selftest --sf args.txt
+// prints "sf <hexadecimal float>" = pgm_chi2_sf(x, k) for every line "k x" of args.txt and nothing else: the host
+// build's values at arguments of the caller's choice (tests/test_crafted_cpu.py compares them with mpmath).
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
@@ -149,11 +152,25 @@ static int test_argument_checks() {
   return 0;
 }
 
+// ---------------------------------------------------------------------------- pgm_chi2_sf at given arguments
+static int print_sf(const char *path) {
+  FILE *f = fopen(path, "r");
+  if (!f) {
+    fprintf(stderr, "cannot open %s\n", path);
+    return 1;
+  }
+  double k, x;
+  while (fscanf(f, "%la %la", &k, &x) == 2) printf("sf %a\n", pgm_chi2_sf(x, k));
+  fclose(f);
+  return 0;
+}
+
 int main(int argc, char **argv) {
-  if (argc < 2) {
-    fprintf(stderr, "usage: ci_selftest <grid file of 'k x sf' lines>\n");
+  if (argc < 2 || (strcmp(argv[1], "--sf") == 0 && argc < 3)) {
+    fprintf(stderr, "usage: ci_selftest <grid file of 'k x sf' lines> | --sf <file of 'k x' lines>\n");
     return 2;
   }
+  if (strcmp(argv[1], "--sf") == 0) return print_sf(argv[2]);
   if (test_igamc(argv[1]) || test_work_lists() || test_argument_checks()) return 1;
   printf("ci_selftest ok\n");
   return 0;

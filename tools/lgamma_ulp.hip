@@ -4,11 +4,16 @@
 // calls the math library functions the score kernel calls, not the kernel.  The result is the U of the
 // tests' error bound (tests/score_cases.py, DESIGN.md "Structure scores").
 //   hipcc --offload-arch=gfx950 -O3 tools/lgamma_ulp.hip -o lgamma_ulp && ./lgamma_ulp [max_count]
+//   ./lgamma_ulp --args FILE
+// measures a list of arguments instead: FILE holds lines "lgamma <x>" and "log <x>" (hexadecimal floats), as
+// tests/crafted_cases.py write_ulp_arguments writes the distinct arguments of the large-count score cases
+// (score_cases.U_DEVICE_LARGE records the result).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #define HIP_OK(expr)                                                                  \
@@ -56,7 +61,34 @@ static int run(const std::vector<double> &x, int use_log, const char *what, doub
   return 0;
 }
 
+static int run_list(const char *path) {
+  FILE *f = fopen(path, "r");
+  if (!f) {
+    fprintf(stderr, "cannot open %s\n", path);
+    return 2;
+  }
+  std::vector<double> lg, lo;
+  char what[16];
+  double v;
+  while (fscanf(f, "%15s %la", what, &v) == 2) {
+    if (strcmp(what, "lgamma") == 0) lg.push_back(v);
+    else if (strcmp(what, "log") == 0) lo.push_back(v);
+    else {
+      fprintf(stderr, "%s: unknown function %s\n", path, what);
+      fclose(f);
+      return 2;
+    }
+  }
+  fclose(f);
+  double worst = 0.0;
+  if (!lg.empty() && run(lg, 0, "lgamma(listed)", &worst)) return 2;
+  if (!lo.empty() && run(lo, 1, "log(listed)", &worst)) return 2;
+  printf("U = %.3f\n", worst);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 2 && strcmp(argv[1], "--args") == 0) return run_list(argv[2]);
   const int64_t max_count = argc > 1 ? atoll(argv[1]) : 100000;
   if (max_count < 1 || max_count > 100000000) {
     fprintf(stderr, "max_count 1 .. 1e8\n");
