@@ -47,6 +47,17 @@ mean is 0.61), and U_Z_DEVICE is its double because other seeds reach other argu
 doubled).  The long-double side must itself be exact next to the zeros of the cosine and sine: sincospi_ld.
 A node's value then carries
     dx_v <= sum_i |beta_i| dx_{p_i} + (p + 2) u (|beta_0| + sum_i |beta_i x_i| + |sigma z|) + U_Z u |sigma z|.
+
+Wide plans.  The second half of this module builds the shapes of tests/test_lg_wide_gpu.py: Gram handles of three and
+four super-tiles, the two sliced launches, affine maps of up to three launches, the net plans of net_cases (300-node
+chain and star, 4,096 parents, every visiting order of a Philox pair, unnamed columns, a dense 40-node net) and a
+300-node random model.  The bounds above are used as they stand: each scales with its own n, d or p, and at 4,096
+parents no further term appeared (the worst error / bound of every family is recorded in that module's docstring).
+Because the bounds carry a factor n they are loose on rounding; what the wide tests are for is structure, so every
+shape has NEGATIVE CONTROLS on the CPU (tests/test_lg_cpu.py): the long-double result with one structural error (a row
+left out, two columns 16 apart exchanged on one side, a slice's partial dropped; affine input 256 dropped; the cosine
+where the sine belongs; one parent's term missing) must lie outside the bound of that shape.  The data carries offset
+means and a shift that is not the window's own mean so that this holds down to a one-row window.
 """
 import json
 import os
@@ -301,8 +312,10 @@ def sincospi_ld(t):
     return (np.choose(q, [s, c, -s, -c]), np.choose(q, [c, -s, -c, s]))
 
 
-def sample_ld(families, betas, stds, n, seed, first_row=0, n_cols=None, u_z=U_Z_DEVICE):
-    """(X LD [n_cols, n], bound fp64 [n_cols, n]) of the forward sampler; the normal index is the column."""
+def sample_ld(families, betas, stds, n, seed, first_row=0, n_cols=None, u_z=U_Z_DEVICE, normals=None):
+    """(X LD [n_cols, n], bound fp64 [n_cols, n]) of the forward sampler; the normal index is the column.
+    normals: normals_ld, or a negative control's stand-in for it."""
+    normals = normals_ld if normals is None else normals
     n_cols = 1 + max(c for f in families for c in f) if n_cols is None else n_cols
     X = np.zeros((n_cols, n), dtype=LD)
     B = np.zeros((n_cols, n), dtype=LD)
@@ -310,7 +323,7 @@ def sample_ld(families, betas, stds, n, seed, first_row=0, n_cols=None, u_z=U_Z_
     for fam, beta, std in zip(families, betas, stds):
         beta = np.asarray(beta, dtype=np.float64).astype(LD)
         p = len(fam) - 1
-        z = normals_ld(seed, rows, fam[0])
+        z = normals(seed, rows, fam[0])
         x = np.full(n, beta[0], dtype=LD)
         mag = np.full(n, abs(beta[0]), dtype=LD)
         err = np.zeros(n, dtype=LD)
@@ -333,3 +346,184 @@ def model_families(model, columns):
     cpds = [model.get_cpds(v) for v in order]
     return (order, [[col[c.variable]] + [col[u] for u in c.evidence] for c in cpds], [np.asarray(c.beta, dtype=np.float64) for c in cpds],
             [float(c.std) for c in cpds])
+
+
+# ---------------------------------------------------------------------- wide and deep synthetic plans
+# The shapes of tests/test_lg_wide_gpu.py and of the negative controls in tests/test_lg_cpu.py (module docstring,
+# "Wide plans").  Everything below is seeded: the CPU controls see the data the device sees.
+GRAM_WIDE_D = (128, 191, 200)        # d + 1 = 129: the third super-tile is the ones column alone; 12 full tiles; 13 tiles, 10 groups
+GRAM_WIDE_ROWS = (1, 15, 16, 17, 33)  # below, at and past one step; two steps and one row
+AFFINE_N_IN = (0, 1, 255, 256, 257, 600)  # PGM_LG_AFFINE_CHUNK = 256: no input, one launch, two, three
+AFFINE_N_OUT = (1, 5)
+AFFINE_ROWS = (1, 255, 256, 257)
+SLICE_MIN, STEP = 1024, 16           # PGM_LG_SLICE_MIN, PGM_LG_STEP (tests/test_lg_cpu.py asserts the binding's)
+
+
+def wide_data(n_cols, ld, seed):
+    """Dependent columns with different means and scales: every entry of the Gram matrix is its own number."""
+    rng = np.random.default_rng(seed)
+    base = rng.normal(size=(3, ld))
+    mix = rng.normal(size=(n_cols, 3))
+    return mix @ base + rng.normal(size=(n_cols, ld)) * rng.uniform(0.5, 2.0, (n_cols, 1)) + rng.normal(size=(n_cols, 1)) * 10
+
+
+def gram_window(d, row0, n_rows, seed, ld=40, n_cols=None, shuffled=False):
+    """(host [n_cols, ld], cols [d], shift [d]) of one Gram case: NaN in every row outside the window and in every
+    column the plan does not name (column d // 2 among them).  The shift is the mean of the column over ALL ld rows of
+    the data before the blanking, not the window's own: a one-row window at its own mean is the zero matrix, on which
+    no structural error shows."""
+    n_cols = d + 2 if n_cols is None else n_cols
+    assert ld > n_rows + row0 and n_cols > d
+    full = wide_data(n_cols, ld, seed)
+    if shuffled:
+        cols = [int(c) for c in np.random.default_rng(seed + 1).permutation(n_cols)[:d]]
+    else:
+        cols = [c for c in range(n_cols) if c != d // 2][:d]
+    shift = colmean(full, cols)
+    host = np.full_like(full, np.nan)
+    host[cols, row0:row0 + n_rows] = full[cols, row0:row0 + n_rows]
+    return host, cols, shift
+
+
+def gram_wide_shapes():
+    """[(name, d, row0, n_rows, kwargs of gram_window)]: every Gram shape of the wide tests but the two kinds of sliced
+    launch, whose row count comes from the handle (slice_rows_of)."""
+    out = []
+    for d in GRAM_WIDE_D:
+        for row0 in (0, 1):
+            for n in GRAM_WIDE_ROWS:
+                out.append((f"d{d}-row{row0}-n{n}", d, row0, n, {"seed": 1000 * d + 10 * n + row0}))
+    out.append(("subset140of150", 140, 0, 33, {"seed": 140, "n_cols": 150, "shuffled": True}))
+    return out
+
+
+def slice_rows_of(kind, max_slices):
+    """n_rows of a sliced case: 'auto' is the first size the automatic choice splits, 'raised' the first at which a
+    forced slice of one step would need more partials than the handle keeps."""
+    return SLICE_MIN + 1 if kind == "auto" else STEP * int(max_slices) + 1
+
+
+def gram_structural_errors(win, cols, shift, slice_rows):
+    """{name: G' long double} for the window `win` [n_cols, n_rows]: the long-double Gram matrix with ONE structural
+    error each. The sums are linear in the rows, so a matrix without some rows is G minus the Gram matrix of those rows."""
+    n = win.shape[1]
+    d = len(cols)
+    G, _ = gram_ld(win, cols, shift)
+    out = {"last_row_left_out": G - gram_ld(win[:, n - 1:], cols, shift)[0]}
+    if d >= 17:  # two columns 16 apart (the same lane of neighbouring tiles) exchanged on the A side only
+        j = d - 17
+        E = G.copy()
+        E[[j, j + 16]] = E[[j + 16, j]]
+        out["columns_16_apart_exchanged"] = E
+    k = ((n + slice_rows - 1) // slice_rows) // 2  # the middle slice; the only one of an unsliced launch
+    out["slice_partial_dropped"] = G - gram_ld(win[:, k * slice_rows:(k + 1) * slice_rows], cols, shift)[0]
+    return out
+
+
+def worst_ratio(got, want, bound):
+    """max |got - want| / bound over the entries (a zero bound with a zero error counts as 0)."""
+    err = np.abs(np.asarray(got).astype(LD) - want).astype(np.float64)
+    bound = np.asarray(bound, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(err == 0, 0.0, err / bound)
+    return float(np.max(r)) if r.size else 0.0
+
+
+def affine_case(n_in, n_out, n_rows, row0, seed=0):
+    """(W [n_out, n_in], c [n_out], in_cols [n_in], host X [n_in + 7, row0 + n_rows + 2]): the inputs are a permutation
+    drawn from the wider X, whose other columns, and whose rows outside the window, hold NaN."""
+    rng = np.random.default_rng([seed, n_in, n_out, n_rows, row0])
+    n_cols = n_in + 7
+    in_cols = [int(c) for c in rng.permutation(n_cols)[:n_in]]
+    X = np.full((n_cols, row0 + n_rows + 2), np.nan)
+    X[in_cols, row0:row0 + n_rows] = rng.normal(size=(n_in, n_rows)) + 3 * rng.normal(size=(n_in, 1))
+    W = rng.normal(size=(n_out, n_in)) / np.sqrt(max(n_in, 1))
+    return W, 5 * rng.normal(size=n_out), in_cols, X
+
+
+def net_cases():
+    """The synthetic plans of the net kernels: {name, families, betas, stds, n_cols, ld, n_big}.  |beta_i| <= 1 on chains
+    and sum_i |beta_i| <= 1 on wide families keep every value O(10).  ld is the rows of the device buffer the GPU test
+    samples into (row0 3 and n_big rows fit with a sentinel row after them)."""
+    if "net" in _CACHE:
+        return _CACHE["net"]
+    rng = np.random.default_rng(20261021)
+    out = []
+
+    def add(name, families, n_cols=None, n_big=257, ld=None):
+        betas, stds = [], []
+        for fam in families:
+            p = len(fam) - 1
+            w = rng.uniform(-1, 1, p)
+            if p > 1:
+                w = w / np.abs(w).sum()
+            betas.append(np.concatenate([[3 * rng.normal()], w]))
+            stds.append(float(rng.uniform(0.5, 2.0)))
+        out.append({"name": name, "families": [list(f) for f in families], "betas": betas, "stds": stds,
+                    "n_cols": 1 + max(c for f in families for c in f) if n_cols is None else n_cols,
+                    "n_big": n_big, "ld": n_big + 6 if ld is None else ld})
+
+    add("chain_300", [[0]] + [[i, i - 1] for i in range(1, 300)])
+    add("star_300", [[c] for c in range(300)] + [[300] + list(range(300))])
+    add("max_parents", [[c] for c in range(4096)] + [[4096] + list(range(4096))], n_big=64, ld=70)
+    add("odd_first", [[1], [0, 1], [3, 0, 1], [2, 3]])
+    add("interleaved", [[0], [2, 0], [1, 2, 0], [3, 1]])
+    add("gaps", [[0], [1, 0], [2, 1], [3, 2, 0], [6, 3], [7, 6, 1], [8, 7], [9, 8, 6, 0]], n_cols=12)
+    add("dense_40", [[i] + list(range(i)) for i in range(40)])
+    _CACHE["net"] = out
+    return out
+
+
+def net_first_rows(n):
+    return (0, (1 << 33) + 5, (1 << 63) - 1 - n)
+
+
+def net_sample(case, n, first_row, seed=77, wrong_trig=False):
+    """sample_ld of a net case, cached; wrong_trig: the structural error of the negative control, an odd column
+    taking the cosine of its pair where the sine belongs."""
+    key = ("net_sample", case["name"], n, first_row, seed, wrong_trig)
+    if key not in _CACHE and n < case["n_big"] and first_row + case["n_big"] < 1 << 63:
+        X, B = net_sample(case, case["n_big"], first_row, seed, wrong_trig)  # a row depends on its stream row alone
+        _CACHE[key] = (X[:, :n], B[:, :n])
+    if key not in _CACHE:
+        normals =(lambda s, rows, col: normals_ld(s, rows, int(col) & ~1)) if wrong_trig else normals_ld
+        _CACHE[key] = sample_ld(case["families"], case["betas"], case["stds"], n, seed, first_row, n_cols=case["n_cols"],
+                                normals=normals)
+    return _CACHE[key]
+
+
+def net_logpdf(case, drop_parent=False):
+    """(X fp64 [n_cols, n_big] the rounding of the restated sample with NaN in the columns no family names, lp, bound)
+    of a net case, cached; drop_parent: the structural error, the last family with a parent scored without its last one."""
+    key = ("net_logpdf", case["name"], drop_parent)
+    if key not in _CACHE:
+        X = net_sample(case, case["n_big"], 0)[0].astype(np.float64)
+        named = sorted({c for f in case["families"] for c in f})
+        blank = [c for c in range(case["n_cols"]) if c not in named]
+        X[blank] = np.nan
+        fams, betas = [list(f) for f in case["families"]], [np.array(b) for b in case["betas"]]
+        if drop_parent:
+            f = max(i for i, fam in enumerate(fams) if len(fam) > 1)
+            fams[f], betas[f] = fams[f][:-1], betas[f][:-1]
+        _CACHE[key] = (X,) + logpdf_ld(np.nan_to_num(X), fams, betas, case["stds"])
+    return _CACHE[key]
+
+
+WIDE_MODEL = {"n_nodes": 300, "edge_prob": 0.03, "seed": 300, "graph_seed": 20261021}
+
+
+def wide_model():
+    """LinearGaussianBayesianNetwork.get_random(300 nodes, edge_prob 0.03).  The call draws its graph from numpy's UNSEEDED
+    generator (as the reference's does), so for this one call the unseeded default_rng is pinned to graph_seed: the
+    model, and with it every condition number the checks use, is the same in every run."""
+    if "wide_model" not in _CACHE:
+        from pgmpy_amd.models import LinearGaussianBayesianNetwork
+
+        real = np.random.default_rng
+        np.random.default_rng = lambda seed=None: real(WIDE_MODEL["graph_seed"] if seed is None else seed)
+        try:
+            _CACHE["wide_model"] = LinearGaussianBayesianNetwork.get_random(
+                n_nodes=WIDE_MODEL["n_nodes"], edge_prob=WIDE_MODEL["edge_prob"], seed=WIDE_MODEL["seed"])
+        finally:
+            np.random.default_rng = real
+    return _CACHE["wide_model"]

@@ -446,3 +446,89 @@ def test_launch_argument_checks(lib):
     assert affine(n_out=0) == E and affine(n_out=65536) == E and affine(ld_out=-1) == E
     assert affine(cols=(ctypes.c_int32 * 2)(0, -1)) == E
     assert "lg_affine" in N.last_error()
+
+
+# ---------------------------------------------------------------------- the wide plans: host side and negative controls
+@pytest.mark.parametrize("case", LC.net_cases(), ids=lambda c: c["name"])
+def test_net_case_plans(case):
+    """The handle's view of every synthetic plan of tests/test_lg_wide_gpu.py."""
+    from pgmpy_amd import _native as N
+    from pgmpy_amd.models._lg import NetPlan
+
+    fams = case["families"]
+    p = NetPlan(fams)
+    assert p.info.n_families == len(fams) and p.info.n_cols == 1 + max(c for f in fams for c in f) <= case["n_cols"]
+    assert p.info.max_parents == max(len(f) - 1 for f in fams) <= N.LG_MAX_PARENTS
+    assert p.n_coef == sum(len(f) + 1 for f in fams)
+    assert p.coef_off == [sum(len(g) + 1 for g in fams[:f]) for f in range(len(fams))]
+    coef = p.coef(case["betas"], case["stds"])
+    for f, fam in enumerate(fams):
+        o = p.coef_off[f]
+        assert np.array_equal(coef[o:o + len(fam)], case["betas"][f]) and coef[o + len(fam)] == case["stds"][f]
+    assert {"max_parents": N.LG_MAX_PARENTS, "star_300": 300, "chain_300": 1, "dense_40": 39}.get(case["name"], p.info.max_parents) \
+        == p.info.max_parents
+    assert case["ld"] >= 3 + case["n_big"] + 1
+
+
+def _exceeds(wrong, want, bound):
+    return LC.worst_ratio(wrong.astype(np.float64), want, bound) > 1.0
+
+
+def _gram_control(d, row0, n_rows, slice_rows, **kw):
+    host, cols, shift = LC.gram_window(d, row0, n_rows, **kw)
+    win = host[:, row0:row0 + n_rows]
+    want, A = LC.gram_ld(win, cols, shift)
+    bound = LC.gram_bound(A, n_rows)
+    wrong = LC.gram_structural_errors(win, cols, shift, slice_rows)
+    assert ("columns_16_apart_exchanged" in wrong) == (d >= 17)
+    for name, E in wrong.items():
+        assert _exceeds(E, want, bound), (name, d, row0, n_rows)
+
+
+def test_gram_bound_sees_structural_errors():
+    """The bounds carry a factor n: at every Gram shape of the wide tests a row left out, two columns of neighbouring
+    tiles exchanged on one side, and a slice's partial dropped each lie outside gram_bound."""
+    from pgmpy_amd import _native as N
+    from pgmpy_amd.models._lg import GramPlan
+
+    assert (LC.SLICE_MIN, LC.STEP) == (N.LG_SLICE_MIN, N.LG_STEP)
+    for _, d, row0, n_rows, kw in LC.gram_wide_shapes():
+        _gram_control(d, row0, n_rows, LC.SLICE_MIN, **kw)
+    for d in (3, 200):
+        p = GramPlan(list(range(d)))
+        for kind, forced in (("auto", None), ("raised", 1)):
+            n_rows = LC.slice_rows_of(kind, p.info.max_slices)
+            p.set_slice(forced or 0)
+            slice_rows, n_slices, _ = p.gram_info(n_rows)
+            assert n_slices >= 2
+            _gram_control(d, 2, n_rows, slice_rows, seed=d + n_rows, ld=n_rows + 7)
+
+
+def test_affine_bound_sees_a_dropped_input():
+    """Input 256, the first of the second launch, left out: outside affine_ld's bound wherever it exists."""
+    for n_in in (n for n in LC.AFFINE_N_IN if n > 256):
+        for n_out in LC.AFFINE_N_OUT:
+            for n_rows in LC.AFFINE_ROWS:
+                for row0 in (0, 3):
+                    W, c, in_cols, host = LC.affine_case(n_in, n_out, n_rows, row0)
+                    win = host[:, row0:row0 + n_rows]
+                    want, bound = LC.affine_ld(W, c, in_cols, win)
+                    wrong = want - np.outer(W[:, 256].astype(LD), win[in_cols[256]].astype(LD))
+                    assert _exceeds(wrong, want, bound), (n_in, n_out, n_rows, row0)
+
+
+@pytest.mark.parametrize("case", LC.net_cases(), ids=lambda c: c["name"])
+def test_net_bounds_see_structural_errors(case):
+    """The cosine where the sine belongs (every odd column, at every n and first_row of the GPU test) and one parent's
+    term missing from the density: outside the bounds of sample_ld and logpdf_ld."""
+    odd = sorted({f[0] for f in case["families"] if f[0] & 1})
+    assert odd
+    for n in (1, case["n_big"]):
+        for first_row in LC.net_first_rows(n):
+            want, bound = LC.net_sample(case, n, first_row)
+            wrong, _ = LC.net_sample(case, n, first_row, wrong_trig=True)
+            for c in odd:
+                assert _exceeds(wrong[c], want[c], bound[c]), (case["name"], n, first_row, c)
+    _, lp, bound = LC.net_logpdf(case)
+    _, wrong, _ = LC.net_logpdf(case, drop_parent=True)
+    assert (np.abs(wrong - lp).astype(np.float64) > bound).all()  # every row
