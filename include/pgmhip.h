@@ -1415,6 +1415,89 @@ int pgm_lgs_score(void *handle, const double *G, const double *shift, int32_t d,
 /* *out = I_{1 - y}(a, 1/2) by the host build of the device's function (csrc/pgm_ibeta.h) */
 int pgm_lgs_ibeta_half(double a, double y, double *out);
 
+/* ---------------------------------------------------------------- dynamic Bayesian networks
+ * Filtering, smoothing and the log-likelihood of MANY evidence sequences under one two-slice network
+ * (DynamicBayesianNetwork / DBNInference, which rebuilds and calibrates a junction tree per slice of one
+ * sequence) in one launch: a sequence is a row, its state lives in LDS.  An extension of ABI 25.
+ *
+ * DATA.  codes[(T + 1) n, ld], uint8, column-major: column t n + v is node v of slice t, a row is a
+ * sequence, PGM_EV_MISSING is "not observed in this cell".  The call reads rows [row0, row0 + n_rows).
+ *
+ * THE PLAN is made on the host from the n slice nodes' cardinalities, a `clamped` and a `queried` flag
+ * per node, the slice-0 families and the transition families (pgm_fit_family: the node, then its parents,
+ * the table in the CPD's layout).  A slice-0 family's columns are 0 .. n - 1.  A transition family's node
+ * is a column n .. 2n - 1 (slice t + 1) and its parents are columns 0 .. n - 1 (slice t) or n .. 2n - 1.
+ * Every node has exactly one family in each set.  The tables of a set lie end to end in the order given
+ * (pgm_dbn_info: off0 / off1), as in a fit plan, so the values of a fitted network are used as they are.
+ * A CLAMPED node is observed in every cell of the batch and enters only as a table offset read from the
+ * codes; a FREE node may be observed or missing per cell.  The enumerated state of a slice is the joint x
+ * of the free nodes (the last fastest), J = prod card(free) <= PGM_DBN_MAX_CONFIGS; the message between
+ * slices is over the free INTERFACE nodes (free nodes that are a slice-t parent of a transition family),
+ * S = prod of their cardinalities, S divides J.  Refused (PGM_EINVAL) before any HIP call: n outside
+ * 1 .. 255, a cardinality outside 1 .. 255, J above the cap, a family column out of range or listed
+ * twice, a cardinality that differs from the node's, a slice-t parent whose node has no slice-0 family, a
+ * node without or with two families in a set, a table or a set of tables of 2^31 entries or more.
+ *
+ * THE RECURSION, per sequence, forward in time (a_t the message, I(x) the interface part of x):
+ *   alpha_0(x)  = 1[e_0(x)] prod_v P0(x_v | pa)                       c_0 = sum alpha_0, alpha_0 /= c_0
+ *   a_t(i)      = sum_{x : I(x) = i} alpha_t(x)
+ *   alpha_t+1(x') = 1[e_t+1(x')] prod_{v: no free slice-t parent} P(x'_v | pa)
+ *                   sum_i a_t(i) prod_{v: a free slice-t parent} P(x'_v | pa(i, x')),  divided by c_t+1
+ *   loglik = sum_t log c_t = log P(e_0:T);  filter_t(v) = the marginal of alpha_t.
+ * The first product does not depend on i and is taken once per x'; an x' that contradicts the cell's
+ * evidence is 0 without being evaluated.  Backward, with beta_T = 1:
+ *   gamma_t(x) = alpha_t(x) beta_t(I(x)) / (its sum);  smooth_t(v) = the marginal of gamma_t
+ *   beta_t-1(i) = sum_x' Phi_t(i, x') beta_t(I(x')) / c_t,   Phi_t the summand of alpha_t.
+ * Only a_t (S doubles) and c_t are kept per slice, in the caller's scratch of n_rows (T + 1) (S + 1)
+ * doubles; alpha_t is recomputed from a_t-1 on the way back.  Scratch is needed for smooth only; a
+ * scratch that is too small is PGM_EINVAL (the caller splits the batch by rows).
+ *
+ * MAPPING.  One wave per workgroup.  J <= 64: 64 / pow2ceil(J) sequences share a wave, one x' per lane;
+ * J > 64: one sequence per wave, the lanes stride over x'.  alpha, a and beta live in LDS (8 (J + 2 S)
+ * + 6 n bytes per sequence; fewer sequences per wave when that would pass 160 KiB), the CPD tables and
+ * the plan's offset tables are read from global memory.  Every sum is taken in an order fixed by (J, S,
+ * card) alone, a lane's own terms in ascending order and then a butterfly over the sequence's lanes;
+ * there are no atomics on values: a sequence's outputs are bit-identical whatever else is in the batch
+ * and wherever it stands in it.
+ *
+ * OUTPUTS, each optional (NULL): filter, smooth [n_rows, T + 1, Q] fp64 with Q = sum card(queried), the
+ * queried nodes in node order, a sequence's block contiguous; loglik [n_rows]; impossible [n_rows] uint8.
+ * A clamped queried node yields its indicator.  A sequence whose evidence has probability 0 (some c_t =
+ * 0) gets impossible = 1, loglik = -inf, NaN filter marginals from that slice on and NaN smooth marginals
+ * at every slice; nothing else in the batch is affected.  PGM_EV_MISSING in a clamped column, or a code
+ * >= its cardinality anywhere, never indexes a table and makes the call return PGM_EINVAL (a device flag
+ * read back after the launch: the call synchronises the stream).  n_rows = 0 is PGM_OK and launches
+ * nothing.  pgm_dbn_plan_create and pgm_dbn_info need no device; pgm_dbn_run checks every argument on the
+ * host before any HIP call (null plan / codes / values, an fp64 pointer that is not 8-byte aligned,
+ * n_cols != n_slices n, n_slices outside 1 .. 65535, a row window outside ld).  The handle follows the
+ * rules of the plan handles. */
+#define PGM_DBN_MAX_CONFIGS 4096
+typedef struct {
+  int32_t n;              /* slice nodes */
+  int32_t n_free;
+  int32_t n_configs;      /* J */
+  int32_t n_interface;    /* S */
+  int32_t n_prev_families; /* transition families with a free slice-t parent: evaluated per (i, x') */
+  int32_t n_cur_families;  /* transition families without one: evaluated once per x' */
+  int32_t seq_per_wave;
+  int32_t block;          /* work-items per workgroup */
+  int32_t n_query;        /* Q */
+  int32_t reserved;
+  int64_t lds_bytes;      /* LDS of a workgroup */
+  int64_t values0;        /* entries of the slice-0 / the transition value buffer */
+  int64_t values1;
+  int64_t scratch_per_slice; /* doubles of scratch per sequence and slice: S + 1 */
+} pgm_dbn_info_t;
+int pgm_dbn_plan_create(const int32_t *card, const uint8_t *clamped, const uint8_t *queried, int32_t n,
+                        const pgm_fit_family *families0, int32_t n_families0, const pgm_fit_family *families1,
+                        int32_t n_families1, void **plan);
+int pgm_dbn_plan_destroy(void *plan);
+/* off0 / off1: the table offset of every family of the set; any output may be NULL */
+int pgm_dbn_info(void *plan, pgm_dbn_info_t *info, int64_t *off0, int64_t *off1);
+int pgm_dbn_run(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, int32_t n_slices,
+                const double *values0, const double *values1, double *filter, double *smooth, double *loglik,
+                uint8_t *impossible, double *scratch, int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

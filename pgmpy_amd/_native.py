@@ -298,6 +298,18 @@ class LgsInfo(ctypes.Structure):
 LGS_MAX_COND, LGS_LANE_MAX, LGS_MAX_TARGETS = 64, 7, 3
 LGS_LL, LGS_BIC, LGS_AIC = 0, 1, 2
 
+
+class DbnInfo(ctypes.Structure):
+    """pgm_dbn_info_t: the state spaces and launch geometry of a pgm_dbn plan (host-only query)."""
+    _fields_ = [("n", ctypes.c_int32), ("n_free", ctypes.c_int32), ("n_configs", ctypes.c_int32),
+                ("n_interface", ctypes.c_int32), ("n_prev_families", ctypes.c_int32), ("n_cur_families", ctypes.c_int32),
+                ("seq_per_wave", ctypes.c_int32), ("block", ctypes.c_int32), ("n_query", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("lds_bytes", ctypes.c_int64), ("values0", ctypes.c_int64),
+                ("values1", ctypes.c_int64), ("scratch_per_slice", ctypes.c_int64)]
+
+
+DBN_MAX_CONFIGS, DBN_MAX_NODES, DBN_MAX_SLICES = 4096, 255, 65535  # PGM_DBN_MAX_CONFIGS and the plan's other limits
+
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
 RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
@@ -547,6 +559,14 @@ _SIGS = {
     "pgm_lgs_pcorr": ([_P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
     "pgm_lgs_score": ([_P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
     "pgm_lgs_ibeta_half": ([ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+    "pgm_dbn_plan_create": ([ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8),
+                             ctypes.c_int32, ctypes.POINTER(FitFamily), ctypes.c_int32, ctypes.POINTER(FitFamily),
+                             ctypes.c_int32, ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_dbn_plan_destroy": ([_P], ctypes.c_int),
+    "pgm_dbn_info": ([_P, ctypes.POINTER(DbnInfo), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
+                     ctypes.c_int),
+    "pgm_dbn_run": ([_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P,
+                     _P, _P, _P, ctypes.c_int64, _P], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

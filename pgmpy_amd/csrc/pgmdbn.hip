@@ -1,0 +1,318 @@
+// pgmdbn.hip — the dynamic-network filter on the device (include/pgmhip.h "dynamic Bayesian networks"):
+// k_dbn runs the scaled forward recursion and, when asked, the backward one for a batch of evidence
+// sequences in one launch.  One wave per workgroup; a sequence owns P lanes of it (P a power of two) and
+// its alpha, message and beta vectors in LDS.  The plan (pgmdbn_plan.cpp) turned every table index into
+// three added offsets: what the clamped codes give (cl, per sequence, slice and family), what the free
+// nodes of x' give (xoff) and what the interface state gives (ioff).
+#include <math.h>
+
+#include "pgm_dbn.h"
+#include "pgm_hip_common.h"
+
+struct DbnArgs {
+  DbnLayout L;
+  const int32_t *tab;
+  const uint8_t *codes;
+  int64_t ld, row0, B;
+  int32_t T1;  // slices
+  const double *val0, *val1;
+  double *filter, *smooth, *loglik, *scratch;
+  uint8_t *impossible;
+  int32_t *err;
+};
+
+namespace {
+
+// everything a lane needs of its sequence; the LDS pointers are the sequence's own
+struct Seq {
+  const DbnArgs &a;
+  double *A, *msg, *beta;
+  int32_t *cl;
+  uint8_t *ev;  // [0, n): the codes of the slice before, [n, 2n): of the slice itself
+  int64_t seq, row;
+  int xl;
+  bool live;
+};
+
+__device__ __forceinline__ double seg_sum(double v, int P) {
+  for (int m = P >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// the codes of slices t - 1 and t, checked: a clamped code that is no state reads as state 0, a free one
+// as missing, and either raises the flag
+__device__ void load_ev(const Seq &s, int t) {
+  const DbnLayout &L = s.a.L;
+  const int32_t *card = s.a.tab + L.o_card, *clamp = s.a.tab + L.o_clamp;
+  bool bad = false;
+  for (int v = s.xl; v < L.n; v += L.P)
+    for (int h = 0; h < 2; ++h) {
+      const int ts = t - 1 + h;
+      int code = 0;
+      if (ts >= 0) {
+        code = s.a.codes[((int64_t)ts * L.n + v) * s.a.ld + s.row];
+        if (code >= card[v]) {
+          if (clamp[v])
+            bad = true, code = 0;
+          else if (code != PGM_EV_MISSING)
+            bad = true, code = PGM_EV_MISSING;
+        }
+      }
+      if (s.live) s.ev[h * L.n + v] = (uint8_t)code;
+    }
+  if (bad && s.live) atomicOr(s.a.err, 1);
+}
+
+__device__ void compute_cl(const Seq &s, int k) {
+  const DbnLayout &L = s.a.L;
+  const int32_t *ctoff = s.a.tab + L.o_ctoff[k], *ctidx = s.a.tab + L.o_ctidx[k], *ctstr = s.a.tab + L.o_ctstr[k];
+  for (int f = s.xl; f < L.n; f += L.P) {
+    int32_t o = 0;
+    for (int e = ctoff[f]; e < ctoff[f + 1]; ++e) o += (int32_t)s.ev[ctidx[e]] * ctstr[e];
+    if (s.live) s.cl[f] = o;
+  }
+}
+
+__device__ __forceinline__ bool consistent(const Seq &s, int x) {
+  const DbnLayout &L = s.a.L;
+  const int32_t *card = s.a.tab + L.o_card, *xstride = s.a.tab + L.o_xstride, *fr = s.a.tab + L.o_free;
+  for (int j = 0; j < L.n_free; ++j) {
+    const int v = fr[j];
+    const int code = s.ev[L.n + v];
+    if (code != PGM_EV_MISSING && code != x / xstride[v] % card[v]) return false;
+  }
+  return true;
+}
+
+// the factor of x that does not depend on the interface state: every slice-0 family at t = 0, the
+// transition families without a free slice-t parent after it
+__device__ __forceinline__ double local_factor(const Seq &s, int x, bool first) {
+  const DbnLayout &L = s.a.L;
+  double p = 1.0;
+  if (first) {
+    const int32_t *voff = s.a.tab + L.o_voff[0], *xoff = s.a.tab + L.o_xoff[0];
+    for (int f = 0; f < L.n; ++f) p *= s.a.val0[voff[f] + s.cl[f] + xoff[f * L.J + x]];
+  } else {
+    const int32_t *voff = s.a.tab + L.o_voff[1], *xoff = s.a.tab + L.o_xoff[1], *cur = s.a.tab + L.o_cur;
+    for (int l = 0; l < L.n_cur; ++l) {
+      const int f = cur[l];
+      p *= s.a.val1[voff[f] + s.cl[f] + xoff[f * L.J + x]];
+    }
+  }
+  return p;
+}
+
+// prod over the transition families with a free slice-t parent, at interface state i and slice state x
+__device__ __forceinline__ double trans_factor(const Seq &s, int i, int x, double p) {
+  const DbnLayout &L = s.a.L;
+  const int32_t *voff = s.a.tab + L.o_voff[1], *xoff = s.a.tab + L.o_xoff[1], *prev = s.a.tab + L.o_prev,
+                *ioff = s.a.tab + L.o_ioff;
+  for (int l = 0; l < L.n_prev; ++l) {
+    const int f = prev[l];
+    p *= s.a.val1[voff[f] + s.cl[f] + xoff[f * L.J + x] + ioff[l * L.S + i]];
+  }
+  return p;
+}
+
+// sum_i msg(i) prod(i, x), i ascending.  With few families the part of a family's offset that x fixes is taken
+// once, outside the loop over i; the products are the same operations in the same order either way.
+static constexpr int kDbnHoist = 8;
+__device__ __forceinline__ double carried(const Seq &s, int x) {
+  const DbnLayout &L = s.a.L;
+  double acc = 0.0;
+  if (L.n_prev > kDbnHoist) {
+    for (int i = 0; i < L.S; ++i) acc += trans_factor(s, i, x, s.msg[i]);
+    return acc;
+  }
+  const int32_t *voff = s.a.tab + L.o_voff[1], *xoff = s.a.tab + L.o_xoff[1], *prev = s.a.tab + L.o_prev,
+                *ioff = s.a.tab + L.o_ioff;
+  int32_t base[kDbnHoist];
+#pragma unroll
+  for (int l = 0; l < kDbnHoist; ++l) {
+    base[l] = 0;
+    if (l < L.n_prev) {
+      const int f = prev[l];
+      base[l] = voff[f] + s.cl[f] + xoff[f * L.J + x];
+    }
+  }
+  for (int i = 0; i < L.S; ++i) {
+    double p = s.msg[i];
+#pragma unroll
+    for (int l = 0; l < kDbnHoist; ++l)
+      if (l < L.n_prev) p *= s.a.val1[base[l] + ioff[l * L.S + i]];
+    acc += p;
+  }
+  return acc;
+}
+
+// the marginals of the queried nodes from A (divided by den), the states of a node in x order
+__device__ void marginals(const Seq &s, double *out, int t, double den, bool nan) {
+  const DbnLayout &L = s.a.L;
+  const int32_t *card = s.a.tab + L.o_card, *clamp = s.a.tab + L.o_clamp, *xstride = s.a.tab + L.o_xstride,
+                *qnode = s.a.tab + L.o_qnode, *qstate = s.a.tab + L.o_qstate;
+  for (int q = s.xl; q < L.Q; q += L.P) {
+    const int v = qnode[q], k = qstate[q];
+    double m = 0.0;
+    if (clamp[v]) {
+      m = s.ev[L.n + v] == k ? 1.0 : 0.0;
+    } else {
+      const int st = xstride[v], blk = st * card[v];
+      for (int hi = 0; hi < L.J; hi += blk)
+        for (int lo = 0; lo < st; ++lo) m += s.A[hi + k * st + lo];
+      m /= den;
+    }
+    if (s.live) out[(s.seq * s.a.T1 + t) * L.Q + q] = nan ? NAN : m;
+  }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kDbnBlock) void k_dbn(const DbnArgs a) {
+  extern __shared__ double lds[];
+  const DbnLayout &L = a.L;
+  const int lane = (int)threadIdx.x, P = L.P, J = L.J, S = L.S, n = L.n;
+  const int seg = lane / P;
+  const int64_t seq = (int64_t)blockIdx.x * L.spw + seg;
+  // a lane without a sequence computes on the first one's data and stores nothing
+  const bool live = seg < L.spw && seq < a.B;
+  const int sg = live ? seg : 0;
+  int32_t *cl_all = reinterpret_cast<int32_t *>(lds + (size_t)L.spw * (J + 2 * S));
+  uint8_t *ev_all = reinterpret_cast<uint8_t *>(cl_all + (size_t)L.spw * n);
+  const Seq s = {a,
+                 lds + (size_t)sg * J,
+                 lds + (size_t)L.spw * J + (size_t)sg * S,
+                 lds + (size_t)L.spw * (J + S) + (size_t)sg * S,
+                 cl_all + (size_t)sg * n,
+                 ev_all + (size_t)sg * 2 * n,
+                 live ? seq : 0,
+                 a.row0 + (live ? seq : 0),
+                 lane % P,
+                 live};
+  const int xl = s.xl, T1 = a.T1;
+  const int32_t *ix = a.tab + L.o_ix, *xperm = a.tab + L.o_xperm;
+  double *scr = a.smooth ? a.scratch + s.seq * T1 * (S + 1) : nullptr;
+
+  // ------------------------------------------------------------------ forward
+  double ll = 0.0;
+  bool dead = false;
+  for (int t = 0; t < T1; ++t) {
+    load_ev(s, t);
+    __syncthreads();
+    compute_cl(s, t ? 1 : 0);
+    if (t)
+      for (int i = xl; i < S; i += P) {
+        double m = 0.0;
+        for (int r = 0; r < L.R; ++r) m += s.A[xperm[i * L.R + r]];
+        if (live) {
+          s.msg[i] = m;
+          if (scr) scr[(t - 1) * (S + 1) + i] = m;
+        }
+      }
+    __syncthreads();
+    double part = 0.0;
+    for (int x = xl; x < J; x += P) {
+      double v = 0.0;
+      if (consistent(s, x)) {
+        v = local_factor(s, x, t == 0);
+        if (t) v *= carried(s, x);
+      }
+      if (live) s.A[x] = v;
+      part += v;
+    }
+    const double c = seg_sum(part, P);
+    if (live)
+      for (int x = xl; x < J; x += P) s.A[x] /= c;
+    if (!(c > 0.0)) dead = true;
+    ll += log(c);
+    if (scr && live && xl == 0) scr[t * (S + 1) + S] = c;
+    __syncthreads();
+    if (a.filter) marginals(s, a.filter, t, 1.0, dead);
+    __syncthreads();
+  }
+  if (live && xl == 0) {
+    if (a.loglik) a.loglik[seq] = dead ? -INFINITY : ll;
+    if (a.impossible) a.impossible[seq] = dead ? 1 : 0;
+  }
+  if (!a.smooth) return;
+
+  // ------------------------------------------------------------------ backward
+  if (live)
+    for (int i = xl; i < S; i += P) s.beta[i] = 1.0;
+  for (int t = T1 - 1; t >= 0; --t) {
+    load_ev(s, t);
+    if (t && live)
+      for (int i = xl; i < S; i += P) s.msg[i] = scr[(t - 1) * (S + 1) + i];
+    const double c = scr[t * (S + 1) + S];
+    __syncthreads();
+    compute_cl(s, t ? 1 : 0);
+    __syncthreads();
+    // gamma_t = alpha_t beta_t(I(x)), alpha_t rebuilt from the message of the slice before
+    double part = 0.0;
+    for (int x = xl; x < J; x += P) {
+      double g = 0.0;
+      if (consistent(s, x)) {
+        g = local_factor(s, x, t == 0);
+        if (t) g *= carried(s, x);
+        g = g / c * s.beta[ix[x]];
+      }
+      if (live) s.A[x] = g;
+      part += g;
+    }
+    const double gs = seg_sum(part, P);
+    __syncthreads();
+    marginals(s, a.smooth, t, gs, dead);
+    __syncthreads();
+    if (!t) break;
+    // beta_t-1(i) = sum_x' w(x') prod(i, x'), w = 1[e] local(x') beta_t(I(x')) / c_t, x' ascending
+    for (int x = xl; x < J; x += P) {
+      const double w = consistent(s, x) ? local_factor(s, x, false) * s.beta[ix[x]] / c : 0.0;
+      if (live) s.A[x] = w;
+    }
+    __syncthreads();
+    for (int i = xl; i < S; i += P) {
+      double b = 0.0;
+      for (int x = 0; x < J; ++x) {
+        const double w = s.A[x];
+        if (w != 0.0) b += trans_factor(s, i, x, w);
+      }
+      if (live) s.beta[i] = b;
+    }
+    __syncthreads();
+  }
+}
+
+extern "C" {
+
+int pgm_dbn_plan_destroy(void *plan) { return pgm_plan_destroy<DbnHandle>(plan); }
+
+int pgm_dbn_run(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, int32_t n_slices,
+                const double *values0, const double *values1, double *filter, double *smooth, double *loglik,
+                uint8_t *impossible, double *scratch, int64_t scratch_bytes, void *stream) {
+  DbnHandle *h = static_cast<DbnHandle *>(plan);
+  bool launch = false;
+  const int st = dbn_run_check(h, codes, n_cols, ld, row0, n_rows, n_slices, values0, values1, filter, smooth, loglik, scratch,
+                               scratch_bytes, &launch);
+  if (st != PGM_OK || !launch) return st;
+  const DbnPlan &p = h->p;
+  const pgmdev::Slot base[] = {pgmdev::upload(h->d_tab, p.tab)};
+  int up = h->dev.use(kHipDevOps, base);
+  if (up == PGM_OK) up = flag_reset(h->dev, stream);
+  if (up != PGM_OK) return up;
+  // above 64 KiB of dynamic LDS a kernel has to be told so before the launch
+  if (p.lds_bytes > 65536)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dbn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)p.lds_bytes));
+  DbnArgs a = {};
+  a.L = p.L, a.tab = h->d_tab, a.codes = codes, a.ld = ld, a.row0 = row0, a.B = n_rows, a.T1 = n_slices;
+  a.val0 = values0, a.val1 = values1, a.filter = filter, a.smooth = smooth, a.loglik = loglik, a.scratch = scratch;
+  a.impossible = impossible, a.err = h->dev.flag();
+  const int64_t blocks = (n_rows + p.L.spw - 1) / p.L.spw;
+  hipLaunchKernelGGL(k_dbn, dim3((unsigned)blocks), dim3(kDbnBlock), (size_t)p.lds_bytes, S(stream), a);
+  int32_t bad = 0;
+  const int rd = flag_read(h->dev, stream, &bad);
+  if (rd != PGM_OK) return rd;
+  if (bad)
+    return pgmi_fail(PGM_EINVAL, "dbn_run: a clamped cell is missing, or a code is >= its node's cardinality");
+  return PGM_OK;
+}
+}

@@ -15,8 +15,8 @@ Deviations from the reference:
 * ``state_names=None`` means the model's states, all of them, in model order (the reference infers them
   from the samples, in order of appearance, and can miss states).
 
-There is no ``DynamicBayesianNetwork`` here.  There is no CPU path: a query raises ``NativeUnavailable``
-without the library or a device.
+A ``DynamicBayesianNetwork`` is not taken here (``DBNInference`` filters and smooths it exactly).  There is no
+CPU path: a query raises ``NativeUnavailable`` without the library or a device.
 """
 import numpy as np
 

@@ -1,6 +1,7 @@
 from .ClusterGraph import ClusterGraph
 from .DiscreteBayesianNetwork import DiscreteBayesianNetwork
 from .DiscreteMarkovNetwork import DiscreteMarkovNetwork
+from .DynamicBayesianNetwork import DynamicBayesianNetwork, DynamicNode
 from .FactorGraph import FactorGraph
 from .JunctionTree import JunctionTree
 from .LinearGaussianBayesianNetwork import LinearGaussianBayesianNetwork
@@ -11,4 +12,5 @@ BayesianNetwork = DiscreteBayesianNetwork
 MarkovNetwork = DiscreteMarkovNetwork
 
 __all__ = ["ClusterGraph", "DiscreteBayesianNetwork", "BayesianNetwork", "DiscreteMarkovNetwork", "MarkovNetwork",
-           "FactorGraph", "JunctionTree", "LinearGaussianBayesianNetwork", "NaiveBayes"]
+           "DynamicBayesianNetwork", "DynamicNode", "FactorGraph", "JunctionTree", "LinearGaussianBayesianNetwork",
+           "NaiveBayes"]
