@@ -1457,6 +1457,7 @@ int pgm_lgs_ibeta_half(double a, double y, double *out);
  * + 6 n bytes per sequence; fewer sequences per wave when that would pass 160 KiB), the CPD tables and
  * the plan's offset tables are read from global memory.  Every sum is taken in an order fixed by (J, S,
  * card) alone, a lane's own terms in ascending order and then a butterfly over the sequence's lanes;
+ * the factors of a product are multiplied in node order, whatever order the families were given in;
  * there are no atomics on values: a sequence's outputs are bit-identical whatever else is in the batch
  * and wherever it stands in it.
  *

@@ -19,7 +19,8 @@ static constexpr int kDbnBlock = 64;            // one wave per workgroup: a bar
 static constexpr int64_t kDbnLdsMax = 163840;   // a workgroup may take the CU's whole LDS
 
 // What the kernel reads of a plan: offsets into one int32 table (DbnPlan::tab), and the geometry.
-// Set 0 is the slice-0 families, set 1 the transition families; a family keeps the index it was given.
+// Set 0 is the slice-0 families, set 1 the transition families; family f is the family of node f (its table
+// lies where the order given put it: voff), so products run in node order whatever order the caller used.
 struct DbnLayout {
   int32_t n, J, S, R;           // slice nodes; joint states of the free nodes; of the free interface; J / S
   int32_t P, spw;               // lanes of a sequence (a power of two <= 64); sequences per wave

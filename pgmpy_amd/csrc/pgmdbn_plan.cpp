@@ -127,12 +127,15 @@ int dbn_plan_build(const int32_t *card, const uint8_t *clamped, const uint8_t *q
   std::vector<int32_t> cur, prev, ioff;
   for (int k = 0; k < 2; ++k) {
     std::vector<int32_t> voff((size_t)n), xoff((size_t)n * Ji, 0), ctoff, ctidx, ctstr;
+    // the kernel's family f is node f's, wherever the caller listed it: the factors of a product are
+    // multiplied in node order, so the bits of a result do not depend on the order the families came in
     for (int32_t f = 0; f < n; ++f) {
-      const pgm_fit_family &F = fams[k][f];
-      voff[(size_t)f] = (int32_t)p.off[k][(size_t)f];
+      const size_t given = (size_t)fam_of[k][(size_t)f];
+      const pgm_fit_family &F = fams[k][given];
+      voff[(size_t)f] = (int32_t)p.off[k][given];
       ctoff.push_back((int32_t)ctidx.size());
       std::vector<int32_t> io;
-      int32_t stride = (int32_t)p.size[k][(size_t)f];
+      int32_t stride = (int32_t)p.size[k][given];
       for (int32_t j = 0; j < F.n_vars; ++j) {
         stride /= F.card[j];  // C order: the last variable fastest
         const int32_t c = F.col[j], v = c % n;

@@ -10,13 +10,19 @@ clamped names and a code matrix [(T + 1) n, B] in the layout the kernel reads.
 
 ``recursion(spec, clamped, ev, dtype)`` is the recursion of include/pgmhip.h ("dynamic Bayesian networks") with
 whole-array numpy sums: the joint x of the free nodes, the message over the free interface, scaling by c_t,
-beta backwards.  ``enumerate_unrolled`` multiplies every CPD of the unrolled network into one array and sums
+beta backwards.  ``fault=`` applies one of the structural errors of ``FAULTS`` to it: tests/test_dbn_cpu.py shows
+with them that the tolerance below sees such an error on every case (``fault_table``).  ``enumerate_unrolled`` multiplies every CPD of the unrolled network into one array and sums
 it, for prod card^(T + 1) <= 2^20.  Both return marginals of EVERY node, [T + 1, sum card].
 
 Tolerance (``tolerance``).  The device adds the same terms as the fp64 run of ``recursion`` in another but fixed
 order.  d, the largest deviation of the fp64 run from the long-double one relative to the largest entry, measures
 what a summation order costs on that case; the device is allowed 16 d, and never less than 64 * 2^-53.  d is a
 property of numpy's arithmetic alone (``deviation``; ``GOLDEN_D`` caches it per case): no device result enters.
+
+Cases.  ``kernel_cases()`` has the smallest shape for each branch of the kernel; ``path_cases()`` the smallest that
+reach what those stop short of (dynamic LDS above 64 KiB from both sides, the benchmarked HMM, two sequences per
+wave, 254 states, n = 255), each with the plan geometry it expects.  ``reference(case, b)`` is the long-double run
+of a sequence, computed once and shared.
 """
 import functools
 import json
@@ -113,8 +119,22 @@ def offsets(spec):
 
 
 # ------------------------------------------------------------------------------------------------ the recursion
-def recursion(spec, clamped, ev, dtype=LD):
-    """(filter [T + 1, Q], smooth [T + 1, Q], loglik, impossible) of one sequence; Q over every node."""
+# the structural errors ``recursion(fault=...)`` can make, each one a slip a kernel or its plan could make
+FAULTS = {
+    "clamped_parent_slice": "a clamped slice-t parent is read from slice t instead of t - 1",
+    "message_group": "the message is summed over the wrong interface group (a reversed)",
+    "beta_index": "gamma takes beta at the wrong interface state (the next one)",
+    "beta_no_local": "local is left out of the beta update",
+    "mask_slice0": "the evidence mask is ignored at slice 0",
+    "digit_order": "the table lookups take the free nodes' digits first-fastest instead of last-fastest",
+    "drop_prev_family": "the first transition family with a free slice-t parent is left out of the product",
+}
+
+
+def recursion(spec, clamped, ev, dtype=LD, fault=None):
+    """(filter [T + 1, Q], smooth [T + 1, Q], loglik, impossible) of one sequence; Q over every node.
+    fault: None or a key of FAULTS."""
+    assert fault is None or fault in FAULTS
     card, n = spec["card"], len(spec["card"])
     names = spec["names"]
     is_clamped = [names[v] in clamped for v in range(n)]
@@ -127,6 +147,10 @@ def recursion(spec, clamped, ev, dtype=LD):
     ishape = [card[v] for v in iface]
     idig = dict(zip(iface, np.unravel_index(np.arange(S), ishape))) if iface else {}
     ix = np.ravel_multi_index([dig[v] for v in iface], ishape) if iface else np.zeros(J, dtype=np.int64)
+    # the digits a table lookup takes: the mask, the marginals and I(x) keep the right ones
+    tdig = dig
+    if fault == "digit_order" and free:
+        tdig = dict(zip(free, np.unravel_index(np.arange(J), fshape, order="F")))
     T1 = ev.shape[0]
     ev = ev.astype(np.int64)
     for t in range(T1):
@@ -140,15 +164,17 @@ def recursion(spec, clamped, ev, dtype=LD):
             v = c % n
             before = t > 0 and c < n
             if is_clamped[v]:
-                at.append(ev[t - 1, v] if before else ev[t, v])
+                at.append(ev[t - 1, v] if before and fault != "clamped_parent_slice" else ev[t, v])
             elif before:
                 at.append(idig[v][:, None])
             else:
-                at.append(dig[v][None, :])
+                at.append(tdig[v][None, :])
         return np.broadcast_to(tab.astype(dtype)[tuple(at)], (S if with_prev else 1, J))
 
     def mask(t):
         m = np.ones(J, dtype=bool)
+        if fault == "mask_slice0" and t == 0:
+            return m
         for v in free:
             if ev[t, v] != MISSING:
                 m &= dig[v] == ev[t, v]
@@ -157,9 +183,12 @@ def recursion(spec, clamped, ev, dtype=LD):
     def factors(t):
         """(local [J], trans [S, J]) of slice t, the evidence mask folded into local."""
         local, trans = np.ones((1, J), dtype=dtype), np.ones((S, J), dtype=dtype)
+        drop = fault == "drop_prev_family"
         for cols, tab in (spec["fam1"] if t else spec["fam0"]):
             prev = t > 0 and any(c < n and not is_clamped[c] for c in cols[1:])
-            if prev:
+            if prev and drop:
+                drop = False
+            elif prev:
                 trans = trans * lookup(cols, tab, t, True)
             else:
                 local = local * lookup(cols, tab, t, False)
@@ -181,6 +210,8 @@ def recursion(spec, clamped, ev, dtype=LD):
         local, trans = factors(t)
         if t:
             a = np.array([alpha[-1][ix == i].sum() for i in range(S)], dtype=dtype)
+            if fault == "message_group":
+                a = a[::-1].copy()
             msgs.append(a)
             un = local * (a[:, None] * trans).sum(axis=0)
         else:
@@ -198,11 +229,12 @@ def recursion(spec, clamped, ev, dtype=LD):
         return filt, smooth, dtype(-np.inf), True
     beta = np.ones(S, dtype=dtype)
     for t in range(T1 - 1, -1, -1):
-        g = alpha[t] * beta[ix]
+        g = alpha[t] * beta[(ix + 1) % S if fault == "beta_index" else ix]
         smooth[t] = marginals(g / g.sum(), t)
         if t:
             local, trans = factors(t)
-            beta = (trans * (local * beta[ix] / cs[t])[None, :]).sum(axis=1)
+            w = beta[ix] / cs[t] if fault == "beta_no_local" else local * beta[ix] / cs[t]
+            beta = (trans * w[None, :]).sum(axis=1)
     return filt, smooth, loglik, False
 
 
@@ -254,8 +286,11 @@ def deviation(spec, clamped, ev):
     marginals' relative to their largest entry (1 at most), the log-likelihood's relative to max(|loglik|, 1): it
     is a sum of log c_t, and a c_t next to 1 (no evidence in the slice) gives a term next to 0 whose error is u of
     c_t, not of the term."""
-    f64, s64, l64, _ = recursion(spec, clamped, ev, np.float64)
-    fld, sld, lld, dead = recursion(spec, clamped, ev, LD)
+    return _deviation(recursion(spec, clamped, ev, np.float64), recursion(spec, clamped, ev, LD))
+
+
+def _deviation(run64, run_ld):
+    (f64, s64, l64, _), (fld, sld, lld, dead) = run64, run_ld
     if dead:
         return 0.0, 0.0
     dm = max(float(np.nanmax(np.abs(f64 - fld))), float(np.nanmax(np.abs(s64 - sld))))
@@ -268,13 +303,40 @@ def tolerance(d):
 
 
 GOLDEN_D = {}  # case name -> (d of the marginals, d of the log-likelihood), the largest over its sequences
+GOLDEN_REF = {}  # (case name, b) -> recursion(..., LD) of sequence b: computed once, shared, never written to
+
+
+def reference(case, b):
+    """The long-double run of sequence b of a case (a case's name stands for its evidence: a changed copy of a
+    case takes another name before it comes here)."""
+    key = (case["name"], int(b))
+    if key not in GOLDEN_REF:
+        GOLDEN_REF[key] = recursion(case["spec"], case["clamped"], case["ev"][b])
+    return GOLDEN_REF[key]
 
 
 def golden_d(case):
     if case["name"] not in GOLDEN_D:
-        ds = [deviation(case["spec"], case["clamped"], e) for e in case["ev"]]
+        ds = [_deviation(recursion(case["spec"], case["clamped"], e, np.float64), reference(case, b))
+              for b, e in enumerate(case["ev"])]
         GOLDEN_D[case["name"]] = (max(d[0] for d in ds), max(d[1] for d in ds))
     return GOLDEN_D[case["name"]]
+
+
+def differs(run, ref, tol_m, tol_l):
+    """Whether a run (filter, smooth, loglik, impossible) leaves the long-double one by more than the tolerance:
+    another NaN pattern or outcome, a marginal more than tol_m off, the log-likelihood more than tol_l (relative
+    to max(|loglik|, 1))."""
+    (f, s, l, dead), (wf, ws, wl, wdead) = run, ref
+    if dead != wdead:
+        return True
+    for got, want in ((f, wf), (s, ws)):
+        if not np.array_equal(np.isnan(got), np.isnan(want)):
+            return True
+        ok = ~np.isnan(want)
+        if ok.any() and float(np.abs(got[ok] - want[ok]).max()) > tol_m:
+            return True
+    return (not dead) and float(abs(l - wl) / max(abs(wl), LD(1))) > tol_l
 
 
 # ------------------------------------------------------------------------------------------------ cases
@@ -326,8 +388,9 @@ def kernel_cases():
     out = []
     doc = doc_spec()
     # J = 2 (Z free), T = 0, 1, 2 and batch sizes that are no multiple of the 32 sequences of a wave
-    for T, B in ((0, 1), (1, 63), (2, 130)):
-        out.append(_case(f"doc_J2_T{T}_B{B}", doc, ["X", "Y"], T, B, 10 + T, hide=0.3))
+    # (the seed of the one-sequence case is one that observes Z: with Z hidden no fault of FAULTS shows at T = 0)
+    for T, B, seed in ((0, 1, 13), (1, 63, 11), (2, 130, 12)):
+        out.append(_case(f"doc_J2_T{T}_B{B}", doc, ["X", "Y"], T, B, seed, hide=0.3))
     # J = 1: everything clamped, the log-likelihood alone
     out.append(_case("all_clamped_J1", doc, ["X", "Y", "Z"], 2, 63, 20))
     # every node free: J = 8 > S = 2, cells observed and missing at random, then two slices of prediction
@@ -359,6 +422,96 @@ def kernel_cases():
     # a deterministic CPD: zeros in the tables
     out.append(_case("deterministic", make_spec(seed=80, deterministic=("X",), **DOC), ["Y"], 2, 63, 81, hide=0.5))
     return {c["name"]: c for c in out}
+
+
+def _n255_spec():
+    """255 binary nodes: every node its own chain, every third an intra-slice parent of the next, every fifth an
+    inter-slice parent of the node two on."""
+    names = [f"N{i:03d}" for i in range(255)]
+    intra = [(names[i], names[i + 1]) for i in range(0, 254, 3)]
+    inter = [(nm, nm) for nm in names] + [(names[i], names[i + 2]) for i in range(1, 253, 5)]
+    return make_spec(names=names, card=[2] * 255, intra=intra, inter=inter, seed=130)
+
+
+@functools.lru_cache(maxsize=None)
+def path_cases():
+    """name -> case: the smallest shapes that reach the paths kernel_cases() stops short of.  ``expect`` is what
+    makes a case the case it claims to be: the plan's J, S, sequences per wave, LDS bytes, families with / without a
+    free slice-t parent.  The tests assert it from plan.info, so a shape that misses its path fails."""
+    out = []
+
+    def add(case, **expect):
+        out.append(dict(case, expect=expect))
+
+    # the benchmarked shape (tools/dbn_bench.py): 8 sequences per wave, 70 = 8 full waves and 6 of the ninth's 8
+    hmm = hmm_spec()
+    add(_case("hmm_J8_S8_n9", hmm, hmm["names"][1:], 3, 70, 110, hide=0.5),
+        J=8, S=8, spw=8, lds=8 * (8 * 24 + 6 * 9), n_prev=1, n_cur=8)
+    # P = 32 > J = 30: two sequences per wave, two idle lanes each; S = 6, R = 5; cardinalities 2, 3, 5
+    mixed = make_spec(names=["A", "B", "C", "O"], card=[2, 3, 5, 2], intra=[("A", "C"), ("C", "O")],
+                      inter=[("A", "A"), ("B", "B"), ("B", "C")], seed=112)
+    add(_case("mixed_J30_S6", mixed, ["O"], 2, 5, 113, hide=0.5),
+        J=30, S=6, spw=2, lds=2 * (8 * (30 + 12) + 6 * 4), n_prev=3, n_cur=1)
+    # 254 states, the most a uint8 code holds beside MISSING; state 253 observed
+    wide = make_spec(names=["H", "O"], card=[254, 2], intra=[("H", "O")], inter=[("H", "H")], seed=120)
+    c254 = _case("card254", wide, ["O"], 2, 3, 121, hide=0.5)
+    c254["ev"][0, 1, 0] = 253
+    c254["codes"] = to_codes(c254["ev"])
+    add(c254, J=254, S=254, spw=1, lds=8 * 3 * 254 + 6 * 2, n_prev=1, n_cur=1)
+    # n at its limit, J = 1: 64 sequences per wave at 24 + 6 n bytes each, past 64 KiB of dynamic LDS
+    n255 = _n255_spec()
+    add(_case("n255_all_clamped", n255, n255["names"], 2, 70, 131),
+        J=1, S=1, spw=64, lds=64 * (24 + 6 * 255), n_prev=0, n_cur=255)
+    # past 64 KiB with one sequence per wave: J = S = 16 * 16 * 12, every free node in the interface
+    big = make_spec(names=["A", "B", "C", "O"], card=[16, 16, 12, 2], intra=[("A", "O"), ("B", "O"), ("C", "O")],
+                    inter=[("A", "A"), ("B", "B"), ("C", "C"), ("A", "B")], seed=140)
+    add(_case("J3072_S3072", big, ["O"], 1, 2, 141, hide=0.5),
+        J=3072, S=3072, spw=1, lds=8 * 3 * 3072 + 6 * 4, n_prev=3, n_cur=1)
+    return {c["name"]: c for c in out}
+
+
+def all_cases():
+    """kernel_cases() and path_cases() in one table."""
+    return {**kernel_cases(), **path_cases()}
+
+
+def has_clamped_prev_parent(case):
+    """Whether some transition family has a clamped slice-t parent."""
+    spec, n = case["spec"], len(case["spec"]["card"])
+    return any(c < n and spec["names"][c] in case["clamped"] for cols, _ in spec["fam1"] for c in cols[1:])
+
+
+def has_free_interface(case):
+    spec, n = case["spec"], len(case["spec"]["card"])
+    return any(c < n and spec["names"][c] not in case["clamped"] for cols, _ in spec["fam1"] for c in cols[1:])
+
+
+# the faults run on J3072_S3072 (one sequence), where a run of the restatement takes a second
+CHEAP_FAULTS = ("message_group", "beta_index", "digit_order")
+FAULT_TABLE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "dbn_fault_table.json")
+
+
+def faults_of(case):
+    """The faults that can be applied to a case."""
+    names = [f for f in FAULTS if f != "clamped_parent_slice" or has_clamped_prev_parent(case)]
+    return [f for f in names if f in CHEAP_FAULTS] if case["name"] == "J3072_S3072" else names
+
+
+def fault_row(case):
+    """{fault: whether tolerance(golden_d(case)) tells the faulted fp64 run from the long-double one on one of the
+    first 16 sequences of the case (J3072_S3072: the first)}."""
+    dm, dl = golden_d(case)
+    tol_m, tol_l = tolerance(dm), tolerance(dl)
+    rows = range(1 if case["name"] == "J3072_S3072" else min(case["B"], 16))
+    with np.errstate(all="ignore"):
+        return {f: any(differs(recursion(case["spec"], case["clamped"], case["ev"][b], np.float64, fault=f),
+                               reference(case, b), tol_m, tol_l) for b in rows) for f in faults_of(case)}
+
+
+def fault_table():
+    """{case: fault_row(case)} over all_cases(): what profiles/dbn_fault_table.json records (a fault that cannot
+    be applied to a case is absent from its row).  ``python -m tests.dbn_cases`` writes the file."""
+    return {name: fault_row(case) for name, case in all_cases().items()}
 
 
 def small_cases():
@@ -422,3 +575,17 @@ def golden_spec(golden, name):
             "fam1": [(f["cols"], np.asarray(f["table"], dtype=np.float64)) for f in g["fam1"]]}
     spec["order"] = _topological(n, [(g["names"].index(p), g["names"].index(c)) for p, c in g["intra"]])
     return spec
+
+
+def fault_table_record():
+    """The content of profiles/dbn_fault_table.json."""
+    return {"what": "whether dbn_cases.tolerance(golden_d(case)) tells recursion(fp64, fault=...) from the long-double "
+                    "run on one of the first 16 sequences of a case; a fault that cannot be applied to a case is absent",
+            "faults": FAULTS, "table": fault_table()}
+
+
+if __name__ == "__main__":
+    with open(FAULT_TABLE, "w") as out:
+        json.dump(fault_table_record(), out, indent=1)
+        out.write("\n")
+    print(f"wrote {FAULT_TABLE}")

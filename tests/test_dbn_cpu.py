@@ -214,6 +214,86 @@ def test_plan_geometry(card, clamped, J, S, spw, prev, cur):
     assert p.scratch_bytes(10, 7) == 10 * 7 * (S + 1) * 8
 
 
+def _spec_families(spec):
+    """The two family sets of a spec as (columns, cardinalities)."""
+    n, card = len(spec["card"]), spec["card"]
+    return tuple([(list(cols), [card[c % n] for c in cols]) for cols, _ in spec[k]] for k in ("fam0", "fam1"))
+
+
+@pytest.mark.parametrize("name,J,S,spw,prev,cur,lds", [
+    ("hmm_J8_S8_n9", 8, 8, 8, 1, 8, 1968),
+    ("mixed_J30_S6", 30, 6, 2, 3, 1, 720),
+    ("card254", 254, 254, 1, 1, 1, 6108),
+    ("n255_all_clamped", 1, 1, 64, 0, 255, 99456),
+    ("J3072_S3072", 3072, 3072, 1, 3, 1, 73752),
+])
+def test_path_case_geometry(name, J, S, spw, prev, cur, lds):
+    """Each case of dbn_cases.path_cases() reaches the path it is there for, and says so in its `expect`."""
+    case = C.path_cases()[name]
+    spec = case["spec"]
+    fam0, fam1 = _spec_families(spec)
+    i = _plan(spec["card"], [v in case["clamped"] for v in spec["names"]], fam0, fam1).info
+    assert (i.n_configs, i.n_interface, i.seq_per_wave, i.n_prev_families, i.n_cur_families, i.lds_bytes) == (J, S, spw, prev, cur, lds)
+    assert case["expect"] == dict(J=J, S=S, spw=spw, n_prev=prev, n_cur=cur, lds=lds)
+    assert (lds > 65536) == (name in ("n255_all_clamped", "J3072_S3072"))
+    assert i.n == len(spec["card"]) <= 255 and case["codes"].shape == ((case["T"] + 1) * i.n, case["B"])
+    if name == "card254":
+        assert (case["ev"][:, :, 0] == 253).any()
+    if name == "hmm_J8_S8_n9":
+        assert case["B"] % spw  # the last wave is partly idle
+
+
+def test_plan_lds_at_the_64k_edge():
+    """An all-clamped chain takes 64 (24 + 6 n) bytes: below 64 KiB at n = 166, above it from n = 167."""
+    for n, lds in ((166, 65280), (167, 65664)):
+        fam0, fam1 = _chain_families([2] * n)
+        i = _plan([2] * n, [1] * n, fam0, fam1).info
+        assert (i.n_configs, i.seq_per_wave, i.lds_bytes) == (1, 64, lds) and lds == 64 * (24 + 6 * n)
+    assert 65280 <= 65536 < 65664
+
+
+@pytest.mark.parametrize("name", ["iface_clamped_2_3", "two_iface"])
+def test_plan_family_order(name):
+    """Families given out of node order: the same geometry, each table where the given order put it."""
+    case = C.kernel_cases()[name]
+    spec = case["spec"]
+    n, clamped = len(spec["card"]), [v in case["clamped"] for v in spec["names"]]
+    fam0, fam1 = _spec_families(spec)
+    perm0, perm1 = list(range(n))[::-1], list(range(1, n)) + [0]
+    a = _plan(spec["card"], clamped, fam0, fam1)
+    b = _plan(spec["card"], clamped, [fam0[i] for i in perm0], [fam1[i] for i in perm1])
+    for field in ("n_configs", "n_interface", "seq_per_wave", "n_prev_families", "n_cur_families", "lds_bytes", "values0", "values1"):
+        assert getattr(a.info, field) == getattr(b.info, field), field
+    for perm, fams, off in ((perm0, fam0, b.offsets0), (perm1, fam1, b.offsets1)):
+        sizes = [int(np.prod(fams[i][1])) for i in perm]
+        assert off == list(np.cumsum([0] + sizes[:-1]))
+
+
+def test_tolerance_sees_structural_faults():
+    """Every fault of dbn_cases.FAULTS, applied to the fp64 run of the restatement, against the long-double run
+    under tolerance(golden_d(case)), on every case (up to 16 sequences; J3072_S3072: one sequence, CHEAP_FAULTS).
+    The table is profiles/dbn_fault_table.json; the conditions below are what it has to meet."""
+    import json
+
+    table = C.fault_table()
+    cases = C.all_cases()
+    assert set(table) == set(cases) and len(C.FAULTS) == 7
+    for name, row in table.items():
+        assert any(row.values()), f"{name} sees no fault: make it stronger"
+        case = cases[name]
+        if case["T"] >= 1 and C.has_free_interface(case):
+            assert row["message_group"] and row["beta_index"], name
+        assert ("clamped_parent_slice" in row) == C.has_clamped_prev_parent(case)
+        if "clamped_parent_slice" in row:
+            assert row["clamped_parent_slice"], name
+    for fault in C.FAULTS:
+        seen = [name for name, row in table.items() if row.get(fault)]
+        assert len(seen) >= 3, (fault, seen)
+    with open(C.FAULT_TABLE) as f:
+        recorded = json.load(f)
+    assert recorded["table"] == table and recorded["faults"] == C.FAULTS
+
+
 def test_plan_interface_smaller_than_joint():
     # A_0 -> A_1 alone carries over; B hangs off A within the slice: S = 3 < J = 15
     p = _plan([3, 5], [0, 0], [([0], [3]), ([1, 0], [5, 3])], [([2, 0], [3, 3]), ([3, 2], [5, 3])])
