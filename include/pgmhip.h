@@ -1499,6 +1499,48 @@ int pgm_dbn_run(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, in
                 const double *values0, const double *values1, double *filter, double *smooth, double *loglik,
                 uint8_t *impossible, double *scratch, int64_t scratch_bytes, void *stream);
 
+/* ---------------------------------------------------------------- dynamic Bayesian networks: MAP sequences
+ * pgm_dbn_viterbi: the single most probable completion of every sequence of the batch, in one launch, on
+ * the plan, the data layout and the mapping of pgm_dbn_run (the queried flags are not used).  One more
+ * extension symbol of ABI 25; pgm_dbn_info_t and the other pgm_dbn_* calls are as they were.
+ *
+ * THE RECURSION, per sequence: the forward one with max for sum, and a backpointer per state.
+ *   delta_0(x)    = 1[e_0(x)] prod_v P0(x_v | pa)                  c_0 = max_x delta_0, delta_0 /= c_0
+ *   m_t(i)        = max_{x : I(x) = i} delta_t(x);   argx_t(i) = the lowest such x that attains it
+ *   delta_t+1(x') = 1[e_t+1(x')] prod_{v: no free slice-t parent} P(x'_v | pa)
+ *                   max_i m_t(i) prod_{v: a free slice-t parent} P(x'_v | pa(i, x'))
+ *   psi_t+1(x')   = the lowest i that attains that max;   bp_t+1(x') = argx_t(psi_t+1(x'))
+ *   c_t+1 = max_x' delta_t+1, delta_t+1 /= c_t+1;   logmap = sum_t log c_t
+ *   backtrack: x*_T = the lowest x that attains max delta_T;   x*_t-1 = bp_t(x*_t).
+ * logmap = log max_x P(x_0:T, e_0:T): the joint with the evidence, not the conditional.  An x' that
+ * contradicts its cell's evidence is 0 without a table read; the factors of a product are multiplied in node
+ * order.  Marginal MAP over a subset of the nodes is not this: every free cell is maximised over.
+ *
+ * TIES go to the lowest index everywhere: a lane keeps its first maximum (strict >) over its ascending
+ * indices; the lanes of a sequence are combined by a butterfly over (value, index) in which the larger
+ * value wins and the lower index on equality, an operation that commutes, so every lane holds the same
+ * pair.  No atomics on values.  A sequence's outputs are bit-identical whatever else is in the batch,
+ * wherever it stands in it and however the caller splits the batch by rows.
+ *
+ * SCRATCH: the backpointers, full states as uint16 (J <= 4096): n_rows T J 2 bytes for T + 1 = n_slices
+ * slices (slice 0 has none), 2-byte aligned; the layout is private to the kernel.  A scratch that is too
+ * small is PGM_EINVAL (the caller splits the batch by rows); n_slices = 1 needs none.  LDS is the plan's
+ * lds_bytes: delta in alpha's place, m in the message's, argx in beta's.
+ *
+ * OUTPUTS.  path, uint8, column-major [(T + 1) n, ld_out] like codes: column t n + v, row row0_out + r for
+ * row r of the window; a free node gets its digit of x*_t (the evidence wherever the cell was observed), a
+ * clamped node its code, so path is a complete code matrix.  logmap [n_rows] fp64 and impossible [n_rows]
+ * uint8, each optional (NULL).  A sequence whose evidence has probability 0 (some c_t not > 0): impossible
+ * = 1, logmap = -inf, PGM_EV_MISSING in every free cell of its path, its clamped cells copied; nothing
+ * else in the batch is affected.  Bad codes are treated as in pgm_dbn_run: they never index a table and
+ * the call returns PGM_EINVAL after the launch.  Checked on the host before any HIP call (PGM_EINVAL): a
+ * null plan / codes / values / path, an fp64 pointer that is not 8-byte aligned, n_cols != n_slices n,
+ * n_slices outside 1 .. 65535, a codes or a path row window outside its leading dimension, a scratch that
+ * is too small.  n_rows = 0 is PGM_OK and launches nothing. */
+int pgm_dbn_viterbi(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, int32_t n_slices,
+                    const double *values0, const double *values1, uint8_t *path, int64_t ld_out, int64_t row0_out,
+                    double *logmap, uint8_t *impossible, void *scratch, int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -567,6 +567,8 @@ _SIGS = {
                      ctypes.c_int),
     "pgm_dbn_run": ([_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P,
                      _P, _P, _P, ctypes.c_int64, _P], ctypes.c_int),
+    "pgm_dbn_viterbi": ([_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, _P, _P, _P,
+                         ctypes.c_int64, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -32,7 +32,7 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmlg_plan.cpp",    # linear-Gaussian networks: column / family validation, tile groups, slice choice, argument checks (host only)
     "pgmlgs.hip",        # Gaussian structure learning: partial correlations and Gaussian scores from the Gram matrix, their C-ABI
     "pgmlgs_plan.cpp",   # Gaussian structure learning: job validation, buckets, argument checks, the host p-value (host only)
-    "pgmdbn.hip",        # dynamic networks: the fused filter / smoother kernel for a batch of sequences, its C-ABI
+    "pgmdbn.hip",        # dynamic networks: the fused filter / smoother kernel and the Viterbi kernel for a batch of sequences, their C-ABI
     "pgmdbn_plan.cpp",   # dynamic networks: node / family validation, offset tables, launch geometry, argument checks (host only)
     "pgmdq.cpp",        # direct AQL dispatch (host code, HSA runtime)
     "pgmpm.cpp",         # plan-specialised batched-BP steps: hipRTC, code-object cache, bound launches (host code)

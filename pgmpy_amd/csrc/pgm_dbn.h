@@ -1,7 +1,8 @@
 // pgm_dbn.h — private interface between the two units of the dynamic-network filter (include/pgmhip.h
 // "dynamic Bayesian networks"): pgmdbn_plan.cpp (host only: validation of the slice nodes and the two
-// family sets, the offset tables, the launch geometry, the argument checks of pgm_dbn_run) and pgmdbn.hip
-// (k_dbn, the device side of the handle, the launch).  Not part of include/pgmhip.h.
+// family sets, the offset tables, the launch geometry, the argument checks of pgm_dbn_run and pgm_dbn_viterbi)
+// and pgmdbn.hip (k_dbn, k_dbn_viterbi, the device side of the handle, the launches).  Not part of
+// include/pgmhip.h.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -60,3 +61,11 @@ PGM_DBN_LOCAL int dbn_run_check(const DbnHandle *h, const uint8_t *codes, int32_
                                 int64_t n_rows, int32_t n_slices, const double *values0, const double *values1,
                                 const double *filter, const double *smooth, const double *loglik, const double *scratch,
                                 int64_t scratch_bytes, bool *launch);
+// the checks of pgm_dbn_viterbi (no HIP call); the backpointers take dbn_viterbi_scratch(...) bytes
+static inline double dbn_viterbi_scratch(int64_t n_rows, int32_t n_slices, int32_t J) {
+  return (double)n_rows * (n_slices - 1) * J * 2.0;
+}
+PGM_DBN_LOCAL int dbn_viterbi_check(const DbnHandle *h, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0,
+                                    int64_t n_rows, int32_t n_slices, const double *values0, const double *values1,
+                                    const uint8_t *path, int64_t ld_out, int64_t row0_out, const double *logmap,
+                                    const void *scratch, int64_t scratch_bytes, bool *launch);

@@ -3,7 +3,8 @@
 // sequences in one launch.  One wave per workgroup; a sequence owns P lanes of it (P a power of two) and
 // its alpha, message and beta vectors in LDS.  The plan (pgmdbn_plan.cpp) turned every table index into
 // three added offsets: what the clamped codes give (cl, per sequence, slice and family), what the free
-// nodes of x' give (xoff) and what the interface state gives (ioff).
+// nodes of x' give (xoff) and what the interface state gives (ioff).  k_dbn_viterbi, further down, is the
+// max-product recursion on the same plan with backpointers and a backtrack: the most probable sequence.
 #include <math.h>
 
 #include "pgm_dbn.h"
@@ -281,6 +282,170 @@ __global__ __launch_bounds__(kDbnBlock) void k_dbn(const DbnArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------- Viterbi
+// k_dbn_viterbi — the max-product form of the forward pass and the backtrack, one launch (include/pgmhip.h
+// "dynamic Bayesian networks: MAP sequences").  The plan, the mapping and the LDS layout are k_dbn's: delta_t
+// lies where alpha_t does, m_t where the message does, and argx_t (S int32) in the beta region.
+// Backpointers: bp, uint16 (J <= 4096), [t - 1][sequence of the launch][J] for t = 1 .. T: the state of
+// slice t - 1 that the best path into state x of slice t comes from.  The sequences of a wave write
+// neighbouring runs of J entries per slice; the backtrack is one dependent load per slice, the same
+// address in every lane of the sequence.  The layout is private to this kernel.
+struct DbnVitArgs {
+  DbnArgs a;  // filter, smooth and scratch unused; loglik is logmap
+  uint8_t *path;
+  int64_t ld_out, row0_out;
+  uint16_t *bp;
+};
+
+namespace {
+
+// max_i msg(i) prod(i, x), i ascending, the first maximum kept (strict >); *psi: that i.  The products are
+// carried()'s: the same operations in the same order.
+__device__ __forceinline__ double carried_max(const Seq &s, int x, int *psi) {
+  const DbnLayout &L = s.a.L;
+  double best = -1.0;
+  int at = 0;
+  if (L.n_prev > kDbnHoist) {
+    for (int i = 0; i < L.S; ++i) {
+      const double p = trans_factor(s, i, x, s.msg[i]);
+      if (p > best) best = p, at = i;
+    }
+    *psi = at;
+    return best;
+  }
+  const int32_t *voff = s.a.tab + L.o_voff[1], *xoff = s.a.tab + L.o_xoff[1], *prev = s.a.tab + L.o_prev,
+                *ioff = s.a.tab + L.o_ioff;
+  int32_t base[kDbnHoist];
+#pragma unroll
+  for (int l = 0; l < kDbnHoist; ++l) {
+    base[l] = 0;
+    if (l < L.n_prev) {
+      const int f = prev[l];
+      base[l] = voff[f] + s.cl[f] + xoff[f * L.J + x];
+    }
+  }
+  for (int i = 0; i < L.S; ++i) {
+    double p = s.msg[i];
+#pragma unroll
+    for (int l = 0; l < kDbnHoist; ++l)
+      if (l < L.n_prev) p *= s.a.val1[base[l] + ioff[l * L.S + i]];
+    if (p > best) best = p, at = i;
+  }
+  *psi = at;
+  return best;
+}
+
+// the maximum over the sequence's lanes and the lowest index that attains it: the larger value wins, the
+// lower index on equality; the operation commutes, so every lane ends with the same pair
+__device__ __forceinline__ void seg_argmax(double &v, int &at, int P) {
+  for (int m = P >> 1; m > 0; m >>= 1) {
+    const double ov = __shfl_xor(v, m, 64);
+    const int oat = __shfl_xor(at, m, 64);
+    if (ov > v || (ov == v && oat < at)) v = ov, at = oat;
+  }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kDbnBlock) void k_dbn_viterbi(const DbnVitArgs va) {
+  extern __shared__ double lds[];
+  const DbnArgs &a = va.a;
+  const DbnLayout &L = a.L;
+  const int lane = (int)threadIdx.x, P = L.P, J = L.J, S = L.S, n = L.n;
+  const int seg = lane / P;
+  const int64_t seq = (int64_t)blockIdx.x * L.spw + seg;
+  // a lane without a sequence computes on the first one's data and stores nothing
+  const bool live = seg < L.spw && seq < a.B;
+  const int sg = live ? seg : 0;
+  int32_t *cl_all = reinterpret_cast<int32_t *>(lds + (size_t)L.spw * (J + 2 * S));
+  uint8_t *ev_all = reinterpret_cast<uint8_t *>(cl_all + (size_t)L.spw * n);
+  const Seq s = {a,
+                 lds + (size_t)sg * J,
+                 lds + (size_t)L.spw * J + (size_t)sg * S,
+                 lds + (size_t)L.spw * (J + S) + (size_t)sg * S,
+                 cl_all + (size_t)sg * n,
+                 ev_all + (size_t)sg * 2 * n,
+                 live ? seq : 0,
+                 a.row0 + (live ? seq : 0),
+                 lane % P,
+                 live};
+  int32_t *argx = reinterpret_cast<int32_t *>(s.beta);
+  const int xl = s.xl, T1 = a.T1;
+  const int32_t *card = a.tab + L.o_card, *clamp = a.tab + L.o_clamp, *xstride = a.tab + L.o_xstride,
+                *fr = a.tab + L.o_free, *xperm = a.tab + L.o_xperm;
+  const int64_t orow = va.row0_out + s.seq;
+
+  // ------------------------------------------------------------------ forward
+  double lm = 0.0;
+  bool dead = false;
+  int xbest = 0;
+  for (int t = 0; t < T1; ++t) {
+    load_ev(s, t);
+    __syncthreads();
+    compute_cl(s, t ? 1 : 0);
+    if (live)
+      for (int v = xl; v < n; v += P)
+        if (clamp[v]) va.path[((int64_t)t * n + v) * va.ld_out + orow] = s.ev[n + v];
+    if (t)
+      for (int i = xl; i < S; i += P) {
+        // the x of a group ascend along r: the first maximum is the lowest x
+        int at = xperm[i * L.R];
+        double m = s.A[at];
+        for (int r = 1; r < L.R; ++r) {
+          const int x = xperm[i * L.R + r];
+          const double v = s.A[x];
+          if (v > m) m = v, at = x;
+        }
+        if (live) s.msg[i] = m, argx[i] = at;
+      }
+    __syncthreads();
+    uint16_t *bp = t ? va.bp + ((int64_t)(t - 1) * a.B + s.seq) * J : nullptr;
+    double best = -1.0;
+    int at = 0x7fffffff;
+    for (int x = xl; x < J; x += P) {
+      double v = 0.0;
+      int from = 0;
+      if (consistent(s, x)) {
+        v = local_factor(s, x, t == 0);
+        if (t) {
+          int psi;
+          v *= carried_max(s, x, &psi);
+          from = argx[psi];
+        }
+      }
+      if (live) {
+        s.A[x] = v;
+        if (t) bp[x] = (uint16_t)from;
+      }
+      if (v > best) best = v, at = x;
+    }
+    seg_argmax(best, at, P);
+    const double c = best;
+    if (live)
+      for (int x = xl; x < J; x += P) s.A[x] /= c;
+    if (!(c > 0.0)) dead = true;
+    lm += log(c);
+    xbest = at;
+    __syncthreads();
+  }
+  if (!live) return;
+  if (xl == 0) {
+    if (a.loglik) a.loglik[seq] = dead ? -INFINITY : lm;
+    if (a.impossible) a.impossible[seq] = dead ? 1 : 0;
+  }
+
+  // ------------------------------------------------------------------ backtrack
+  // (no barrier and no LDS from here on: the lanes of a sequence walk the same states)
+  int x = xbest;
+  for (int t = T1 - 1; t >= 0; --t) {
+    for (int j = xl; j < L.n_free; j += P) {
+      const int v = fr[j];
+      va.path[((int64_t)t * n + v) * va.ld_out + orow] = dead ? (uint8_t)PGM_EV_MISSING : (uint8_t)(x / xstride[v] % card[v]);
+    }
+    if (t && !dead) x = va.bp[((int64_t)(t - 1) * a.B + seq) * J + x];
+  }
+}
+
 extern "C" {
 
 int pgm_dbn_plan_destroy(void *plan) { return pgm_plan_destroy<DbnHandle>(plan); }
@@ -313,6 +478,38 @@ int pgm_dbn_run(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, in
   if (rd != PGM_OK) return rd;
   if (bad)
     return pgmi_fail(PGM_EINVAL, "dbn_run: a clamped cell is missing, or a code is >= its node's cardinality");
+  return PGM_OK;
+}
+
+int pgm_dbn_viterbi(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, int32_t n_slices,
+                    const double *values0, const double *values1, uint8_t *path, int64_t ld_out, int64_t row0_out,
+                    double *logmap, uint8_t *impossible, void *scratch, int64_t scratch_bytes, void *stream) {
+  DbnHandle *h = static_cast<DbnHandle *>(plan);
+  bool launch = false;
+  const int st = dbn_viterbi_check(h, codes, n_cols, ld, row0, n_rows, n_slices, values0, values1, path, ld_out, row0_out, logmap,
+                                   scratch, scratch_bytes, &launch);
+  if (st != PGM_OK || !launch) return st;
+  const DbnPlan &p = h->p;
+  const pgmdev::Slot base[] = {pgmdev::upload(h->d_tab, p.tab)};
+  int up = h->dev.use(kHipDevOps, base);
+  if (up == PGM_OK) up = flag_reset(h->dev, stream);
+  if (up != PGM_OK) return up;
+  // the attribute is a kernel's own: k_dbn having been told does not cover this one
+  if (p.lds_bytes > 65536)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dbn_viterbi), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)p.lds_bytes));
+  DbnVitArgs va = {};
+  DbnArgs &a = va.a;
+  a.L = p.L, a.tab = h->d_tab, a.codes = codes, a.ld = ld, a.row0 = row0, a.B = n_rows, a.T1 = n_slices;
+  a.val0 = values0, a.val1 = values1, a.loglik = logmap, a.impossible = impossible, a.err = h->dev.flag();
+  va.path = path, va.ld_out = ld_out, va.row0_out = row0_out, va.bp = static_cast<uint16_t *>(scratch);
+  const int64_t blocks = (n_rows + p.L.spw - 1) / p.L.spw;
+  hipLaunchKernelGGL(k_dbn_viterbi, dim3((unsigned)blocks), dim3(kDbnBlock), (size_t)p.lds_bytes, S(stream), va);
+  int32_t bad = 0;
+  const int rd = flag_read(h->dev, stream, &bad);
+  if (rd != PGM_OK) return rd;
+  if (bad)
+    return pgmi_fail(PGM_EINVAL, "dbn_viterbi: a clamped cell is missing, or a code is >= its node's cardinality");
   return PGM_OK;
 }
 }

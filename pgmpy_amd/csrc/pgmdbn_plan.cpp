@@ -1,7 +1,7 @@
 // pgmdbn_plan.cpp — the host side of the dynamic-network filter (include/pgmhip.h "dynamic Bayesian
 // networks"): validation of the slice nodes and the two family sets, the offset tables the kernel reads, the
-// launch geometry and the argument checks of pgm_dbn_run.  No HIP call and no HIP include: ctypes drives all
-// of it without a device.  The kernel and the launch are pgmdbn.hip.
+// launch geometry and the argument checks of pgm_dbn_run and pgm_dbn_viterbi.  No HIP call and no HIP include:
+// ctypes drives all of it without a device.  The kernels and the launches are pgmdbn.hip.
 #include <algorithm>
 #include <new>
 
@@ -209,6 +209,39 @@ int dbn_run_check(const DbnHandle *h, const uint8_t *codes, int32_t n_cols, int6
       return pgmi_failf(PGM_EINVAL, "dbn_run: smooth needs %.0f bytes of scratch (n_rows x slices x (S + 1) doubles), %lld given",
                         need, (long long)scratch_bytes);
   }
+  *launch = n_rows > 0;
+  return PGM_OK;
+}
+
+int dbn_viterbi_check(const DbnHandle *h, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
+                      int32_t n_slices, const double *values0, const double *values1, const uint8_t *path, int64_t ld_out,
+                      int64_t row0_out, const double *logmap, const void *scratch, int64_t scratch_bytes, bool *launch) {
+  *launch = false;
+  if (!h) return pgmi_failf(PGM_EINVAL, "dbn_viterbi: null plan");
+  const DbnLayout &L = h->p.L;
+  if (!codes || !values0 || !values1) return pgmi_failf(PGM_EINVAL, "dbn_viterbi: null codes / values");
+  if (!path) return pgmi_failf(PGM_EINVAL, "dbn_viterbi: null path");
+  if (n_slices < 1 || n_slices > kDbnMaxSlices)
+    return pgmi_failf(PGM_EINVAL, "dbn_viterbi: %d slices (1 .. %d)", n_slices, kDbnMaxSlices);
+  if ((int64_t)n_cols != (int64_t)n_slices * L.n)
+    return pgmi_failf(PGM_EINVAL, "dbn_viterbi: %d code columns, %d slices of %d nodes need %lld", n_cols, n_slices, L.n,
+                      (long long)n_slices * L.n);
+  if (ld < 0 || row0 < 0 || n_rows < 0 || n_rows > ld || row0 > ld - n_rows)
+    return pgmi_failf(PGM_EINVAL, "dbn_viterbi: rows [%lld, %lld + %lld) are outside ld %lld", (long long)row0, (long long)row0,
+                      (long long)n_rows, (long long)ld);
+  if (ld_out < 0 || row0_out < 0 || n_rows > ld_out || row0_out > ld_out - n_rows)
+    return pgmi_failf(PGM_EINVAL, "dbn_viterbi: path rows [%lld, %lld + %lld) are outside ld_out %lld", (long long)row0_out,
+                      (long long)row0_out, (long long)n_rows, (long long)ld_out);
+  const void *f64[] = {values0, values1, logmap};
+  for (const void *q : f64)
+    if ((uintptr_t)q % 8) return pgmi_failf(PGM_EINVAL, "dbn_viterbi: an fp64 pointer is not 8-byte aligned");
+  if ((uintptr_t)scratch % 2) return pgmi_failf(PGM_EINVAL, "dbn_viterbi: the scratch is not 2-byte aligned");
+  // n_rows <= ld and the factors are small: no overflow before the comparison
+  const double need = dbn_viterbi_scratch(n_rows, n_slices, L.J);
+  if (scratch_bytes < 0 || need > (double)scratch_bytes || (need > 0 && !scratch))
+    return pgmi_failf(PGM_EINVAL,
+                      "dbn_viterbi: the backpointers need %.0f bytes of scratch (n_rows x (slices - 1) x J uint16), %lld given", need,
+                      (long long)scratch_bytes);
   *launch = n_rows > 0;
   return PGM_OK;
 }

@@ -1,5 +1,6 @@
 """Binding of the pgm_dbn_* entry points (include/pgmhip.h, pgmpy_amd/csrc/pgmdbn.hip): filtering,
-smoothing and the log-likelihood of a batch of evidence sequences under a two-slice network in one launch.
+smoothing and the log-likelihood of a batch of evidence sequences under a two-slice network in one launch,
+and (pgm_dbn_viterbi) their most probable completions.
 
 A plan is made from the slice nodes' cardinalities, a clamped and a queried flag per node and two family
 sets, ``(columns, cardinalities)`` as in a fit plan: the slice-0 families over columns ``0 .. n - 1`` and
@@ -87,6 +88,44 @@ class DbnPlan(Plan):
                                   at(impossible, 1), N.ptr(scratch), 0 if scratch is None else scratch.numel() * 8,
                                   N.stream_handle()), "dbn_run")
         return filt, smooth, loglik, impossible
+
+    def viterbi_scratch_bytes(self, n_rows, n_slices):
+        """Bytes of backpointers one launch of `viterbi` takes: a uint16 per state of every slice but the first."""
+        return int(n_rows) * max(int(n_slices) - 1, 0) * int(self.info.n_configs) * 2
+
+    def viterbi(self, codes, values0, values1, n_rows=None, row0=0, scratch_bytes=SCRATCH_BYTES):
+        """The most probable completion of the rows [row0, row0 + n_rows) of the device codes [(T + 1) n, ld].
+        Returns device tensors (path, logmap, impossible): uint8 [(T + 1) n, n_rows] in the layout of `codes`
+        (a complete code matrix; 255 in the free cells of an impossible sequence), fp64 [n_rows] = log max_x
+        P(x, e), uint8 [n_rows].  A batch whose backpointers would pass `scratch_bytes` runs in several launches
+        over row windows; a sequence's results do not depend on the split.  Raises ValueError when a clamped
+        cell is missing or a code is no state."""
+        import torch
+
+        L = N.lib()
+        n_cols, ld, n_rows = codes_window(codes, n_rows, row0)
+        if n_cols % self.n:
+            raise ValueError(f"codes have {n_cols} columns, not a multiple of the {self.n} slice nodes")
+        n_slices = n_cols // self.n
+        flat_tensor("values0", values0, int(self.info.values0))
+        flat_tensor("values1", values1, int(self.info.values1))
+        dev = codes.device
+        rows = max(n_rows, 0)
+        ld_out = max(rows, 1)  # an empty window still hands the library a path to check
+        path = torch.empty((n_cols, ld_out), dtype=torch.uint8, device=dev)
+        logmap = torch.empty(rows, dtype=torch.float64, device=dev)
+        impossible = torch.empty(rows, dtype=torch.uint8, device=dev)
+        per_row = self.viterbi_scratch_bytes(1, n_slices)
+        chunk = max(1, min(rows, int(scratch_bytes) // per_row)) if rows and per_row else rows
+        scratch = torch.empty(max(chunk * per_row // 2, 1), dtype=torch.int16, device=dev)
+        # an empty (or negative) window still goes to the library once: it checks the arguments
+        for r0 in range(0, rows, chunk) if rows else [0]:
+            nr = min(chunk, rows - r0) if rows else n_rows
+            N.check(L.pgm_dbn_viterbi(self._h, N.ptr(codes), n_cols, ld, int(row0) + r0, nr, n_slices, N.ptr(values0),
+                                      N.ptr(values1), N.ptr(path), ld_out, r0, ctypes.c_void_p(logmap.data_ptr() + r0 * 8),
+                                      ctypes.c_void_p(impossible.data_ptr() + r0), N.ptr(scratch), scratch.numel() * 2,
+                                      N.stream_handle()), "dbn_viterbi")
+        return (path if rows else path[:, :0]), logmap, impossible
 
 
 def flat_values(cpds):

@@ -17,6 +17,8 @@ Three levels:
   * ``filter_codes`` / ``smooth_codes`` / ``log_likelihood_codes``: a resident uint8 code tensor
     ``[(T + 1) n, B]`` (column ``t n + v`` is node v, sorted name order, of slice t; 255: not observed)
     and device tensors back.
+The most probable sequence (Viterbi, csrc/pgmdbn.hip k_dbn_viterbi) has the same three levels: ``map_query``,
+``viterbi_batch``, ``viterbi_codes``; it maximises over every unobserved cell jointly.
 There is no CPU path: without a device a compute call raises ``NativeUnavailable``.
 """
 import numpy as np
@@ -53,6 +55,47 @@ class DBNResult:
         from .batch import download
 
         return download(self.loglik)
+
+    @property
+    def impossible(self):
+        from .batch import download
+
+        return download(self.flags).astype(bool)
+
+
+class ViterbiResult:
+    """What ``viterbi_batch`` returns: ``sequences()`` a frame with one ``(name, t)`` column per node and slice
+    holding state names (NaN in the unobserved cells of an impossible row), ``log_probability`` [B] =
+    log max_x P(x, e) (-inf for an impossible row), ``impossible`` [B] (bool); ``path``, ``logmap`` and ``flags``
+    are the device tensors (``path`` is a code matrix in the layout of the input)."""
+
+    def __init__(self, names, state_names, path, logmap, flags):
+        self._names, self._state_names = names, state_names
+        self.path, self.logmap, self.flags = path, logmap, flags
+
+    def sequences(self):
+        import pandas as pd
+
+        from .batch import download
+
+        codes = download(self.path.contiguous())
+        n = len(self._names)
+        cols, keys = {}, []
+        for c in range(codes.shape[0]):
+            name = self._names[c % n]
+            states = np.asarray(list(self._state_names[name]) + [np.nan], dtype=object)
+            col = codes[c].astype(np.int64)
+            cols[c] = states[np.where(col == MISSING, len(states) - 1, col)]
+            keys.append((name, c // n))
+        frame = pd.DataFrame(cols, index=range(codes.shape[1]))
+        frame.columns = pd.Index(keys, tupleize_cols=False)
+        return frame
+
+    @property
+    def log_probability(self):
+        from .batch import download
+
+        return download(self.logmap)
 
     @property
     def impossible(self):
@@ -132,6 +175,17 @@ class DBNInference:
         _, (_, _, loglik, flags) = self._run_codes(codes, observed, [], False, False)
         return loglik, flags
 
+    @E.serialized
+    def viterbi_codes(self, codes, observed=(), scratch_bytes=SCRATCH_BYTES):
+        """(path [(T + 1) n, B] uint8, logmap [B], impossible [B]) on the device: the jointly most probable
+        completion of every sequence, as a code matrix in the layout of `codes` (what ``fit``,
+        ``log_probability_codes`` and ``smooth_codes`` read), and log max_x P(x, e_0:T), the joint with the
+        evidence.  Ties go to the lowest state index.  An impossible sequence keeps 255 in its unobserved
+        cells and gets -inf and the flag."""
+        plan = self.plan(observed, [])
+        values0, values1 = self._tables()
+        return plan.viterbi(codes, values0, values1, scratch_bytes=scratch_bytes)
+
     # ------------------------------------------------------------------ frames
     def encode(self, data):
         """(host codes [(T + 1) n, B] of a frame with (name, t) columns, the names observed in every cell)."""
@@ -173,6 +227,45 @@ class DBNInference:
     def log_likelihood_batch(self, data):
         """log P(e_0:T) for every sequence (row) of `data`."""
         return self._batch(data, [], False, False)
+
+    def viterbi_batch(self, data):
+        """The most probable completion of every sequence (row) of `data`: a ``ViterbiResult``."""
+        codes, observed = self.encode(data)
+        path, logmap, flags = self.viterbi_codes(E.to_device_raw(codes), observed)
+        return ViterbiResult(self.names, self.state_names, path, logmap, flags)
+
+    def map_query(self, variables=None, evidence=None):
+        """{(name, t): state name} of one sequence, shaped like ``VariableElimination.map_query``: the jointly
+        most probable assignment of ALL the unobserved nodes of slices 0 .. last given the evidence, last being
+        the largest slice queried or observed.  `variables` (default: every unobserved node of those slices)
+        only selects which entries are returned: this is not marginal MAP over a subset, whose answer may
+        differ.  Ties go to the lowest state index.  Impossible evidence raises ValueError.  (The reference's
+        DBNInference has no such method.)"""
+        from .batch import download
+
+        evidence = {tuple(k): s for k, s in (evidence or {}).items()}
+        chosen = None if variables is None else [tuple(v) for v in variables]
+        for name, t in list(chosen or []) + list(evidence):
+            if name not in self.index:
+                raise ValueError(f"Node {name} not in the model")
+            if not isinstance(t, (int, np.integer)) or t < 0:
+                raise ValueError(f"({name}, {t}): the time slice must be a non-negative integer")
+        if chosen is not None and not chosen:
+            return {}
+        n = len(self.names)
+        last = max([t for _, t in chosen or []] + [t for _, t in evidence], default=0)
+        codes = np.full(((last + 1) * n, 1), MISSING, dtype=np.uint8)
+        for (name, t), state in evidence.items():
+            codes[t * n + self.index[name], 0] = self.cpds0[self.index[name]].get_state_no((name, 0), state)
+        seen = codes.reshape(last + 1, n) != MISSING
+        observed = [name for v, name in enumerate(self.names) if seen[:, v].all()]
+        path, _, flags = self.viterbi_codes(E.to_device_raw(codes), observed)
+        if download(flags)[0]:
+            raise ValueError("map_query: the evidence has probability 0 under the model")
+        host = download(path.contiguous())[:, 0]
+        if chosen is None:
+            chosen = [(name, t) for t in range(last + 1) for name in self.names if (name, t) not in evidence]
+        return {(name, t): self.state_names[name][int(host[t * n + self.index[name]])] for name, t in chosen}
 
     # ------------------------------------------------------------------ the reference's entry points
     def _one(self, variables, evidence, smooth):
