@@ -487,6 +487,12 @@ int pgm_rows_plan_destroy(void *handle);
  * all-affine plan: one query variable and no hidden variable per component).  Writes at most len
  * bytes (NUL-terminated) and the full size + 1 to *needed.  No device needed (tests, inspection). */
 int pgm_rows_plan_source(const pgm_rows_plan *plan, char *buf, size_t len, size_t *needed);
+/* The same kernels under the streaming cache policy (evidence codes and outputs pass the caches: a
+ * second hipRTC program of the plan, bit-identical outputs), and to *min_rows (may be NULL) the row count
+ * from which a launch runs it (INT64_MAX: never).  PGM_ROWS_STREAM, read when a plan is created, overrides
+ * both for A/B runs: 0 = default program always; 1..5 = streaming always, nontemporal code loads if bit 0,
+ * store form (value >> 1): 0 sc1, 1 sc1 nt, 2 sc0 sc1 nt.  Same buffer contract as pgm_rows_plan_source. */
+int pgm_rows_plan_stream_source(const pgm_rows_plan *plan, char *buf, size_t len, size_t *needed, int64_t *min_rows);
 /* Rows [row0, row0 + n_rows) of codes.  Outputs are column-major with leading dim ld_out (>= n_rows) and
  * row r written at column r (not row0 + r); any may be NULL unless its mode bit is set:
  *   marg [n_marg][ld_out] f64   joint [n_joint][ld_out] f64   map [n_rows] int32   gap [n_rows] f64 */

@@ -428,6 +428,8 @@ _SIGS = {
     "pgm_rows_bound_run": ([_P], ctypes.c_int),
     "pgm_rows_plan_source": ([ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)],
                              ctypes.c_int),
+    "pgm_rows_plan_stream_source": ([ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                     ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
     "pgm_rows_bound_destroy": ([_P], ctypes.c_int),
     "pgm_rows_bound_kernel": ([_P, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32),
                                ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),

@@ -50,10 +50,21 @@ struct PGM_ROWS_LOCAL RowsPlan {
   std::string jit_src;    // source of the plan-specialised kernels (plans without a table component)
 };
 
+// How the generated kernels touch memory: the cache policy of the evidence-code loads and of the output
+// stores.  Nothing else depends on it (addresses, widths, arithmetic, grid and LDS use are the same for
+// every policy, so the outputs are bit-identical); the CPT loads and the ring's system-scope code loads
+// are default-policy under all of them.  The default policy emits the source the golden files pin.
+struct RowsPolicy {
+  enum Stores { kStoreSc1 = 0, kStoreSc1Nt = 1, kStoreSc0Sc1Nt = 2 };  // all write-through (kRowsJitWriteThrough)
+  bool nt_loads = false;  // evidence codes with the nontemporal hint
+  int stores = kStoreSc1;
+  bool is_default() const { return !nt_loads && stores == kStoreSc1; }
+};
+
 // validate and compile a plan (pl non-null); PGM_OK, or PGM_EINVAL with pgm_last_error set
 PGM_ROWS_LOCAL int rows_plan_compile(const pgm_rows_plan *pl, RowsPlan &out);
 // pgm_rows_plan_source without the copy-out: the specialisability check and the generated source
-PGM_ROWS_LOCAL int rows_plan_source(const pgm_rows_plan *pl, std::string &src);
+PGM_ROWS_LOCAL int rows_plan_source(const pgm_rows_plan *pl, std::string &src, const RowsPolicy &pol = RowsPolicy());
 
 // the alignment / addressing contract of the two-rows-per-lane body (pgm_rows_jit2, pgm_rows_ring)
 PGM_ROWS_LOCAL bool rows2_aligned(int32_t mode, const uint8_t *codes, int64_t ld_codes, int64_t row0, int64_t n_rows,
@@ -96,5 +107,6 @@ static constexpr int ring_wg() { return 256; }
 // writes it (no dirty output left for an end-of-dispatch release to write back; measured MI355X, 100k
 // rows: HIP launch 4.7 -> 3.8 us, direct queue 6.2 -> 4.0 us with the per-dispatch release dropped,
 // WRITE_SIZE 13.28 MB per launch either way; r02 also measured plain (write-back) and nontemporal forms
-// and rejected them)
+// and rejected them — plain `nt` is not write-through; the streaming policy's stores are sc1 AND nt, with
+// the same WRITE_SIZE: RowsPolicy above, the rule in pgmrows.hip)
 static constexpr bool kRowsJitWriteThrough = true;

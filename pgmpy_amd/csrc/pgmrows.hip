@@ -564,16 +564,26 @@ static void launch_rows_f(int maxt, int maxfc, dim3 g, dim3 b, size_t lds, hipSt
 struct RowsHandle : RowsPlan {
   double *d_values = nullptr;
   int32_t *d_desc = nullptr;
-  // plan-specialised kernel (hipRTC): jit_src is generated at create for all-affine plans, compiled on first use
+  // plan-specialised kernels (hipRTC): jit_src is generated at create for all-affine plans; one program
+  // per cache policy of the stream (RowsPolicy), each compiled on first use
+  struct Prog {
+    std::string src;
+    int state = 0;  // 0 not compiled, 1 ready, -1 unavailable
+    hipModule_t mod = nullptr;
+    hipFunction_t fn = nullptr;
+    hipFunction_t fn2 = nullptr;        // two rows per thread
+    hipFunction_t fn_floor = nullptr;   // PGM_ROWS_FLOOR: the same dispatch's loads + stores only
+    hipFunction_t fn_floor2 = nullptr;  // ... of the two-rows-per-thread dispatch
+    hipFunction_t fn_ring = nullptr;    // the resident ring kernel (pgm_rows_ring_*)
+    std::vector<char> code;             // the compiled code object (the direct AQL path loads it again)
+    const char *name_of(hipFunction_t f) const {
+      return f == fn2 ? "pgm_rows_jit2" : f == fn_floor ? "pgm_rows_floor" : f == fn_floor2 ? "pgm_rows_floor2" : "pgm_rows_jit";
+    }
+  };
   std::mutex jit_mu;
-  int jit_state = 0;  // 0 not compiled, 1 ready, -1 unavailable (the AOT kernels run instead)
-  hipModule_t jit_mod = nullptr;
-  hipFunction_t jit_fn = nullptr;
-  hipFunction_t jit_fn2 = nullptr;  // two rows per thread
-  hipFunction_t jit_fn_floor = nullptr;  // PGM_ROWS_FLOOR: the same dispatch's loads + stores only
-  hipFunction_t jit_fn_floor2 = nullptr;  // ... of the two-rows-per-thread dispatch
-  hipFunction_t jit_fn_ring = nullptr;    // the resident ring kernel (pgm_rows_ring_*)
-  std::vector<char> jit_code;         // the compiled code object (the direct AQL path loads it again)
+  Prog prog_default;  // jit_src: when it is unavailable (state -1) the AOT kernels run instead
+  Prog prog_stream;   // the same kernels under the streaming policy (rows_stream_policy), bit-identical outputs
+  int64_t stream_min_rows = 0;        // launches of at least this many rows run prog_stream (rows_prog)
   bool jit_write_through = false;     // its output stores are write-through (kRowsJitWriteThrough)
   int device = 0;                     // the HIP device current at create (its buffers / module live there)
   // pgm_rows_shard_run's resources on this handle's device, created on first use and kept until the
@@ -590,32 +600,79 @@ struct RowsHandle : RowsPlan {
   std::mutex shard_mu;  // one pgm_rows_shard_run shard at a time per handle
 };
 
-// compile + load the handle's specialised kernel once; false when unavailable (AOT kernels run)
-static bool rows_jit_ready(RowsHandle *h) {
-  if (h->jit_src.empty()) return false;
+// compile + load one program of the handle once; false when unavailable
+static bool rows_prog_ready(RowsHandle *h, RowsHandle::Prog &pg, const char *what) {
+  if (pg.src.empty()) return false;
   std::lock_guard<std::mutex> lk(h->jit_mu);
-  if (h->jit_state != 0) return h->jit_state > 0;
-  h->jit_state = -1;
+  if (pg.state != 0) return pg.state > 0;
+  pg.state = -1;
   static const bool disabled = getenv("PGM_NO_JIT") != nullptr;  // testing: AOT kernels only
   if (disabled) return false;
   std::vector<char> code;
-  if (!pgmi_rtc_code(h->jit_src, "specialised row kernel", code)) return false;
-  h->jit_code = code;
-  if (hipModuleLoadData(&h->jit_mod, code.data()) != hipSuccess) {
+  if (!pgmi_rtc_code(pg.src, what, code)) return false;
+  pg.code = code;
+  if (hipModuleLoadData(&pg.mod, code.data()) != hipSuccess) {
     (void)hipGetLastError();
-    h->jit_mod = nullptr;
+    pg.mod = nullptr;
     return false;
   }
-  if (hipModuleGetFunction(&h->jit_fn, h->jit_mod, "pgm_rows_jit") != hipSuccess ||
-      hipModuleGetFunction(&h->jit_fn2, h->jit_mod, "pgm_rows_jit2") != hipSuccess ||
-      hipModuleGetFunction(&h->jit_fn_floor, h->jit_mod, "pgm_rows_floor") != hipSuccess ||
-      hipModuleGetFunction(&h->jit_fn_floor2, h->jit_mod, "pgm_rows_floor2") != hipSuccess ||
-      hipModuleGetFunction(&h->jit_fn_ring, h->jit_mod, "pgm_rows_ring") != hipSuccess) {
+  if (hipModuleGetFunction(&pg.fn, pg.mod, "pgm_rows_jit") != hipSuccess ||
+      hipModuleGetFunction(&pg.fn2, pg.mod, "pgm_rows_jit2") != hipSuccess ||
+      hipModuleGetFunction(&pg.fn_floor, pg.mod, "pgm_rows_floor") != hipSuccess ||
+      hipModuleGetFunction(&pg.fn_floor2, pg.mod, "pgm_rows_floor2") != hipSuccess ||
+      hipModuleGetFunction(&pg.fn_ring, pg.mod, "pgm_rows_ring") != hipSuccess) {
     (void)hipGetLastError();
     return false;
   }
-  h->jit_state = 1;
+  pg.state = 1;
   return true;
+}
+
+// the specialised kernels exist for this handle; false: the AOT kernels run
+static bool rows_jit_ready(RowsHandle *h) { return rows_prog_ready(h, h->prog_default, "specialised row kernel"); }
+
+// The cache policy of the streaming program and the row count from which a launch runs it: THE rule for
+// pgm_rows_plan_run / _bind (and through the bound launch the direct queues) and the ring.
+// Measured on MI355X (profiles/r07stream/, DESIGN.md "cache policy of the stream"): launches of at least
+// 50,000 rows store their outputs write-through AND nontemporal (sc1 nt) and load their codes as before.
+//   - The outputs are never read on the device; as plain write-through lines they are allocated in the 256
+//     MiB Infinity Cache and push out the evidence codes every new dispatch waits for before its first
+//     store.  With `nt` the 96 x 100k-row bench window runs 2.5-2.6 -> 1.9-2.0 us of GPU span per dispatch
+//     (bench value 27.5-28.3 -> 33.7-34.4 G rows/s at 20 steps, 32.4-33.7 -> 41.5-42.7 G at 50, six
+//     interleaved rounds); WRITE_SIZE stays 13,281.25 KB per launch, so the stores are still write-through.
+//   - Nontemporal code loads undo it (2.6-2.9 us alone, 2.6-2.7 us with the stores): they keep the codes
+//     out of that cache.  sc0 sc1 nt stores measure the same as sc1 nt.  Neither is kept.
+//   - From 50,000 rows: 96 batches of 50 k rows (0.69 GB) gain 1.7 -> 1.15-1.2 us; at 20 k and 10 k rows
+//     (sets that fit the cache) streaming is even or 2-4 % behind, and four 100k-row launches rewriting the
+//     same cached outputs lose 1.6 -> 1.9 us — the price where a set does fit.
+static constexpr bool kRowsStreamLoads = false;
+static constexpr int kRowsStreamStores = RowsPolicy::kStoreSc1Nt;
+static constexpr int64_t kRowsStreamMinRows = 50000;
+// A/B switch PGM_ROWS_STREAM, read when a plan is created: unset = the rule above; 0 = the default
+// program for every launch; a policy word w in 1..5 = the streaming program for every launch, with
+// nontemporal code loads if w & 1 and store form (w >> 1): 0 sc1, 1 sc1 nt, 2 sc0 sc1 nt
+static RowsPolicy rows_stream_policy(int64_t *min_rows) {
+  RowsPolicy pol;
+  pol.nt_loads = kRowsStreamLoads;
+  pol.stores = kRowsStreamStores;
+  *min_rows = kRowsStreamMinRows;
+  const char *e = getenv("PGM_ROWS_STREAM");
+  if (e && *e) {
+    const int w = atoi(e);
+    if (w < 0 || w > 5) return pol;
+    pol.nt_loads = (w & 1) != 0;
+    pol.stores = w >> 1;
+    *min_rows = w == 0 ? INT64_MAX : 0;
+  }
+  return pol;
+}
+
+// the program a launch of n_rows rows runs (call after rows_jit_ready(h) held); the streaming program
+// computes what the default one does, so where it cannot be built the default one runs
+static RowsHandle::Prog *rows_prog(RowsHandle *h, int64_t n_rows) {
+  if (n_rows >= h->stream_min_rows && rows_prog_ready(h, h->prog_stream, "specialised row kernel (streaming)"))
+    return &h->prog_stream;
+  return &h->prog_default;
 }
 
 extern "C" {
@@ -631,6 +688,10 @@ int pgm_rows_plan_create(const pgm_rows_plan *pl, const double *host_values, voi
   if (!h) return pgmi_failf(PGM_ENOMEM, "rows_plan_create: host allocation");
   static_cast<RowsPlan &>(*h) = std::move(plan);
   h->jit_write_through = !h->jit_src.empty() && kRowsJitWriteThrough;
+  h->prog_default.src = h->jit_src;
+  const RowsPolicy pol = rows_stream_policy(&h->stream_min_rows);
+  if (h->jit_src.empty() || pol.is_default()) h->stream_min_rows = INT64_MAX;  // one program
+  else (void)rows_plan_source(pl, h->prog_stream.src, pol);
   (void)hipGetDevice(&h->device);
   hipError_t e = hipSuccess;
   e = hipMalloc((void **)&h->d_values, sizeof(double) * (pl->n_values + 1));
@@ -669,6 +730,23 @@ int pgm_rows_plan_source(const pgm_rows_plan *pl, char *buf, size_t len, size_t 
   return PGM_OK;
 }
 
+int pgm_rows_plan_stream_source(const pgm_rows_plan *pl, char *buf, size_t len, size_t *needed, int64_t *min_rows) {
+  STALE_PROBE();
+  int64_t from = 0;
+  const RowsPolicy pol = rows_stream_policy(&from);
+  std::string src;
+  const int st = rows_plan_source(pl, src, pol);
+  if (st != PGM_OK) return st;
+  if (min_rows) *min_rows = pol.is_default() ? INT64_MAX : from;
+  if (needed) *needed = src.size() + 1;
+  if (buf && len > 0) {
+    const size_t n = std::min(len - 1, src.size());
+    memcpy(buf, src.data(), n);
+    buf[n] = 0;
+  }
+  return PGM_OK;
+}
+
 int pgm_rows_launch_info(const pgm_rows_plan *pl, int32_t mode, const uint8_t *codes, int64_t ld_codes, int64_t row0,
                          int64_t n_rows, const double *marg, const double *joint, int64_t ld_out, const int32_t *map,
                          const double *gap, int32_t jit_available, pgm_rows_launch_info_t *info) {
@@ -693,7 +771,8 @@ int pgm_rows_plan_destroy(void *handle) {
   (void)hipSetDevice(prev);
   if (h->d_values) (void)hipFree(h->d_values);
   if (h->d_desc) (void)hipFree(h->d_desc);
-  if (h->jit_mod) (void)hipModuleUnload(h->jit_mod);
+  if (h->prog_default.mod) (void)hipModuleUnload(h->prog_default.mod);
+  if (h->prog_stream.mod) (void)hipModuleUnload(h->prog_stream.mod);
   delete h;
   return PGM_OK;
 }
@@ -727,7 +806,8 @@ static int rows_plan_run(void *handle, int32_t mode, const uint8_t *codes, int64
     int32_t *mp = map, *ef = err_flag;
     int32_t md = mode;
     void *args[] = {(void *)&v, (void *)&cp, &ldc, &r0, &nr, (void *)&mg, &ldo, (void *)&mp, (void *)&gp, (void *)&ef, &md};
-    HIP_TRY(hipModuleLaunchKernel(li.kernel == PGM_RK_JIT2 ? h->jit_fn2 : h->jit_fn, li.blocks, 1, 1, li.wg, 1, 1, 0, s,
+    const RowsHandle::Prog *pg = rows_prog(h, n_rows);
+    HIP_TRY(hipModuleLaunchKernel(li.kernel == PGM_RK_JIT2 ? pg->fn2 : pg->fn, li.blocks, 1, 1, li.wg, 1, 1, 0, s,
                                   args, nullptr));
     return PGM_OK;
   }
@@ -782,6 +862,7 @@ struct RowsJitArgs {  // pgm_rows_jit's parameters, packed as the kernel's argum
 struct RowsBound {
   // specialised kernel bound: the packed argument segment and launch shape, launched directly
   hipFunction_t fn = nullptr;
+  const RowsHandle::Prog *prog = nullptr;  // the program fn belongs to (rows_prog)
   RowsJitArgs args;
   size_t args_size = sizeof(RowsJitArgs);
   unsigned blocks = 0;
@@ -828,10 +909,12 @@ int pgm_rows_plan_bind(void *handle, int32_t mode, const uint8_t *codes, int64_t
   RowsHandle *h = (RowsHandle *)handle;
   // the same choice rows_plan_run makes (the dry run above compiled the kernel if it applies)
   pgm_rows_launch_info_t li;
-  if (n_rows > 0 && h->jit_state > 0 && rows_jit_mode(mode) &&
+  if (n_rows > 0 && h->prog_default.state > 0 && rows_jit_mode(mode) &&
       rows_launch_choose(*h, mode, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, true, &li) == PGM_OK) {
     const bool two = li.kernel == PGM_RK_JIT2;
-    b->fn = floor ? (two ? h->jit_fn_floor2 : h->jit_fn_floor) : two ? h->jit_fn2 : h->jit_fn;
+    const RowsHandle::Prog *pg = rows_prog(h, n_rows);  // the floor carries the policy of the kernel it stands for
+    b->prog = pg;
+    b->fn = floor ? (two ? pg->fn_floor2 : pg->fn_floor) : two ? pg->fn2 : pg->fn;
     b->args = RowsJitArgs{h->d_values, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, err_flag, mode, 0};
     b->blocks = li.blocks;
   } else if (floor) {
@@ -859,8 +942,7 @@ int pgm_rows_bound_run(void *bound) {
 int pgm_rows_bound_kernel(void *bound, char *name, size_t cap, uint32_t *blocks, uint32_t *wg) {
   RowsBound *b = (RowsBound *)bound;
   if (!b || !name || cap == 0) return pgmi_failf(PGM_EINVAL, "rows_bound_kernel: null argument");
-  RowsHandle *h = (RowsHandle *)b->handle;
-  const char *k = !b->fn ? "" : b->fn == h->jit_fn2 ? "pgm_rows_jit2" : b->fn == h->jit_fn_floor ? "pgm_rows_floor" : b->fn == h->jit_fn_floor2 ? "pgm_rows_floor2" : "pgm_rows_jit";
+  const char *k = !b->fn ? "" : b->prog->name_of(b->fn);
   snprintf(name, cap, "%s", k);
   if (blocks) *blocks = b->fn ? b->blocks : 0;
   if (wg) *wg = b->fn ? (uint32_t)jit_wg() : 0;
@@ -1098,7 +1180,7 @@ int pgm_rows_ring_create(void *handle, int32_t mode, int32_t n_slots, const uint
   if (e == hipSuccess) e = hipGetDevice(&dev);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   if (e == hipSuccess)
-    e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit_fn_ring, ring_wg(), 0);
+    e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rows_prog(h, n_rows)->fn_ring, ring_wg(), 0);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     if (rg->d_slots) (void)hipFree(rg->d_slots);
@@ -1173,7 +1255,7 @@ static int ring_start(RowsRing *rg, uint32_t n_batches, double timeout_s, int si
     HIP_TRY(hipStreamSynchronize(rg->stream));
     rg->reset_gctl = false;
   }
-  HIP_TRY(hipModuleLaunchKernel(rg->h->jit_fn_ring, rg->blocks, 1, 1, (unsigned)ring_wg(), 1, 1, 0, rg->stream, args,
+  HIP_TRY(hipModuleLaunchKernel(rows_prog(rg->h, rg->n_rows)->fn_ring, rg->blocks, 1, 1, (unsigned)ring_wg(), 1, 1, 0, rg->stream, args,
                                 nullptr));
   rg->running = true;
   return PGM_OK;
@@ -1264,10 +1346,10 @@ int pgmi_rows_bound_jit(void *bound, pgmi_jit_launch *out) {
   if (!b || !out) return pgmi_failf(PGM_EINVAL, "rows_bound_jit: null argument");
   if (!b->fn) return pgmi_failf(PGM_EINVAL, "direct launch needs the plan-specialised kernel (hipRTC), not an AOT kernel");
   RowsHandle *h = (RowsHandle *)b->handle;
-  if (h->jit_code.empty()) return pgmi_failf(PGM_EINVAL, "direct launch: no code object kept for this plan");
-  out->code = h->jit_code.data();
-  out->code_size = h->jit_code.size();
-  out->kernel = b->fn == h->jit_fn2 ? "pgm_rows_jit2" : b->fn == h->jit_fn_floor ? "pgm_rows_floor" : b->fn == h->jit_fn_floor2 ? "pgm_rows_floor2" : "pgm_rows_jit";
+  if (b->prog->code.empty()) return pgmi_failf(PGM_EINVAL, "direct launch: no code object kept for this plan");
+  out->code = b->prog->code.data();
+  out->code_size = b->prog->code.size();
+  out->kernel = b->prog->name_of(b->fn);
   out->args = &b->args;
   out->args_size = b->args_size;
   out->blocks = b->blocks;

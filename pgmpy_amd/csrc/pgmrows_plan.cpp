@@ -62,8 +62,8 @@ int jit_wg() {
   return wg;
 }
 
-// Every output store of the generated kernels is write-through (PGM_WT4 / PGM_WT8 / PGM_WT16 below;
-// why, and what it buys: kRowsJitWriteThrough in pgm_rows.h).
+// Every output store of the generated kernels is write-through under every policy (PGM_WT4 / PGM_WT8 /
+// PGM_WT16, emit_rows_prelude; why, and what it buys: kRowsJitWriteThrough in pgm_rows.h).
 
 // the distinct evidence columns of a plan, each loaded once per row
 static std::vector<int> rows_cols(const pgm_rows_plan *pl) {
@@ -76,17 +76,24 @@ static std::vector<int> rows_cols(const pgm_rows_plan *pl) {
 // the row's evidence codes (row rc of the columns at C + row0, leading dimension ldc): e<i>_<u>
 // coherent: system-scope relaxed loads (past every non-coherent cache, no invalidation needed) — the
 // ring kernel's codes, which may be written after the launch started
-static void emit_rows_code_loads(std::string &o, const std::vector<int> &cols, int R, bool coherent = false) {
+// pol.nt_loads: the plain loads carry the nontemporal hint (codes are read once per launch; the coherent
+// form is left alone: nothing shows that `nt` keeps a system-scope load's freshness)
+static void emit_rows_code_loads(std::string &o, const std::vector<int> &cols, int R, const RowsPolicy &pol,
+                                 bool coherent = false) {
   if (!cols.empty()) o += "  const unsigned char *cr = C + row0 + rc;\n";
   for (size_t i = 0; i < cols.size(); ++i) {
     if (R == 1) {
-      pgmi_appendf(o, "  const unsigned e%zu_0 = cr[%dLL * ldc];\n", i, cols[i]);
+      if (pol.nt_loads) pgmi_appendf(o, "  const unsigned e%zu_0 = __builtin_nontemporal_load(&cr[%dLL * ldc]);\n", i, cols[i]);
+      else pgmi_appendf(o, "  const unsigned e%zu_0 = cr[%dLL * ldc];\n", i, cols[i]);
     } else if (coherent) {
       pgmi_appendf(o, "  const unsigned w%zu = __hip_atomic_load((__attribute__((address_space(1))) unsigned short *)(cr + %dLL * ldc), __ATOMIC_RELAXED, "
                    "__HIP_MEMORY_SCOPE_SYSTEM);\n", i, cols[i]);
       pgmi_appendf(o, "  const unsigned e%zu_0 = w%zu & 255u, e%zu_1 = w%zu >> 8;\n", i, i, i, i);
     } else {
-      pgmi_appendf(o, "  const unsigned w%zu = *(const unsigned short *)(cr + %dLL * ldc);\n", i, cols[i]);
+      if (pol.nt_loads)
+        pgmi_appendf(o, "  const unsigned w%zu = __builtin_nontemporal_load((const unsigned short *)(cr + %dLL * ldc));\n", i, cols[i]);
+      else
+        pgmi_appendf(o, "  const unsigned w%zu = *(const unsigned short *)(cr + %dLL * ldc);\n", i, cols[i]);
       pgmi_appendf(o, "  const unsigned e%zu_0 = w%zu & 255u, e%zu_1 = w%zu >> 8;\n", i, i, i, i);
     }
   }
@@ -185,7 +192,7 @@ static void emit_rows_compute(std::string &o, const pgm_rows_plan *pl, int R, co
 static bool jit_values_lds(int nv) { return nv * 8 <= 48 * 1024; }
 
 // R rows per thread (1, or 2 with 16-B marginal stores / 2-byte code loads); names carry the row's suffix
-static void emit_rows_kernel(std::string &o, const pgm_rows_plan *pl, int R) {
+static void emit_rows_kernel(std::string &o, const pgm_rows_plan *pl, int R, const RowsPolicy &pol) {
   const int NV = pl->n_values + 1;  // + trailing 1.0
   // CPT values staged in LDS when they fit (else gathered straight from global memory through L1/L2)
   const bool lds = jit_values_lds(NV);
@@ -206,7 +213,7 @@ static void emit_rows_kernel(std::string &o, const pgm_rows_plan *pl, int R) {
     for (int i = 0; i < K; ++i) pgmi_appendf(o, "  const double s%d = V[t + %d < %d ? t + %d : %d];\n", i, WG * i, NV, WG * i, NV - 1);
   }
   const std::vector<int> cols = rows_cols(pl);
-  emit_rows_code_loads(o, cols, R);
+  emit_rows_code_loads(o, cols, R, pol);
   if (lds) {
     for (int i = 0; i < K; ++i) pgmi_appendf(o, "  S[t + %d < %d ? t + %d : %d] = s%d;\n", WG * i, NV, WG * i, NV - 1, i);
     o += "  __syncthreads();\n#define VAL(i) S[i]\n";
@@ -238,7 +245,7 @@ static void emit_rows_kernel(std::string &o, const pgm_rows_plan *pl, int R) {
 // all items done; ctl[1] (cancel) set by the host; or `timeout` ticks of the constant 100 MHz wall
 // clock without the needed batch (ctl[2] |= 2); either of the last two raises g[2] (stop) for all.
 // The CPT values are staged in LDS once per workgroup for the whole stream.
-static void emit_rows_ring(std::string &o, const pgm_rows_plan *pl) {
+static void emit_rows_ring(std::string &o, const pgm_rows_plan *pl, const RowsPolicy &pol) {
   const int NV = pl->n_values + 1;
   const int WG = ring_wg();
   const int K = (NV + WG - 1) / WG;
@@ -341,7 +348,7 @@ static void emit_rows_ring(std::string &o, const pgm_rows_plan *pl) {
        "    const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc(G, 0, 0x7fffffff, 0x00020000);\n"
        "    do {\n";
   const std::vector<int> cols = rows_cols(pl);
-  emit_rows_code_loads(o, cols, 2, true);
+  emit_rows_code_loads(o, cols, 2, pol, true);
   emit_rows_compute(o, pl, 2, cols, "break");
   o += "    } while (0);\n  }\n}\n#undef VAL\n";
 }
@@ -350,7 +357,7 @@ static void emit_rows_ring(std::string &o, const pgm_rows_plan *pl) {
 // thread, as pgm_rows_jit / pgm_rows_jit2), its evidence-column loads and its output stores (same
 // addresses, same widths, same cache policy), with the CPT staging, gathers and arithmetic replaced by
 // one conversion of the loaded codes
-static void emit_rows_floor(std::string &o, const pgm_rows_plan *pl, int R) {
+static void emit_rows_floor(std::string &o, const pgm_rows_plan *pl, int R, const RowsPolicy &pol) {
   const int WG = jit_wg();
   pgmi_appendf(o, "extern \"C\" __global__ void __launch_bounds__(%d) pgm_rows_floor%s(const double *__restrict__ V, "
              "const unsigned char *__restrict__ C, long long ldc, long long row0, long long n, "
@@ -364,7 +371,9 @@ static void emit_rows_floor(std::string &o, const pgm_rows_plan *pl, int R) {
   o += "  unsigned x = 0u;\n";
   if (!cols.empty()) o += "  const unsigned char *cr = C + row0 + r;\n";
   for (size_t i = 0; i < cols.size(); ++i) {
-    if (R == 1) pgmi_appendf(o, "  x += cr[%dLL * ldc];\n", cols[i]);
+    if (R == 1 && pol.nt_loads) pgmi_appendf(o, "  x += __builtin_nontemporal_load(&cr[%dLL * ldc]);\n", cols[i]);
+    else if (R == 1) pgmi_appendf(o, "  x += cr[%dLL * ldc];\n", cols[i]);
+    else if (pol.nt_loads) pgmi_appendf(o, "  x += __builtin_nontemporal_load((const unsigned short *)(cr + %dLL * ldc));\n", cols[i]);
     else pgmi_appendf(o, "  x += *(const unsigned short *)(cr + %dLL * ldc);\n", cols[i]);
   }
   o += "  const double v = (double)x;\n  if (mode & 1) {\n";
@@ -385,27 +394,44 @@ static void emit_rows_floor(std::string &o, const pgm_rows_plan *pl, int R) {
     o += "    if (MP) PGM_WT4(int, &MP[r], (int)x);\n    if ((mode & 8) && G) PGM_WT8(double, &G[r], v);\n  }\n}\n";
 }
 
-// the whole source of a plan: both row kernels, both floor kernels, the ring kernel
-static std::string rows_jit_source(const pgm_rows_plan *pl) {
-  // write-through stores: 4/8 B as relaxed agent-scope atomic stores (global_store ... sc1), 16 B as
-  // a buffer store with the sc1 cache bit (element offset into the resource's base, bytes < 2 GiB)
-  std::string o =
-      "typedef unsigned int pgm_u32x4 __attribute__((ext_vector_type(4)));\n"
-      "#define PGM_WT4(T, p, v) __hip_atomic_store((__attribute__((address_space(1))) T *)(p), (v), "
-      "__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)\n"
-      "#define PGM_WT8(T, p, v) PGM_WT4(T, p, v)\n"
-      "#define PGM_WT16(rs, off, a, b) do { const double2 v_ = make_double2((a), (b)); pgm_u32x4 w_; "
-      "__builtin_memcpy(&w_, &v_, 16); __builtin_amdgcn_raw_buffer_store_b128(w_, rs, (int)((off) * 8), 0, 16); } "
-      "while (0)\n";
-  emit_rows_kernel(o, pl, 1);
+// the store macros of a source.  Default policy: 4/8 B as relaxed agent-scope atomic stores (global_store
+// ... sc1), 16 B as a buffer store with the sc1 cache bit (element offset into the resource's base, bytes
+// < 2 GiB).  Streaming policies: the same stores, write-through AND nontemporal — no builtin gives a
+// global store both bits, so 4/8 B are the instruction itself (sc1 nt, or sc0 sc1 nt); the 16-B buffer
+// store takes them in its aux operand (sc0 = 1, nt = 2, sc1 = 16)
+static void emit_rows_prelude(std::string &o, const RowsPolicy &pol) {
+  o += "typedef unsigned int pgm_u32x4 __attribute__((ext_vector_type(4)));\n";
+  if (pol.stores == RowsPolicy::kStoreSc1) {
+    o += "#define PGM_WT4(T, p, v) __hip_atomic_store((__attribute__((address_space(1))) T *)(p), (v), "
+         "__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)\n"
+         "#define PGM_WT8(T, p, v) PGM_WT4(T, p, v)\n";
+  } else {
+    const char *bits = pol.stores == RowsPolicy::kStoreSc0Sc1Nt ? "sc0 sc1 nt" : "sc1 nt";
+    pgmi_appendf(o, "#define PGM_WT4(T, p, v) do { const T s_ = (v); asm volatile(\"global_store_dword %%0, %%1, off %s\" "
+                    ":: \"v\"((__attribute__((address_space(1))) T *)(p)), \"v\"(s_) : \"memory\"); } while (0)\n", bits);
+    pgmi_appendf(o, "#define PGM_WT8(T, p, v) do { const T s_ = (v); asm volatile(\"global_store_dwordx2 %%0, %%1, off %s\" "
+                    ":: \"v\"((__attribute__((address_space(1))) T *)(p)), \"v\"(s_) : \"memory\"); } while (0)\n", bits);
+  }
+  const int aux = pol.stores == RowsPolicy::kStoreSc1 ? 16 : pol.stores == RowsPolicy::kStoreSc1Nt ? 18 : 19;
+  pgmi_appendf(o, "#define PGM_WT16(rs, off, a, b) do { const double2 v_ = make_double2((a), (b)); pgm_u32x4 w_; "
+                  "__builtin_memcpy(&w_, &v_, 16); __builtin_amdgcn_raw_buffer_store_b128(w_, rs, (int)((off) * 8), 0, %d); } "
+                  "while (0)\n", aux);
+}
+
+// the whole source of a plan: both row kernels, both floor kernels, the ring kernel.  The policy changes
+// how memory is touched and nothing else: the default one emits the text the golden files pin
+static std::string rows_jit_source(const pgm_rows_plan *pl, const RowsPolicy &pol = RowsPolicy()) {
+  std::string o;
+  emit_rows_prelude(o, pol);
+  emit_rows_kernel(o, pl, 1, pol);
   o += "\n";
-  emit_rows_kernel(o, pl, 2);
+  emit_rows_kernel(o, pl, 2, pol);
   o += "\n";
-  emit_rows_floor(o, pl, 1);
+  emit_rows_floor(o, pl, 1, pol);
   o += "\n";
-  emit_rows_floor(o, pl, 2);
+  emit_rows_floor(o, pl, 2, pol);
   o += "\n";
-  emit_rows_ring(o, pl);
+  emit_rows_ring(o, pl, pol);
   return o;
 }
 
@@ -523,7 +549,7 @@ int rows_launch_info(const pgm_rows_plan *pl, int32_t mode, const uint8_t *codes
   return rows_launch_choose(plan, mode, codes, ld_codes, row0, n_rows, marg, ld_out, map, gap, jit, info);
 }
 
-int rows_plan_source(const pgm_rows_plan *pl, std::string &src) {
+int rows_plan_source(const pgm_rows_plan *pl, std::string &src, const RowsPolicy &pol) {
   if (!pl) return pgmi_failf(PGM_EINVAL, "rows_plan_source: null plan");
   if (pl->n_comp < 1 || pl->n_comp > PGM_ROWS_MAX_COMP || pl->n_fac < 0 || pl->n_fac > PGM_ROWS_MAX_FAC ||
       pl->n_ev < 0 || pl->n_ev > PGM_ROWS_MAX_EV || pl->n_loop < 0 || pl->n_loop > PGM_ROWS_MAX_LOOP)
@@ -532,7 +558,7 @@ int rows_plan_source(const pgm_rows_plan *pl, std::string &src) {
     if (pl->comp_n_query[c] > 1 || pl->comp_loop_end[c] - pl->comp_loop_begin[c] != pl->comp_n_query[c])
       return pgmi_failf(PGM_EINVAL, "rows_plan_source: component %d is not specialisable (query dims %d, loop dims %d)", c,
                         pl->comp_n_query[c], pl->comp_loop_end[c] - pl->comp_loop_begin[c]);
-  src = rows_jit_source(pl);
+  src = rows_jit_source(pl, pol);
   return PGM_OK;
 }
 

@@ -247,6 +247,18 @@ class PatternPlan:
         N.check(L.pgm_rows_plan_source(ctypes.byref(pl), buf, need.value, None), "rows_plan_source")
         return buf.value.decode()
 
+    def streaming_source(self):
+        """(source, min_rows): the same kernels under the streaming cache policy, and the row count from
+        which a launch runs them (pgm_rows_plan_stream_source); host-only, no device needed."""
+        pl, _, _ = self._rows_plan_struct(split=True)
+        L = N.load_library()
+        need, from_rows = ctypes.c_size_t(), ctypes.c_int64()
+        N.check(L.pgm_rows_plan_stream_source(ctypes.byref(pl), None, 0, ctypes.byref(need), None), "rows_plan_stream_source")
+        buf = ctypes.create_string_buffer(need.value)
+        N.check(L.pgm_rows_plan_stream_source(ctypes.byref(pl), buf, need.value, None, ctypes.byref(from_rows)),
+                "rows_plan_stream_source")
+        return buf.value.decode(), from_rows.value
+
     def _make_rows_plan(self, split):
         pl, values, n_comp = self._rows_plan_struct(split)
         L = N.lib()

@@ -4,7 +4,8 @@
 //   c++ -std=c++17 -g -fsanitize=address,undefined -I include -I pgmpy_amd/csrc
 //       tools/rows_plan_selftest.cpp pgmpy_amd/csrc/pgmrows_plan.cpp -o rows_plan_selftest
 // Exit status 0 and "rows_plan_selftest ok" when every check holds.  `--print` lists, per plan, what
-// the unit under test computes (descriptor words / SHA-256, source length / SHA-256) and checks nothing.
+// the unit under test computes (descriptor words / SHA-256, source length / SHA-256) and checks nothing;
+// `--source CASE WORD` writes a case's source under a cache-policy word (test_stream_policy) to stdout.
 //
 // The expected descriptor and source hashes below were recorded from the monolithic pgmhip.hip this
 // unit was split out of (its pgm_rows_plan_create / pgm_rows_plan_source on the same structs), so
@@ -12,6 +13,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -711,13 +713,98 @@ static int test_source_shape() {
   return 0;
 }
 
+// ---------------------------------------------------------------------------- cache policy of the stream
+// policy word as PGM_ROWS_STREAM reads it: bit 0 nontemporal code loads, bits 1-2 the store form
+static RowsPolicy policy_of(int w) {
+  RowsPolicy pol;
+  pol.nt_loads = (w & 1) != 0;
+  pol.stores = (w >> 1) & 3;
+  return pol;
+}
+
+static size_t count_of(const std::string &s, const char *what) {
+  size_t n = 0;
+  for (size_t at = s.find(what); at != std::string::npos; at = s.find(what, at + 1)) ++n;
+  return n;
+}
+
+static void replace_all(std::string &s, const std::string &from, const std::string &to) {
+  for (size_t at = s.find(from); at != std::string::npos; at = s.find(from, at + to.size())) s.replace(at, from.size(), to);
+}
+
+// `--source CASE WORD`: the source of a case under a policy word, for the compile test
+static int print_source(const char *name, int word) {
+  for (size_t i = 0; i < kNumCases; ++i) {
+    if (strcmp(kCases[i].name, name)) continue;
+    const pgm_rows_plan p = kCases[i].make();
+    std::string src;
+    if (word < 0 || word > 5 || rows_plan_source(&p, src, policy_of(word)) != PGM_OK) return 1;
+    fwrite(src.data(), 1, src.size(), stdout);
+    return 0;
+  }
+  return 1;
+}
+
+static int test_stream_policy() {
+  CHECK(RowsPolicy().is_default() && policy_of(0).is_default() && !policy_of(1).is_default() && !policy_of(2).is_default());
+  for (size_t i = 0; i < kNumCases; ++i) {
+    const pgm_rows_plan p = kCases[i].make();
+    RowsPlan r;
+    CHECK(rows_plan_compile(&p, r) == PGM_OK);
+    if (r.any_table) continue;
+    std::string def;
+    CHECK(rows_plan_source(&p, def, policy_of(0)) == PGM_OK && def == r.jit_src);  // the default policy: today's bytes
+    const size_t body0 = def.find("extern \"C\"");
+    CHECK(body0 != std::string::npos);
+    const size_t n_plain1 = count_of(def, " = cr[") + count_of(def, " += cr[");
+    const size_t n_plain2 = count_of(def, " = *(const unsigned short *)(cr + ") + count_of(def, " += *(const unsigned short *)(cr + ");
+    const size_t n_coherent = count_of(def, "__hip_atomic_load((__attribute__((address_space(1))) unsigned short *)(cr + ");
+    CHECK(n_plain1 == n_plain2 && n_plain1 == 2 * n_coherent);  // jit + floor, jit2 + floor2, ring
+    for (int w = 1; w <= 5; ++w) {
+      const RowsPolicy pol = policy_of(w);
+      std::string src;
+      CHECK(rows_plan_source(&p, src, pol) == PGM_OK);
+      CHECK((src != def) == (pol.stores != RowsPolicy::kStoreSc1 || n_plain1 > 0));  // a plan may read no evidence
+      const size_t body = src.find("extern \"C\"");
+      CHECK(body != std::string::npos);
+      // loads: every plain code load and no other carries the hint; the ring's and the CPT's are untouched
+      CHECK(count_of(src, "__builtin_nontemporal_load(") == (pol.nt_loads ? n_plain1 + n_plain2 : 0));
+      CHECK(count_of(src, "__hip_atomic_load((__attribute__((address_space(1))) unsigned short *)(cr + ") == n_coherent);
+      CHECK(count_of(src, "V[") == count_of(def, "V["));
+      // stores: the macros alone change
+      const std::string pre = src.substr(0, body);
+      CHECK(count_of(pre, "#define PGM_WT") == 3);
+      if (pol.stores == RowsPolicy::kStoreSc1) {
+        CHECK(pre == def.substr(0, body0));
+      } else {
+        const bool sc0 = pol.stores == RowsPolicy::kStoreSc0Sc1Nt;
+        CHECK(count_of(pre, sc0 ? "off sc0 sc1 nt\"" : "off sc1 nt\"") == 2 && count_of(pre, "__hip_atomic_store") == 0);
+        CHECK(count_of(pre, sc0 ? ", 0, 19); }" : ", 0, 18); }") == 1);
+        CHECK(count_of(pre, "global_store_dword %0") == 1 && count_of(pre, "global_store_dwordx2 %0") == 1);
+      }
+      // the bodies are the default's once the hint is taken off
+      std::string b = src.substr(body);
+      replace_all(b, "__builtin_nontemporal_load(&cr[", "cr[");
+      replace_all(b, "__builtin_nontemporal_load((const unsigned short *)(cr + ", "*(const unsigned short *)(cr + ");
+      if (pol.nt_loads) {
+        replace_all(b, " * ldc]);\n", " * ldc];\n");
+        replace_all(b, " * ldc));\n", " * ldc);\n");
+      }
+      CHECK(b == def.substr(body0));
+    }
+  }
+  return 0;
+}
+
 int main(int argc, char **argv) {
   if (argc > 1 && !strcmp(argv[1], "--print")) return print_cases();
+  if (argc > 3 && !strcmp(argv[1], "--source")) return print_source(argv[2], atoi(argv[3]));
   CHECK(sha256("abc", 3) == "ba7816bf8f01cfea414140de5dae2223b00361a396177a9cb410ff61f20015ad");
   CHECK(sha256("abcdbcdecdefdefgefghfghighijhijkijkljklmklmnlmnomnopnopq", 56) ==
         "248d6a61d20638b8e5c026930c3e6039a33ce45964ff2167f6ecedd419db06c1");  // two blocks
   if (test_recorded() || test_affine_nq1() || test_nq0() || test_two_comp() || test_table_2x3() ||
-      test_term_padding() || test_rejected() || test_rows2_aligned() || test_launch_info() || test_source_shape())
+      test_term_padding() || test_rejected() || test_rows2_aligned() || test_launch_info() || test_source_shape() ||
+      test_stream_policy())
     return 1;
   printf("rows_plan_selftest ok\n");
   return 0;
