@@ -15,6 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 # one hipcc command: the .hip units carry the kernels, the .cpp units are host code
 SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmhip.hip",        # primitive factor kernels + their C-ABI, the error string
+    "pgmprim_plan.cpp",  # primitive factor kernels: descriptor validation, dim coalescing, kernel and geometry choice, batch job assembly (host only)
     "pgmrows.hip",       # fused row plan: kernels + C-ABI
     "pgmrows_plan.cpp",  # fused row plan: plan compiler + generator of the specialised source (host only)
     "pgmfit.hip",        # parameter learning: family-count + CPD finishing kernels, their C-ABI

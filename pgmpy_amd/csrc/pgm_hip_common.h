@@ -1,7 +1,8 @@
 // pgm_hip_common.h — what the HIP units (pgmhip.hip, pgmrows.hip, pgmfit.hip, pgmsample.hip, pgmgibbs.hip,
 // pgmpm.cpp) share: the HIP error check of a C-ABI entry point and the stream cast; and for the plan handles of the
 // last three the HIP side of pgm_plan_dev.h and the flagged launch.  The one error string lives in
-// pgmhip.hip (pgmi_failf).
+// pgmhip.hip (pgmi_failf); the host-only plan units (pgmprim_plan.cpp with plan_contract among them) include
+// none of this and report through pgmi_failf alone.
 #pragma once
 #include <hip/hip_runtime.h>
 

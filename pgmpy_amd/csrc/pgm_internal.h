@@ -1,4 +1,5 @@
-// pgm_internal.h — private interface between pgmhip.hip / pgmrows.hip (kernels, C-ABI), pgmdq.cpp (direct AQL
+// pgm_internal.h — private interface between pgmhip.hip / pgmrows.hip (kernels, C-ABI), pgmprim_plan.cpp (the
+// primitive planner, host only: plan_contract, plan_gather, plan_contract_n), pgmdq.cpp (direct AQL
 // dispatch), pgmpm.cpp (plan-specialised batched-BP steps: hipRTC, bound launches) and pgmpm_gen.cpp (their
 // planner and source generators, host only).  Not part of the C-ABI of include/pgmhip.h.
 #pragma once
@@ -46,8 +47,8 @@ inline FDiv make_fdiv(uint32_t d) {
   return FDiv{d, (uint32_t)m, l};
 }
 
-// a planned contraction (pgmhip.hip plan_contract; the generic kernels read it, pgmpm.cpp compiles a
-// batch of them into a specialised kernel)
+// a planned contraction (pgmprim_plan.cpp plan_contract; the generic kernels of pgmhip.hip read it,
+// pgmpm.cpp compiles a batch of them into a specialised kernel)
 struct ContractK {
   int32_t nk, nr, g_log2, n_split;
   uint32_t n_out, n_red, red_chunk, row_mode;  // red_chunk: reduction-OUTER indices per split

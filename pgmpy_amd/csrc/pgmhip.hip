@@ -4,6 +4,10 @@
 // (pgmpy_amd/build.py).  Declarations and the reference call site each entry
 // point replaces: include/pgmhip.h.  Design, data layout and the roofline of
 // every kernel: DESIGN.md.  The fused row plan (k_rows, pgm_rows_*) is pgmrows.hip.
+// The host arithmetic that decides which kernel a descriptor runs and with what
+// geometry (plan_contract, plan_prodn, plan_gather, plan_contract_n, the batch job
+// assembly) and the entry points that never touch the device are pgmprim_plan.cpp
+// (pgm_prim.h); an entry point here calls the planner, returns its status, launches.
 //
 // Kernels
 //   k_contract / k_contract_final  generic strided broadcast-combine + axis reduce (HBM-bound)
@@ -26,7 +30,10 @@
 
 #include "pgmhip.h"
 #include "pgm_internal.h"
+#include "pgm_prim.h"
 #include "pgm_hip_common.h"
+
+using namespace pgmprim;
 
 #define PGM_ABI_VERSION 25  // 25: pgm_rows_launch_info (host-only query of the row-plan launch: kernel family, template arguments, row groups, grid, LDS; pgm_rows_plan_run takes its choice from the same function); 24: pgm_contract_info (host-only query of the planned contraction kernel; the launcher takes its choice from the same function); 23: pgm_batch_add_contract_n (n-ary contraction jobs), pgm_dq_timer_dispatch_times, pgm_host_scan_* / pgm_host_lut_map_u8; 22: pgm_dq_bind_pm / pgm_dq_run_chain / pgm_dq_profiling; 21: pgm_batch_specialise; 20: pgm_batch_info and the grid-barrier levelled batch removed (levels: single-workgroup mode only); 19: pgm_stream_sync_spin; 18: pgm_batch_set_mode (single-workgroup levelled batch), pgm_batch_blocks; 17: pgm_rows_shard_run (rows sharded over several GPUs from host buffers); 16: pgm_rows_ring_start_ready; 15: pgm_batch_add_level / pgm_batch_info (levelled batch), pgm_memcpy_d2h_async; 14: pgm_rows_ring_* (resident ring of row batches); 13: pgm_dq_timer_dispatch_stats, pgm_rows_bound_kernel; 12: pgm_dq_launch_group, pgm_dq_timer_stop_ticks, PGM_ROWS_FLOOR; 11: pgm_product_n_marginal_bind / pgm_pm_bound_*; 10: pgm_dq_* direct AQL dispatch, pgm_codes_remap; 9: gemm lane_order, batch product_n / indicator
 
@@ -396,7 +403,7 @@ __global__ __launch_bounds__(256) void k_contract_rows(const ContractK p, const 
 // Row mode, short reduction (n_red <= 512, no split): every reduction offset is decoded once per
 // block into LDS, then each row sums flat over them with 8 loads and 8 accumulators in flight
 // (a BP separator marginal: a few clique variables summed for every (separator state, row)).
-#define RTAB_MAX 512
+// (RTAB_MAX: pgm_prim.h)
 template <int CMB, int RED>
 __global__ __launch_bounds__(256) void k_contract_rows_tab(const ContractK p, const double *__restrict__ A,
                                                            const double *__restrict__ B, double *__restrict__ C) {
@@ -527,207 +534,15 @@ __global__ __launch_bounds__(256) void k_contract_final(const ContractK p, const
   }
 }
 
-// host: drop card-1 dims, merge dims that are contiguous for every operand
-struct Dims {
-  int n = 0;
-  int64_t card[PGM_MAX_DIMS];
-  int64_t s[3][PGM_MAX_DIMS];
-};
-
-static void coalesce(Dims &d, int nops) {
-  Dims o;
-  for (int i = 0; i < d.n; ++i) {
-    if (d.card[i] == 1) continue;
-    if (o.n > 0) {
-      bool ok = true;
-      const int j = o.n - 1;
-      for (int t = 0; t < nops; ++t)
-        if (o.s[t][j] != d.card[i] * d.s[t][i]) ok = false;
-      if (ok) {
-        o.card[j] *= d.card[i];
-        for (int t = 0; t < nops; ++t) o.s[t][j] = d.s[t][i];
-        continue;
-      }
-    }
-    o.card[o.n] = d.card[i];
-    for (int t = 0; t < nops; ++t) o.s[t][o.n] = d.s[t][i];
-    ++o.n;
-  }
-  d = o;
-}
-
-static const uint64_t kTargetThreads = 256ull * 2048;  // 256 CUs x 32 waves x 64 lanes
-
-struct ContractLaunch {
-  ContractK k;
-  dim3 grid;
-  uint64_t ws_doubles;
-  bool empty;
-};
-
-static int plan_contract(const pgm_contract_desc *d, ContractLaunch &L) {
-  if (!d) return fail(PGM_EINVAL, "contract: null descriptor");
-  if (d->n_keep < 0 || d->n_keep > PGM_MAX_DIMS || d->n_red < 0 || d->n_red > PGM_MAX_DIMS)
-    return fail(PGM_EINVAL, "contract: n_keep/n_red out of range (%d, %d)", d->n_keep, d->n_red);
-  if (d->combine < 0 || d->combine > 4 || d->reduce < 0 || d->reduce > 2)
-    return fail(PGM_EINVAL, "contract: bad combine/reduce (%d, %d)", d->combine, d->reduce);
-  if (d->reduce == PGM_RED_NONE && d->n_red > 0)
-    return fail(PGM_EINVAL, "contract: reduction dims given with PGM_RED_NONE");
-  Dims kd, rd;
-  kd.n = d->n_keep;
-  uint64_t n_out = 1, n_red = 1;
-  for (int i = 0; i < d->n_keep; ++i) {
-    if (d->keep_card[i] <= 0) return fail(PGM_EINVAL, "contract: keep_card[%d] = %lld", i, (long long)d->keep_card[i]);
-    kd.card[i] = d->keep_card[i];
-    kd.s[0][i] = d->keep_sa[i];
-    kd.s[1][i] = d->keep_sb[i];
-    kd.s[2][i] = d->keep_sc[i];
-    n_out *= (uint64_t)d->keep_card[i];
-  }
-  rd.n = d->n_red;
-  for (int i = 0; i < d->n_red; ++i) {
-    if (d->red_card[i] <= 0) return fail(PGM_EINVAL, "contract: red_card[%d] = %lld", i, (long long)d->red_card[i]);
-    rd.card[i] = d->red_card[i];
-    rd.s[0][i] = d->red_sa[i];
-    rd.s[1][i] = d->red_sb[i];
-    n_red *= (uint64_t)d->red_card[i];
-  }
-  if (n_out >= (1ull << 31) || n_red >= (1ull << 31))
-    return fail(PGM_EINVAL, "contract: index space too large (%llu x %llu; limit 2^31 each)",
-                (unsigned long long)n_out, (unsigned long long)n_red);
-  coalesce(kd, 3);
-  coalesce(rd, 2);
-  // few outputs (flat mode) and one long reduction run: cut the run into (outer x chunk) so the
-  // split-K below has reduction-outer indices to distribute (a batched dot product over a packed
-  // operand pair would otherwise leave 64 lanes per output walking the whole run)
-  if (d->reduce != PGM_RED_NONE && rd.n > 0 && rd.n < KMAX && kd.n <= KMAX && n_out <= 4096 &&
-      !(kd.n > 0 && kd.card[kd.n - 1] >= 64)) {
-    const int64_t ri = rd.card[rd.n - 1];
-    if (ri >= 8192 && n_red / (uint64_t)ri < 256) {
-      for (int64_t c = 4096; c >= 256; c >>= 1) {
-        if (ri % c) continue;
-        const int last = rd.n - 1;
-        rd.card[rd.n] = c;
-        rd.s[0][rd.n] = rd.s[0][last];
-        rd.s[1][rd.n] = rd.s[1][last];
-        rd.card[last] = ri / c;
-        rd.s[0][last] *= c;
-        rd.s[1][last] *= c;
-        ++rd.n;
-        break;
-      }
-    }
-  }
-  if (kd.n > KMAX || rd.n > KMAX)
-    return fail(PGM_EINVAL, "contract: %d keep / %d reduce dims after coalescing (limit %d)", kd.n, rd.n, KMAX);
-  ContractK &k = L.k;
-  memset(&k, 0, sizeof k);
-  k.nk = kd.n;
-  k.nr = rd.n;
-  for (int i = 0; i < kd.n; ++i) {
-    k.kdiv[i] = make_fdiv((uint32_t)kd.card[i]);
-    k.ksa[i] = kd.s[0][i];
-    k.ksb[i] = kd.s[1][i];
-    k.ksc[i] = kd.s[2][i];
-  }
-  for (int i = 0; i < rd.n; ++i) {
-    k.rdiv[i] = make_fdiv((uint32_t)rd.card[i]);
-    k.rsa[i] = rd.s[0][i];
-    k.rsb[i] = rd.s[1][i];
-  }
-  k.n_out = (uint32_t)n_out;
-  k.n_red = (uint32_t)n_red;
-  L.empty = (n_out == 0);
-  // reduction = outer (decoded, wave-uniform) x innermost (walked by increments)
-  if (rd.n > 0) {
-    k.ri_card = (uint32_t)rd.card[rd.n - 1];
-    k.ri_sa = rd.s[0][rd.n - 1];
-    k.ri_sb = rd.s[1][rd.n - 1];
-  } else {
-    k.ri_card = 1;
-    k.ri_sa = k.ri_sb = 0;
-  }
-  k.n_ro = (uint32_t)(n_red / k.ri_card);
-  const bool has_red = d->reduce != PGM_RED_NONE && n_red > 1;
-  const uint64_t NX = kd.n > 0 ? (uint64_t)kd.card[kd.n - 1] : 1;
-  // row mode when the innermost output dim fills waves and no lane-parallel reduction is needed
-  const bool red_contig = rd.n > 0 && rd.s[0][rd.n - 1] == 1;
-  k.row_mode = (kd.n > 0 && NX >= 64 && !(has_red && red_contig && NX < 256 && n_out < kTargetThreads)) ? 1 : 0;
-  int g_log2 = 0;
-  uint32_t n_split = 1;
-  if (k.row_mode) {
-    const uint64_t n_outer = n_out / NX;
-    const uint64_t xchunks = (NX + 255) / 256;
-    const uint64_t target_blocks = 2048;
-    uint64_t gy = std::min<uint64_t>(n_outer, 65535);
-    uint64_t gx = std::min<uint64_t>(xchunks, std::max<uint64_t>(1, target_blocks / gy));
-    k.ri_chunk = k.ri_card;
-    k.ri_nb = 1;
-    if (has_red && gx * gy < target_blocks / 2) {
-      // few outputs and a long reduction: split it (virtual outer index = (ro, chunk of the inner dim))
-      const uint64_t want = (target_blocks / 2 + gx * gy - 1) / (gx * gy);
-      if (k.n_ro < want && k.ri_card >= 64) {
-        const uint64_t nb = std::min<uint64_t>((want + k.n_ro - 1) / k.n_ro, k.ri_card / 16);
-        k.ri_nb = (uint32_t)std::max<uint64_t>(nb, 1);
-        k.ri_chunk = (uint32_t)((k.ri_card + k.ri_nb - 1) / k.ri_nb);
-        k.ri_nb = (k.ri_card + k.ri_chunk - 1) / k.ri_chunk;
-      }
-      n_split = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(want, (uint64_t)k.n_ro * k.ri_nb), 256);
-    }
-    k.n_v = k.n_ro * k.ri_nb;
-    L.grid = dim3((unsigned)gx, (unsigned)gy, n_split);
-  } else {
-    if (has_red) {
-      while (g_log2 < 6 && (n_out << g_log2) < kTargetThreads && (1ull << (g_log2 + 1)) <= k.ri_card) ++g_log2;
-      const uint64_t par = n_out << g_log2;
-      if (par < kTargetThreads / 4 && k.n_ro > 1) {
-        uint64_t want = (kTargetThreads / 4 + par - 1) / par;
-        n_split = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(want, k.n_ro), 1024);
-      }
-    }
-    const uint64_t threads = n_out << g_log2;
-    uint64_t blocks = (threads + 255) / 256;
-    blocks = std::min<uint64_t>(std::max<uint64_t>(blocks, 1), 65535);
-    L.grid = dim3((unsigned)blocks, n_split, 1);
-  }
-  k.g_log2 = g_log2;
-  k.n_split = (int32_t)n_split;
-  k.red_chunk = k.row_mode ? (uint32_t)((k.n_v + n_split - 1) / n_split) : (uint32_t)((k.n_ro + n_split - 1) / n_split);
-  L.ws_doubles = n_split > 1 ? (uint64_t)n_split * n_out : 0;
-  return PGM_OK;
-}
-
-// two-rows-per-lane eligibility of a row-mode COPY contraction (A read, C written); r01's 8-B-only row
-// paths ran at 0.54-0.70x the 16-B rate
-static bool rows2_ok(const ContractK &k, const double *A, const double *C) {
-  if (!k.row_mode || k.nk < 1) return false;
-  const int kx = k.nk - 1;
-  if (k.kdiv[kx].d % 2 || k.ksa[kx] != 1 || k.ksc[kx] != 1) return false;
-  if (((uintptr_t)A & 15) || ((uintptr_t)C & 15)) return false;
-  for (int i = 0; i < kx; ++i)
-    if (k.ksa[i] % 2 || k.ksc[i] % 2) return false;
-  for (int i = 0; i < k.nr; ++i)
-    if (k.rsa[i] % 2) return false;
-  return k.nr == 0 || k.ri_sa % 2 == 0;
-}
-
-// the kernel a planned contraction runs (enum pgm_contract_kernel) and its grid: the one place that
-// decides it, for the launcher and for pgm_contract_info
-static int contract_kernel(const ContractLaunch &L, int combine, int reduce, const double *A, const double *C,
-                           dim3 &grid) {
-  grid = L.grid;
-  if (!L.k.row_mode) return PGM_CK_FLAT;
-  if (reduce == PGM_RED_NONE || L.k.n_split != 1 || L.k.ri_nb != 1 || L.k.n_red > RTAB_MAX) return PGM_CK_ROWS;
-  if (combine != PGM_COMBINE_COPY || !rows2_ok(L.k, A, C)) return PGM_CK_ROWS_TAB;
-  grid.x = (unsigned)std::max<uint64_t>(1, (grid.x + 1) / 2);
-  return PGM_CK_ROWS_TAB2;
-}
+// the plan of a contraction (plan_contract) and the kernel it runs (contract_kernel): pgmprim_plan.cpp
 
 template <int CMB, int RED>
 static void launch_contract_t(const ContractLaunch &L, const double *A, const double *B, double *C, double *ws,
                               hipStream_t s) {
-  dim3 g;
-  switch (contract_kernel(L, CMB, RED, A, C, g)) {
+  uint32_t grid[3];
+  const int kernel = contract_kernel(L, CMB, RED, A, C, grid);
+  const dim3 g(grid[0], grid[1], grid[2]);
+  switch (kernel) {
     case PGM_CK_ROWS_TAB2: hipLaunchKernelGGL((k_contract_rows_tab2<RED>), g, dim3(256), 0, s, L.k, A, C); break;
     case PGM_CK_ROWS_TAB: hipLaunchKernelGGL((k_contract_rows_tab<CMB, RED>), g, dim3(256), 0, s, L.k, A, B, C); break;
     case PGM_CK_ROWS: hipLaunchKernelGGL((k_contract_rows<CMB, RED>), g, dim3(256), 0, s, L.k, A, B, C, ws); break;
@@ -751,16 +566,7 @@ static void launch_contract_c(int red, const ContractLaunch &L, const double *A,
 }
 
 // ----------------------------------------------------------------------------- n-ary product
-struct ProdNK {
-  int32_t n_ops, nk;
-  int32_t kind[PMAX];
-  uint32_t n_out, row_mode;
-  uint32_t pairs, _pad;  // batched jobs: two innermost elements per lane with 16-B accesses
-  FDiv kdiv[KMAX];
-  int64_t ksc[KMAX];
-  int64_t ks[PMAX][KMAX];
-  const double *ops[PMAX];
-};
+// ProdNK (a planned n-ary product): pgm_prim.h
 
 // all operand values first (unused slots alias operand 0 with stride 0, so every load is valid and
 // no load sits behind a branch), then the product with the per-operand kinds (uniform branches)
@@ -1160,18 +966,7 @@ __device__ __forceinline__ void indicator_body(const uint8_t *__restrict__ codes
 // block map, each job runs the flat-mode contraction (or the gather) over its own blocks.  One
 // level of a compiled contraction path (all steps whose inputs are ready) is one launch instead
 // of one launch per step.
-struct BatchJob {
-  int32_t kind, cmb, red, _pad;  // kind 0: contraction, 1: gather, 2: n-ary product, 3: findings indicator
-  int64_t ind_rows, ind_card, ind_s_state, ind_s_row;
-  uint32_t block0, nblocks;
-  const double *A, *B;
-  double *C;
-  const uint8_t *codes;
-  int32_t *err;
-  ContractK c;
-  GatherK g;
-  ProdNK pn;
-};
+// BatchJob: pgm_prim.h
 
 template <int CMB>
 __device__ __forceinline__ void batch_contract_c(const BatchJob &J, uint64_t tid, uint64_t n) {
@@ -1198,18 +993,7 @@ __global__ __launch_bounds__(256) void k_batch(const BatchJob *__restrict__ jobs
   batch_block(jobs, block_job, blockIdx.x);
 }
 
-// A single-workgroup levelled batch of contractions only (the tail of a contraction path, C1 / C2): the
-// job descriptors (contraction part only), the block map and the level table are copied into LDS once at
-// the start — every load of them independent, issued together — so each level's blocks read their
-// descriptor from LDS instead of a block-map load followed by a dependent descriptor load from memory
-// (two round trips per level).  Same per-job code as k_batch_c, so the same results bit for bit.
-struct alignas(16) ChainJob {
-  int32_t cmb, red;
-  uint32_t block0, nblocks;
-  const double *A, *B;
-  double *C;
-  ContractK c;
-};
+// ChainJob (a job of a single-workgroup levelled batch of contractions, staged in LDS): pgm_prim.h
 
 template <int CMB>
 __device__ __forceinline__ void chain_contract_c(const ChainJob &J, uint64_t tid, uint64_t n) {
@@ -1911,48 +1695,6 @@ int pgm_event_elapsed_ms(void *start, void *stop, float *ms) {
   return PGM_OK;
 }
 
-int pgm_contract_workspace(const pgm_contract_desc *d, size_t *bytes) {
-  STALE_PROBE();
-  if (!bytes) return fail(PGM_EINVAL, "null pointer");
-  ContractLaunch L;
-  int rc = plan_contract(d, L);
-  if (rc) return rc;
-  *bytes = L.ws_doubles * sizeof(double);
-  return PGM_OK;
-}
-
-int pgm_contract_info(const pgm_contract_desc *d, const double *A, const double *C, pgm_contract_info_t *info) {
-  if (!info) return fail(PGM_EINVAL, "null pointer");
-  ContractLaunch L;
-  int rc = plan_contract(d, L);
-  if (rc) return rc;
-  memset(info, 0, sizeof *info);
-  const ContractK &k = L.k;
-  dim3 g;
-  info->kernel = contract_kernel(L, d->combine, d->reduce, A, C, g);
-  info->g_log2 = k.g_log2;
-  info->n_split = (uint32_t)k.n_split;
-  info->red_chunk = k.red_chunk;
-  info->ri_nb = k.ri_nb;
-  info->ri_chunk = k.ri_chunk;
-  info->grid[0] = g.x;
-  info->grid[1] = g.y;
-  info->grid[2] = g.z;
-  info->n_ro = k.n_ro;
-  info->n_v = k.n_v;
-  info->n_out = k.n_out;
-  info->n_red = k.n_red;
-  info->ri_card = k.ri_card;
-  const uint64_t NX = k.nk > 0 ? k.kdiv[k.nk - 1].d : 1;
-  info->nx = (uint32_t)NX;
-  info->unrolled = info->kernel == PGM_CK_ROWS && d->reduce == PGM_RED_NONE && NX > 3ull * g.x * 256;
-  // split s covers reduction-outer indices [s * red_chunk, ...): empty once that start is past the end
-  const uint64_t units = k.row_mode ? k.n_v : k.n_ro;
-  const uint64_t used = k.red_chunk ? (units + k.red_chunk - 1) / k.red_chunk : 0;
-  info->empty_splits = (uint32_t)((uint64_t)k.n_split > used ? (uint64_t)k.n_split - used : 0);
-  return PGM_OK;
-}
-
 int pgm_contract(const pgm_contract_desc *d, const double *A, const double *B, double *C, void *workspace,
                  size_t workspace_bytes, void *stream) {
   STALE_PROBE();
@@ -1978,96 +1720,22 @@ int pgm_contract(const pgm_contract_desc *d, const double *A, const double *B, d
   return PGM_OK;
 }
 
-}  // extern "C"
-
-// descriptor -> kernel parameters (coalesced dims, aliased unused operand slots); shared by
-// pgm_product_n and the batched product_n job
-static int plan_prodn(const pgm_productn_desc *d, const double *const *ops, ProdNK &k) {
-  if (!d || !ops) return fail(PGM_EINVAL, "product_n: null argument");
-  if (d->n_ops < 1 || d->n_ops > PMAX || d->n_keep < 0 || d->n_keep > PGM_MAX_DIMS)
-    return fail(PGM_EINVAL, "product_n: n_ops %d (1..%d) / n_keep %d", d->n_ops, PMAX, d->n_keep);
-  // coalesce: one Dims per group of up to 3 operand strides is not enough -> do it by hand
-  int n = 0;
-  int64_t card[PGM_MAX_DIMS], sc[PGM_MAX_DIMS], so[PMAX][PGM_MAX_DIMS];
-  uint64_t n_out = 1;
-  for (int i = 0; i < d->n_keep; ++i) {
-    if (d->keep_card[i] <= 0) return fail(PGM_EINVAL, "product_n: keep_card[%d] <= 0", i);
-    n_out *= (uint64_t)d->keep_card[i];
-    if (d->keep_card[i] == 1) continue;
-    if (n > 0) {
-      bool ok = sc[n - 1] == d->keep_card[i] * d->keep_sc[i];
-      for (int t = 0; t < d->n_ops; ++t) ok = ok && so[t][n - 1] == d->keep_card[i] * d->keep_s[t][i];
-      if (ok) {
-        card[n - 1] *= d->keep_card[i];
-        sc[n - 1] = d->keep_sc[i];
-        for (int t = 0; t < d->n_ops; ++t) so[t][n - 1] = d->keep_s[t][i];
-        continue;
-      }
-    }
-    card[n] = d->keep_card[i];
-    sc[n] = d->keep_sc[i];
-    for (int t = 0; t < d->n_ops; ++t) so[t][n] = d->keep_s[t][i];
-    ++n;
-  }
-  if (n_out >= (1ull << 31)) return fail(PGM_EINVAL, "product_n: output too large");
-  if (n > KMAX) return fail(PGM_EINVAL, "product_n: %d dims after coalescing (limit %d)", n, KMAX);
-  memset(&k, 0, sizeof k);
-  k.n_ops = d->n_ops;
-  k.nk = n;
-  k.n_out = (uint32_t)n_out;
-  for (int i = 0; i < n; ++i) {
-    k.kdiv[i] = make_fdiv((uint32_t)card[i]);
-    k.ksc[i] = sc[i];
-    for (int t = 0; t < d->n_ops; ++t) k.ks[t][i] = so[t][i];
-  }
-  for (int t = 0; t < d->n_ops; ++t) {
-    if (!ops[t]) return fail(PGM_EINVAL, "product_n: null operand %d", t);
-    k.ops[t] = ops[t];
-    k.kind[t] = d->op_kind[t];
-    if (d->op_kind[t] < 0 || d->op_kind[t] > 2) return fail(PGM_EINVAL, "product_n: bad op_kind[%d]", t);
-    if (d->op_kind[t] == PGM_PRODN_RATIO && (t + 1 >= d->n_ops || d->op_kind[t + 1] != PGM_PRODN_DEN))
-      return fail(PGM_EINVAL, "product_n: a RATIO operand must be followed by its DEN operand");
-    if (d->op_kind[t] == PGM_PRODN_DEN && (t == 0 || d->op_kind[t - 1] != PGM_PRODN_RATIO))
-      return fail(PGM_EINVAL, "product_n: a DEN operand must follow a RATIO operand");
-  }
-  for (int t = d->n_ops; t < PMAX; ++t) {  // unused slots alias operand 0 with stride 0 (valid loads)
-    k.ops[t] = k.ops[0];
-    k.kind[t] = PGM_PRODN_MUL;
-    for (int i = 0; i < n; ++i) k.ks[t][i] = 0;
-  }
-  const uint64_t NX = n > 0 ? (uint64_t)card[n - 1] : 1;
-  k.row_mode = (n > 0 && NX >= 64) ? 1 : 0;
-  return PGM_OK;
-}
-
-extern "C" {
-
 int pgm_product_n(const pgm_productn_desc *d, const double *const *ops, double *C, void *stream) {
   STALE_PROBE();
   if (!d || !ops || !C) return fail(PGM_EINVAL, "product_n: null argument");
   ProdNK k;
   const int prc = plan_prodn(d, ops, k);
   if (prc != PGM_OK) return prc;
-  const int n = k.nk;
   const uint64_t n_out = k.n_out;
-  const uint64_t NX = n > 0 ? (uint64_t)k.kdiv[n - 1].d : 1;
-  const int64_t *sc = k.ksc;
+  const uint64_t NX = k.nk > 0 ? (uint64_t)k.kdiv[k.nk - 1].d : 1;
+  uint32_t g[3] = {1, 1, 1};
   // two rows per lane when every access is 16-B aligned (batched BP: rows innermost, even count)
-  bool rows2 = k.row_mode && (NX % 2 == 0) && sc[n - 1] == 1 && ((uintptr_t)C & 15) == 0;
-  for (int i = 0; rows2 && i < n - 1; ++i) rows2 = (sc[i] % 2) == 0;
-  for (int t = 0; rows2 && t < d->n_ops; ++t) {
-    const int64_t sx = k.ks[t][n - 1];
-    rows2 = sx == 0 || (sx == 1 && ((uintptr_t)ops[t] & 15) == 0);
-    for (int i = 0; rows2 && sx == 1 && i < n - 1; ++i) rows2 = (k.ks[t][i] % 2) == 0;
-  }
-  dim3 grid;
-  if (rows2) {
-    const uint64_t NP = NX / 2, n_outer = n_out / NX;
+  if (k.row_mode && prodn_pairs_ok(k, C)) {
+    const uint64_t NP = NX / 2;
     const uint64_t bs = std::min<uint64_t>(256, (NP + 63) / 64 * 64);
-    const uint64_t gy = std::min<uint64_t>(n_outer, 65535);
-    const uint64_t gx = std::min<uint64_t>((NP + bs - 1) / bs, std::max<uint64_t>(1, 2048 / gy));
+    row_grid(n_out / NX, (NP + bs - 1) / bs, g);
     hipStream_t s = S(stream);
-    const dim3 g2((unsigned)gx, (unsigned)gy, 1), b2((unsigned)bs);
+    const dim3 g2(g[0], g[1], 1), b2((unsigned)bs);
     switch (d->n_ops <= 2 ? 2 : d->n_ops <= 4 ? 4 : 8) {
       case 2: hipLaunchKernelGGL((k_productn_rows2<2>), g2, b2, 0, s, k, C); break;
       case 4: hipLaunchKernelGGL((k_productn_rows2<4>), g2, b2, 0, s, k, C); break;
@@ -2076,14 +1744,11 @@ int pgm_product_n(const pgm_productn_desc *d, const double *const *ops, double *
     HIP_TRY(hipGetLastError());
     return PGM_OK;
   }
-  if (k.row_mode) {
-    const uint64_t xchunks = (NX + 255) / 256, n_outer = n_out / NX;
-    const uint64_t gy = std::min<uint64_t>(n_outer, 65535);
-    const uint64_t gx = std::min<uint64_t>(xchunks, std::max<uint64_t>(1, 2048 / gy));
-    grid = dim3((unsigned)gx, (unsigned)gy, 1);
-  } else {
-    grid = dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>((n_out + 255) / 256, 1), 65535), 1, 1);
-  }
+  if (k.row_mode)
+    row_grid(n_out / NX, (NX + 255) / 256, g);
+  else
+    g[0] = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n_out + 255) / 256, 1), 65535);
+  const dim3 grid(g[0], g[1], 1);
   hipStream_t s = S(stream);
   switch (d->n_ops <= 2 ? 2 : d->n_ops <= 4 ? 4 : 8) {
     case 2: hipLaunchKernelGGL((k_productn<2>), grid, dim3(256), 0, s, k, C); break;
@@ -2181,54 +1846,7 @@ int pgm_graph_destroy(void *graph_exec) {
 
 }  // extern "C"
 
-static int plan_gather(const pgm_gather_desc *d, GatherK &k) {
-  if (d->n_keep < 0 || d->n_keep > KMAX || d->n_ev < 0 || d->n_ev > PGM_MAX_DIMS)
-    return fail(PGM_EINVAL, "gather: n_keep %d (limit %d) / n_ev %d", d->n_keep, KMAX, d->n_ev);
-  if (d->batch_dim >= d->n_keep) return fail(PGM_EINVAL, "gather: batch_dim out of range");
-  memset(&k, 0, sizeof k);
-  k.nk = d->n_keep;
-  k.n_ev = d->n_ev;
-  k.batch_dim = d->batch_dim;
-  k.ld = d->ld;
-  k.row0 = d->row0;
-  uint64_t n_out = 1;
-  for (int i = 0; i < d->n_keep; ++i) {
-    if (d->keep_card[i] <= 0) return fail(PGM_EINVAL, "gather: keep_card[%d] <= 0", i);
-    n_out *= (uint64_t)d->keep_card[i];
-    k.kdiv[i] = make_fdiv((uint32_t)d->keep_card[i]);
-    k.ksa[i] = d->keep_sa[i];
-    k.ksc[i] = d->keep_sc[i];
-  }
-  if (n_out >= (1ull << 31)) return fail(PGM_EINVAL, "gather: output too large");
-  for (int j = 0; j < d->n_ev; ++j) {
-    k.ev_col[j] = d->ev_col[j];
-    k.ev_stride[j] = d->ev_stride[j];
-    k.ev_card[j] = (int32_t)d->ev_card[j];
-  }
-  k.n_out = (uint32_t)n_out;
-  return PGM_OK;
-}
-
-struct BatchHandle {
-  std::vector<BatchJob> jobs;
-  std::vector<uint32_t> block_job;
-  std::vector<uint32_t> level_off{0};  // single-workgroup levelled batch: first block of each level (+ the end)
-  BatchJob *d_jobs = nullptr;
-  uint32_t *d_map = nullptr;
-  uint32_t *d_level = nullptr;
-  int32_t mode = PGM_BATCH_GRID;  // PGM_BATCH_ONE_WORKGROUP: k_batch_wg_c
-  int32_t spec = -1;  // every job a contraction with one (combine, reduce): combine * 3 + reduce; products: 100
-  ChainJob *d_chain = nullptr;  // ONE_WORKGROUP batch (contractions only): descriptors staged in LDS
-  size_t chain_lds = 0;         // dynamic LDS bytes of k_batch_wg_c
-  // r06: n-ary contraction jobs (kind 4; BatchJob::_pad indexes these): specialised kernel only
-  std::vector<ContractNK> njobs;
-  std::vector<std::vector<const double *>> nops;
-};
-
-static const int32_t kBatchSpecProducts = 100;  // BatchHandle::spec of a products-only batch
-// single-workgroup chains of contractions: descriptors, block map and level table staged in LDS
-// (k_batch_wg_c) up to this many bytes
-static const size_t kChainLdsMax = 48 * 1024;
+// plan_gather, BatchHandle and the batch caps: pgm_prim.h / pgmprim_plan.cpp
 
 template <int CMB>
 static void launch_batch_cr(int red, dim3 g, hipStream_t s, const BatchJob *jobs, const uint32_t *map) {
@@ -2249,23 +1867,6 @@ static void launch_batch_c(int spec, dim3 g, hipStream_t s, const BatchJob *jobs
     default: launch_batch_cr<PGM_COMBINE_COPY>(red, g, s, jobs, map); break;
   }
 }
-
-// a batch contraction job with a reduction takes G lanes per output (G a power of two up to the innermost
-// reduction extent) while its outputs x G stay under this many lanes (r04: 32 K / 128 K slower on C2,
-// profiles/r04p/)
-static uint64_t env_u64(const char *name, uint64_t dflt) {
-  const char *v = getenv(name);
-  return v && *v ? strtoull(v, nullptr, 10) : dflt;
-}
-static const uint64_t kBatchLanesCap = env_u64("PGM_BATCH_LANES_CAP", 4096);
-// workgroups one batch job may take (its lanes grid-stride over the job's outputs beyond that; r04:
-// 1,024 / 4,096 no faster on C1 / C2 / C4, profiles/r04j/)
-static const uint64_t kBatchMaxBlocks = env_u64("PGM_BATCH_MAX_BLOCKS", 256);
-// a batch contraction without a reduction (a broadcast product or a copy: one load per operand per output)
-// may take more workgroups than one that reduces: its lanes otherwise walk several outputs one after
-// another, a full memory round trip each (C2's 448,000-output product level: 11.7 -> 8.9 us at 1,024
-// blocks, profiles/r04t/), while the reducing jobs of a level were measured slower with more
-static const uint64_t kBatchMaxBlocksProduct = env_u64("PGM_BATCH_MAX_BLOCKS_PRODUCT", 1024);
 
 extern "C" {
 
@@ -2291,285 +1892,6 @@ int pgm_batch_create(void **handle) {
   return *handle ? PGM_OK : fail(PGM_ENOMEM, "batch_create: host allocation");
 }
 
-// 256-thread blocks a batch job of `threads` lanes takes (cap 0: kBatchMaxBlocks; its lanes grid-stride beyond)
-static uint64_t batch_job_blocks(uint64_t threads, uint64_t cap = 0) {
-  return std::min<uint64_t>(std::max<uint64_t>((threads + 255) / 256, 1), cap ? cap : kBatchMaxBlocks);
-}
-
-static int batch_append(BatchHandle *h, BatchJob &J, uint64_t threads, uint64_t cap = 0) {
-  if (h->d_jobs) return fail(PGM_EINVAL, "batch: already finalized");
-  const uint64_t nb = batch_job_blocks(threads, cap);
-  if (h->block_job.size() + nb > 0x7fffffffull) return fail(PGM_EINVAL, "batch: too many blocks");
-  J.block0 = (uint32_t)h->block_job.size();
-  J.nblocks = (uint32_t)nb;
-  h->block_job.insert(h->block_job.end(), nb, (uint32_t)h->jobs.size());
-  h->jobs.push_back(J);
-  return PGM_OK;
-}
-
-int pgm_batch_add_contract(void *handle, const pgm_contract_desc *d, const double *A, const double *B, double *C) {
-  STALE_PROBE();
-  BatchHandle *h = (BatchHandle *)handle;
-  if (!h || !A || !C) return fail(PGM_EINVAL, "batch_add_contract: null argument");
-  if (d && d->combine != PGM_COMBINE_COPY && !B) return fail(PGM_EINVAL, "batch_add_contract: null B");
-  ContractLaunch L;
-  int rc = plan_contract(d, L);
-  if (rc != PGM_OK) return rc;
-  if (L.empty) return PGM_OK;
-  BatchJob J;
-  memset(&J, 0, sizeof J);
-  J.kind = 0;
-  J.cmb = d->combine;
-  J.red = d->reduce;
-  J.A = A;
-  J.B = B;
-  J.C = C;
-  J.c = L.k;
-  // flat mode, no split: lanes per output grow while the job is small and the reduction long
-  ContractK &k = J.c;
-  k.row_mode = 0;
-  k.n_split = 1;
-  k.red_chunk = k.n_ro;
-  // (a single-workgroup levelled batch runs its blocks one after another: spread a job over at most
-  // one block's lanes there)
-  const uint64_t lanes_cap = h->mode == PGM_BATCH_ONE_WORKGROUP ? 256 : kBatchLanesCap;
-  int g = 0;
-  if (d->reduce != PGM_RED_NONE && (uint64_t)k.n_ro * k.ri_card > 1)
-    while (g < 6 && ((uint64_t)k.n_out << g) < lanes_cap && (1u << (g + 1)) <= k.ri_card) ++g;
-  k.g_log2 = g;
-  // output pairs with 16-B accesses when one lane per output is the choice anyway and every access
-  // along the innermost kept dim is aligned and unit-stride (or broadcast)
-  const int kx = k.nk - 1;
-  const bool use_b = d->combine != PGM_COMBINE_COPY;
-  bool pairs = g == 0 && kx >= 0 && k.kdiv[kx].d % 2 == 0 && k.ksc[kx] == 1 && ((uintptr_t)C & 15) == 0;
-  const bool va = pairs && k.ksa[kx] != 0, vb = pairs && use_b && k.ksb[kx] != 0;
-  pairs = pairs && (k.ksa[kx] == 0 || k.ksa[kx] == 1) && (!use_b || k.ksb[kx] == 0 || k.ksb[kx] == 1);
-  for (int i = 0; pairs && i < kx; ++i) pairs = k.ksc[i] % 2 == 0 && (!va || k.ksa[i] % 2 == 0) && (!vb || k.ksb[i] % 2 == 0);
-  for (int i = 0; pairs && i + 1 < k.nr; ++i) pairs = (!va || k.rsa[i] % 2 == 0) && (!vb || k.rsb[i] % 2 == 0);
-  if (pairs) pairs = (!va || (k.ri_sa % 2 == 0 && ((uintptr_t)A & 15) == 0)) && (!vb || (k.ri_sb % 2 == 0 && ((uintptr_t)B & 15) == 0));
-  if (pairs) {
-    k.row_mode = 2;
-    return batch_append(h, J, (uint64_t)k.n_out / 2, k.n_red <= 1 ? kBatchMaxBlocksProduct : 0);
-  }
-  return batch_append(h, J, (uint64_t)k.n_out << g, k.n_red <= 1 ? kBatchMaxBlocksProduct : 0);
-}
-
-int pgm_batch_add_gather(void *handle, const pgm_gather_desc *d, const double *A, const uint8_t *codes, double *C,
-                         int32_t *err_flag) {
-  STALE_PROBE();
-  BatchHandle *h = (BatchHandle *)handle;
-  if (!h || !d || !A || !C) return fail(PGM_EINVAL, "batch_add_gather: null argument");
-  if (d->n_ev > 0 && !codes) return fail(PGM_EINVAL, "batch_add_gather: null codes");
-  BatchJob J;
-  memset(&J, 0, sizeof J);
-  int rc = plan_gather(d, J.g);
-  if (rc != PGM_OK) return rc;
-  if (J.g.n_out == 0) return PGM_OK;
-  J.kind = 1;
-  J.A = A;
-  J.C = C;
-  J.codes = codes;
-  J.err = err_flag;
-  return batch_append(h, J, J.g.n_out);
-}
-
-int pgm_batch_add_product_n(void *handle, const pgm_productn_desc *d, const double *const *ops, double *C) {
-  STALE_PROBE();
-  BatchHandle *h = (BatchHandle *)handle;
-  if (!h || !C) return fail(PGM_EINVAL, "batch_add_product_n: null argument");
-  BatchJob J;
-  memset(&J, 0, sizeof J);
-  int rc = plan_prodn(d, ops, J.pn);
-  if (rc != PGM_OK) return rc;
-  if (J.pn.n_out == 0) return PGM_OK;
-  J.kind = 2;
-  J.C = C;
-  // pairs: 16-B accesses when every access along the innermost dim is aligned and unit/zero stride
-  ProdNK &k = J.pn;
-  const int kx = k.nk - 1;
-  bool pairs = kx >= 0 && k.kdiv[kx].d % 2 == 0 && k.ksc[kx] == 1 && ((uintptr_t)C & 15) == 0;
-  for (int i = 0; pairs && i < kx; ++i) pairs = k.ksc[i] % 2 == 0;
-  for (int t = 0; pairs && t < k.n_ops; ++t) {
-    const int64_t sx = k.ks[t][kx];
-    pairs = sx == 0 || (sx == 1 && ((uintptr_t)k.ops[t] & 15) == 0);
-    for (int i = 0; pairs && sx == 1 && i < kx; ++i) pairs = k.ks[t][i] % 2 == 0;
-  }
-  k.pairs = pairs ? 1u : 0u;
-  return batch_append(h, J, pairs ? k.n_out / 2 : k.n_out);
-}
-
-// an n-ary contraction's plan: unit dims dropped, adjacent dims merged where every operand (and C, for
-// kept dims) steps through them as one, G lanes per output for long reductions of few outputs
-static int plan_contract_n(const pgm_contractn_desc *d, const double *const *ops, ContractNK &k, bool need_ops = true) {
-  if (!d || (need_ops && !ops)) return fail(PGM_EINVAL, "contract_n: null argument");
-  const int n = d->n_ops;
-  if (n < 1 || n > MOPS) return fail(PGM_EINVAL, "contract_n: %d operands (1..%d)", n, MOPS);
-  if (d->reduce != PGM_RED_SUM && d->reduce != PGM_RED_MAX) return fail(PGM_EINVAL, "contract_n: reduce must be sum or max");
-  if (d->n_keep < 0 || d->n_keep > PGM_MAX_DIMS || d->n_red < 0 || d->n_red > PGM_MAX_DIMS)
-    return fail(PGM_EINVAL, "contract_n: %d kept / %d reduced dims", d->n_keep, d->n_red);
-  for (int t = 0; need_ops && t < n; ++t)
-    if (!ops[t]) return fail(PGM_EINVAL, "contract_n: operand %d is null", t);
-  memset(&k, 0, sizeof k);
-  k.n_ops = n;
-  k.red = d->reduce;
-  // kept dims (C-order: the last fastest), then reduced dims; each side merged from the inside out
-  struct Dim {
-    int64_t card, sc, s[MOPS];
-  };
-  auto collect = [&](int nd, const int64_t *card, const int64_t *sc, const int64_t (*st)[PGM_MAX_DIMS], std::vector<Dim> &out) {
-    for (int i = 0; i < nd; ++i) {
-      if (card[i] < 0) return false;
-      if (card[i] == 1) continue;
-      Dim x;
-      x.card = card[i];
-      x.sc = sc ? sc[i] : 0;
-      for (int t = 0; t < n; ++t) x.s[t] = st[t][i];
-      if (!out.empty()) {  // merge into the previous (outer) dim when it is this one's continuation
-        Dim &o = out.back();
-        bool ok = !sc || o.sc == x.sc * x.card;
-        for (int t = 0; ok && t < n; ++t) ok = o.s[t] == x.s[t] * x.card;
-        if (ok) {
-          o.card *= x.card;
-          o.sc = x.sc;
-          for (int t = 0; t < n; ++t) o.s[t] = x.s[t];
-          continue;
-        }
-      }
-      out.push_back(x);
-    }
-    return true;
-  };
-  std::vector<Dim> kd, rd;
-  for (int i = 0; i < d->n_keep; ++i)
-    if (d->keep_card[i] == 0) {
-      k.n_out = 0;
-      return PGM_OK;  // empty output: nothing to do
-    }
-  if (!collect(d->n_keep, d->keep_card, d->keep_sc, d->keep_s, kd) || !collect(d->n_red, d->red_card, nullptr, d->red_s, rd))
-    return fail(PGM_EINVAL, "contract_n: negative cardinality");
-  if ((int)kd.size() > KMAX || (int)rd.size() > KMAX)
-    return fail(PGM_EINVAL, "contract_n: %zu kept / %zu reduced dims after merging (at most %d each)", kd.size(), rd.size(), KMAX);
-  uint64_t n_out = 1, n_red = 1;
-  k.nk = (int)kd.size();
-  k.nr = (int)rd.size();
-  for (int i = 0; i < k.nk; ++i) {
-    n_out *= (uint64_t)kd[i].card;
-    if (n_out > 0x7fffffffull) return fail(PGM_EINVAL, "contract_n: output over 2^31 entries");
-    k.kcard[i] = (uint32_t)kd[i].card;
-    k.ksc[i] = kd[i].sc;
-    for (int t = 0; t < n; ++t) k.ks[t][i] = kd[i].s[t];
-  }
-  for (int i = 0; i < k.nr; ++i) {
-    if (rd[i].card == 0) {
-      n_red = 0;
-      break;
-    }
-    n_red *= (uint64_t)rd[i].card;
-    if (n_red > 0x7fffffffull) return fail(PGM_EINVAL, "contract_n: reduction over 2^31 entries");
-    k.rcard[i] = (uint32_t)rd[i].card;
-    for (int t = 0; t < n; ++t) k.rs[t][i] = rd[i].s[t];
-  }
-  if (n_red == 0) return fail(PGM_EINVAL, "contract_n: an empty reduction");
-  k.n_out = (uint32_t)n_out;
-  k.n_red = (uint32_t)n_red;
-  // lanes per output: up to 64 while the job's lanes stay under 4x a batch contraction's cap (a fused
-  // step's reduction is a walk of dependent load rounds; more lanes, fewer rounds each)
-  static const uint64_t nary_lanes = env_u64("PGM_NARY_LANES", 4 * kBatchLanesCap);
-  int g = 0;
-  if (k.nr > 0)
-    while (g < 6 && ((uint64_t)k.n_out << g) < nary_lanes && (1ull << (g + 1)) <= n_red) ++g;
-  k.g_log2 = g;
-  return PGM_OK;
-}
-
-// an n-ary job's lanes and block cap in a batch (pgm_batch_add_contract_n and pgm_contract_n_info)
-static uint64_t contract_n_threads(const ContractNK &k) { return (uint64_t)k.n_out << k.g_log2; }
-static uint64_t contract_n_cap(const ContractNK &k) { return k.nr == 0 ? kBatchMaxBlocksProduct : 0; }
-
-int pgm_batch_add_contract_n(void *handle, const pgm_contractn_desc *d, const double *const *ops, double *C) {
-  STALE_PROBE();
-  BatchHandle *h = (BatchHandle *)handle;
-  if (!h || !C) return fail(PGM_EINVAL, "batch_add_contract_n: null argument");
-  ContractNK k;
-  int rc = plan_contract_n(d, ops, k);
-  if (rc != PGM_OK) return rc;
-  if (k.n_out == 0) return PGM_OK;
-  BatchJob J;
-  memset(&J, 0, sizeof J);
-  J.kind = 4;
-  J.red = k.red;
-  J.C = C;
-  J._pad = (int32_t)h->njobs.size();
-  rc = batch_append(h, J, contract_n_threads(k), contract_n_cap(k));
-  if (rc != PGM_OK) return rc;
-  h->njobs.push_back(k);
-  h->nops.emplace_back(ops, ops + k.n_ops);
-  return PGM_OK;
-}
-
-int pgm_contract_n_info(const pgm_contractn_desc *d, const double *const *ops, pgm_contractn_info_t *info) {
-  if (!info) return fail(PGM_EINVAL, "contract_n_info: null pointer");
-  ContractNK k;
-  int rc = plan_contract_n(d, ops, k, false);
-  if (rc != PGM_OK) return rc;
-  memset(info, 0, sizeof *info);
-  info->nk = k.nk;
-  info->nr = k.nr;
-  info->g_log2 = k.g_log2;
-  info->n_out = k.n_out;
-  info->n_red = k.n_red;
-  for (int i = 0; i < k.nk; ++i) info->kcard[i] = k.kcard[i];
-  for (int i = 0; i < k.nr; ++i) info->rcard[i] = k.rcard[i];
-  info->blocks = k.n_out ? (uint32_t)batch_job_blocks(contract_n_threads(k), contract_n_cap(k)) : 0;
-  return PGM_OK;
-}
-
-int pgm_batch_add_indicator(void *handle, const uint8_t *codes, int64_t n_rows, int64_t card, double *out,
-                            int64_t s_state, int64_t s_row, int32_t *err_flag) {
-  STALE_PROBE();
-  BatchHandle *h = (BatchHandle *)handle;
-  if (!h || !codes || !out) return fail(PGM_EINVAL, "batch_add_indicator: null argument");
-  if (n_rows <= 0 || card <= 0) return PGM_OK;
-  BatchJob J;
-  memset(&J, 0, sizeof J);
-  J.kind = 3;
-  J.codes = codes;
-  J.C = out;
-  J.err = err_flag;
-  J.ind_rows = n_rows;
-  J.ind_card = card;
-  J.ind_s_state = s_state;
-  J.ind_s_row = s_row;
-  return batch_append(h, J, (uint64_t)(n_rows * card));
-}
-
-int pgm_batch_set_mode(void *handle, int32_t mode) {
-  STALE_PROBE();
-  BatchHandle *h = (BatchHandle *)handle;
-  if (!h) return fail(PGM_EINVAL, "batch_set_mode: null handle");
-  if (h->d_jobs || !h->jobs.empty()) return fail(PGM_EINVAL, "batch_set_mode: set before the first job");
-  if (mode != PGM_BATCH_GRID && mode != PGM_BATCH_ONE_WORKGROUP) return fail(PGM_EINVAL, "batch_set_mode: mode %d", mode);
-  h->mode = mode;
-  return PGM_OK;
-}
-
-int pgm_batch_blocks(void *handle, int64_t *blocks) {
-  BatchHandle *h = (BatchHandle *)handle;
-  if (!h || !blocks) return fail(PGM_EINVAL, "batch_blocks: null argument");
-  *blocks = (int64_t)h->block_job.size();
-  return PGM_OK;
-}
-
-int pgm_batch_add_level(void *handle) {
-  STALE_PROBE();
-  BatchHandle *h = (BatchHandle *)handle;
-  if (!h) return fail(PGM_EINVAL, "batch_add_level: null handle");
-  if (h->d_jobs) return fail(PGM_EINVAL, "batch_add_level: already finalized");
-  if (h->mode != PGM_BATCH_ONE_WORKGROUP) return fail(PGM_EINVAL, "batch_add_level: levels need PGM_BATCH_ONE_WORKGROUP");
-  if (h->block_job.size() > h->level_off.back()) h->level_off.push_back((uint32_t)h->block_job.size());
-  return PGM_OK;
-}
-
 static void batch_free(BatchHandle *h) {
   if (h->d_jobs) (void)hipFree(h->d_jobs);
   if (h->d_map) (void)hipFree(h->d_map);
@@ -2587,21 +1909,10 @@ int pgm_batch_finalize(void *handle) {
   BatchHandle *h = (BatchHandle *)handle;
   if (!h) return fail(PGM_EINVAL, "batch_finalize: null handle");
   if (h->d_jobs || h->jobs.empty()) return PGM_OK;
-  if (h->level_off.back() < h->block_job.size()) h->level_off.push_back((uint32_t)h->block_job.size());
-  h->spec = -1;
-  bool uni = true, prod = true, contract_only = true;
-  for (const BatchJob &J : h->jobs) {
-    uni = uni && J.kind == 0 && J.cmb == h->jobs[0].cmb && J.red == h->jobs[0].red;
-    prod = prod && J.kind == 2;
-    contract_only = contract_only && (J.kind == 0 || J.kind == 4);  // (kind 4: specialised kernel only)
-  }
-  if (uni) h->spec = h->jobs[0].cmb * 3 + h->jobs[0].red;
-  if (prod) h->spec = kBatchSpecProducts;
-  const size_t lds = h->jobs.size() * sizeof(ChainJob) + 4 * (h->block_job.size() + h->level_off.size());
-  if (h->mode == PGM_BATCH_ONE_WORKGROUP && !contract_only)
-    return fail(PGM_EINVAL, "batch_finalize: a single-workgroup batch takes contractions only");
-  if (h->mode == PGM_BATCH_ONE_WORKGROUP && lds > kChainLdsMax)
-    return fail(PGM_EINVAL, "batch_finalize: single-workgroup tables of %zu bytes exceed the LDS budget", lds);
+  std::vector<ChainJob> cj;
+  size_t lds = 0;
+  const int rc = batch_close(h, cj, lds);
+  if (rc != PGM_OK) return rc;
   hipError_t e = hipMalloc((void **)&h->d_jobs, sizeof(BatchJob) * h->jobs.size());
   if (e == hipSuccess) e = hipMalloc((void **)&h->d_map, sizeof(uint32_t) * h->block_job.size());
   if (e == hipSuccess)
@@ -2612,20 +1923,6 @@ int pgm_batch_finalize(void *handle) {
     e = hipMalloc((void **)&h->d_level, sizeof(uint32_t) * h->level_off.size());
     if (e == hipSuccess)
       e = hipMemcpy(h->d_level, h->level_off.data(), sizeof(uint32_t) * h->level_off.size(), hipMemcpyHostToDevice);
-    std::vector<ChainJob> cj(h->jobs.size());
-    for (size_t i = 0; i < h->jobs.size(); ++i) {
-      const BatchJob &J = h->jobs[i];
-      ChainJob &c = cj[i];
-      memset(&c, 0, sizeof c);
-      c.cmb = J.cmb;
-      c.red = J.red;
-      c.block0 = J.block0;
-      c.nblocks = J.nblocks;
-      c.A = J.A;
-      c.B = J.B;
-      c.C = J.C;
-      c.c = J.c;
-    }
     if (e == hipSuccess) e = hipMalloc((void **)&h->d_chain, sizeof(ChainJob) * cj.size());
     if (e == hipSuccess) e = hipMemcpy(h->d_chain, cj.data(), sizeof(ChainJob) * cj.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) h->chain_lds = lds;
@@ -2731,8 +2028,7 @@ int pgm_argmax(const double *X, int64_t n_rows, int64_t row_len, int64_t s_row, 
   if (n_rows <= 0) return PGM_OK;
   if (row_len <= 0) return fail(PGM_EINVAL, "argmax: empty rows (np.argmax of an empty sequence)");
   if (row_len >= (1ll << 31)) return fail(PGM_EINVAL, "argmax: row too long");
-  int g = 0;
-  while (g < 6 && ((uint64_t)n_rows << g) < kTargetThreads && (1ll << (g + 1)) <= row_len) ++g;
+  const int g = lanes_log2((uint64_t)n_rows, kTargetThreads, (uint64_t)row_len);
   uint64_t threads = (uint64_t)n_rows << g;
   uint64_t blocks = std::min<uint64_t>((threads + 255) / 256, 65535);
   hipLaunchKernelGGL(k_argmax, dim3((unsigned)blocks), dim3(256), 0, S(stream), X, (uint64_t)n_rows,
