@@ -1547,6 +1547,59 @@ int pgm_dbn_viterbi(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld
                     const double *values0, const double *values1, uint8_t *path, int64_t ld_out, int64_t row0_out,
                     double *logmap, uint8_t *impossible, void *scratch, int64_t scratch_bytes, void *stream);
 
+/* ---------------------------------------------------------------- dynamic Bayesian networks: expected counts
+ * pgm_dbn_estep: the E-step of Baum-Welch for every sequence of the batch, in one launch, on the plan, the
+ * data layout, the clamped / free split and the mapping of pgm_dbn_run (the queried flags are not used).
+ * Two more extension symbols of ABI 25; pgm_dbn_info_t and the other pgm_dbn_* calls are as they were.
+ *
+ * THE RECURSION, per sequence.  Forward: pgm_dbn_run's, a_t and c_t kept in the caller's scratch of n_rows
+ * (T + 1) (S + 1) doubles (the same rule and the same PGM_EINVAL for a scratch that is too small).  Backward,
+ * slice by slice, with gamma_t(x) = alpha_t(x) beta_t(I(x)) as pgm_dbn_run computes it and gs its sum:
+ *   t = 0, every slice-0 family f:       tables0[entry of f at x]       += gamma_0(x) / gs
+ *   t >= 1, f without a free slice-t parent: tables1[entry of f at x']  += gamma_t(x') / gs
+ *   t >= 1, f with a free slice-t parent:    tables1[entry of f at (i, x')] += xi_t(i, x') / gs
+ *   xi_t(i, x') = local(x') (a_t-1(i) prod(i, x')) / c_t beta_t(I(x')),   sum_i xi_t(i, x') = gamma_t(x').
+ * The entry of a family is the one pgm_dbn_run reads its factor from: tables0 / tables1 are device fp64
+ * buffers in the layout of values0 / values1, so pgm_fit_finish | PGM_FIT_WEIGHTED over the same family
+ * lists is the M-step.  The tables are ADDED TO, not overwritten, as pgm_fit_estep does.  Slice-0 tables get
+ * slice 0 only, the transition tables slices 1 .. T: the maximum-likelihood statistics of the unrolled
+ * network.  A term of xi is built by the operations of the matching term of gamma, in the same order (the
+ * message times the factors in node order, then local, / c_t, * beta) and weighted by a division by gs:
+ * where one (i, x') survives the evidence its weight is g / g = 1.0, and a fully observed batch gives
+ * exact integers.  An x' that contradicts its cell's evidence, or a term that is 0, is never added.
+ *
+ * ACCUMULATION.  PGM_DBN_ESTEP_TILE: an fp64 copy of both table sets lives in LDS behind the sequences'
+ * state (when lds_bytes rounded up to 8, + 8 (values0 + values1) <= 160 KiB); the adds are LDS atomics;
+ * workgroups take groups of seq_per_wave sequences in a grid-stride loop, the grid capped at max_blocks
+ * (256 CUs x the workgroups whose LDS fits a CU, 32 at most), and a workgroup adds the non-zero entries
+ * of its tile to the tables once, at its end, one global atomic each.  PGM_DBN_ESTEP_DIRECT (taken when
+ * the tile does not fit, or forced by the flag of that name): one workgroup per group, every add a global
+ * atomic.  The tables are sums of fp64 atomics in no fixed order: they are NOT bit-identical from run to
+ * run (a sum of n non-negative terms is within (n - 1) 2^-53 relative in any order).  loglik and
+ * impossible involve no atomics and are bit-identical to pgm_dbn_run's.
+ *
+ * loglik [n_rows] and impossible [n_rows] are optional (NULL) and as in pgm_dbn_run.  An impossible
+ * sequence (some c_t not > 0) adds nothing to any table.  Bad codes are treated as in pgm_dbn_run: they
+ * never index a table, the call returns PGM_EINVAL after the launch and the tables are then unspecified.
+ * Checked on the host before any HIP call (PGM_EINVAL): everything pgm_dbn_run checks for a smoother, null
+ * tables0 / tables1, a table pointer that is not 8-byte aligned, unknown flag bits.  n_rows = 0 is PGM_OK
+ * and launches nothing.  pgm_dbn_estep_info needs no device: the path a call with `flags` takes. */
+#define PGM_DBN_ESTEP_DIRECT 1u /* flags: every add a global atomic, whether or not the tile fits */
+#define PGM_DBN_ESTEP_TILE 0    /* pgm_dbn_estep_info_t.path */
+typedef struct {
+  int32_t path;          /* PGM_DBN_ESTEP_TILE, or PGM_DBN_ESTEP_DIRECT */
+  int32_t tile_fits;     /* whether the tile fits in LDS beside the sequences' state */
+  int32_t blocks_per_cu; /* tile path: workgroups whose LDS fits a CU (32 at most); direct: 0 */
+  int32_t reserved;
+  int64_t lds_bytes;     /* LDS of a workgroup on the path taken */
+  int64_t tile_bytes;    /* 8 (values0 + values1) */
+  int64_t max_blocks;    /* tile path: grid = min(groups of sequences, max_blocks); direct: 0, one workgroup per group */
+} pgm_dbn_estep_info_t;
+int pgm_dbn_estep_info(void *plan, uint32_t flags, pgm_dbn_estep_info_t *info);
+int pgm_dbn_estep(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, int32_t n_slices,
+                  const double *values0, const double *values1, double *tables0, double *tables1, double *loglik,
+                  uint8_t *impossible, double *scratch, int64_t scratch_bytes, uint32_t flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

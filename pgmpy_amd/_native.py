@@ -310,6 +310,17 @@ class DbnInfo(ctypes.Structure):
 
 DBN_MAX_CONFIGS, DBN_MAX_NODES, DBN_MAX_SLICES = 4096, 255, 65535  # PGM_DBN_MAX_CONFIGS and the plan's other limits
 
+
+class DbnEstepInfo(ctypes.Structure):
+    """pgm_dbn_estep_info_t: the accumulation path and launch geometry of pgm_dbn_estep (host-only query)."""
+    _fields_ = [("path", ctypes.c_int32), ("tile_fits", ctypes.c_int32), ("blocks_per_cu", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("lds_bytes", ctypes.c_int64), ("tile_bytes", ctypes.c_int64),
+                ("max_blocks", ctypes.c_int64)]
+
+
+DBN_ESTEP_TILE, DBN_ESTEP_DIRECT = 0, 1  # PGM_DBN_ESTEP_*: the path of an info; DIRECT is also the flag that forces it
+DBN_LDS_MAX = 163840  # the LDS a workgroup of the dynamic-network kernels may take
+
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
 RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
@@ -571,6 +582,9 @@ _SIGS = {
                      _P, _P, _P, ctypes.c_int64, _P], ctypes.c_int),
     "pgm_dbn_viterbi": ([_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, _P, _P, _P,
                          ctypes.c_int64, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P], ctypes.c_int),
+    "pgm_dbn_estep_info": ([_P, ctypes.c_uint32, ctypes.POINTER(DbnEstepInfo)], ctypes.c_int),
+    "pgm_dbn_estep": ([_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P,
+                       _P, _P, _P, ctypes.c_int64, ctypes.c_uint32, _P], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

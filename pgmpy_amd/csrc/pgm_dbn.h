@@ -1,8 +1,8 @@
 // pgm_dbn.h — private interface between the two units of the dynamic-network filter (include/pgmhip.h
 // "dynamic Bayesian networks"): pgmdbn_plan.cpp (host only: validation of the slice nodes and the two
-// family sets, the offset tables, the launch geometry, the argument checks of pgm_dbn_run and pgm_dbn_viterbi)
-// and pgmdbn.hip (k_dbn, k_dbn_viterbi, the device side of the handle, the launches).  Not part of
-// include/pgmhip.h.
+// family sets, the offset tables, the launch geometry, the argument checks of pgm_dbn_run, pgm_dbn_viterbi and
+// pgm_dbn_estep) and pgmdbn.hip (k_dbn, k_dbn_viterbi, k_dbn_estep, the device side of the handle, the
+// launches).  Not part of include/pgmhip.h.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -61,6 +61,24 @@ PGM_DBN_LOCAL int dbn_run_check(const DbnHandle *h, const uint8_t *codes, int32_
                                 int64_t n_rows, int32_t n_slices, const double *values0, const double *values1,
                                 const double *filter, const double *smooth, const double *loglik, const double *scratch,
                                 int64_t scratch_bytes, bool *launch);
+// k_dbn_estep's accumulation (include/pgmhip.h "expected counts"): the fp64 tile of both table sets lies in
+// LDS behind the sequences' state, at the next multiple of 8 bytes; the grid of the tile path is capped at
+// kDbnCus x the workgroups whose LDS fits a CU, so that a workgroup flushes its tile once
+static constexpr int kDbnCus = 256;            // the MI355X's; another count changes the cap, not the result
+static constexpr int kDbnWavesPerCu = 32;      // one-wave workgroups a CU holds
+struct DbnEstepGeom {
+  bool tile = false, fits = false;
+  int64_t tile_at = 0;      // doubles into LDS where the tile begins
+  int64_t tile_bytes = 0, lds_bytes = 0;
+  int32_t blocks_per_cu = 0;
+  int64_t max_blocks = 0;
+};
+PGM_DBN_LOCAL DbnEstepGeom dbn_estep_geom(const DbnPlan &p, uint32_t flags);
+// the checks of pgm_dbn_estep (no HIP call): dbn_run_check's for a smoother, the tables, the flags
+PGM_DBN_LOCAL int dbn_estep_check(const DbnHandle *h, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0,
+                                  int64_t n_rows, int32_t n_slices, const double *values0, const double *values1,
+                                  const double *tables0, const double *tables1, const double *loglik, const double *scratch,
+                                  int64_t scratch_bytes, uint32_t flags, bool *launch);
 // the checks of pgm_dbn_viterbi (no HIP call); the backpointers take dbn_viterbi_scratch(...) bytes
 static inline double dbn_viterbi_scratch(int64_t n_rows, int32_t n_slices, int32_t J) {
   return (double)n_rows * (n_slices - 1) * J * 2.0;

@@ -5,7 +5,10 @@
 // three added offsets: what the clamped codes give (cl, per sequence, slice and family), what the free
 // nodes of x' give (xoff) and what the interface state gives (ioff).  k_dbn_viterbi, further down, is the
 // max-product recursion on the same plan with backpointers and a backtrack: the most probable sequence.
+// k_dbn_estep, last, is the smoother with every term of gamma added to fp64 count tables: Baum-Welch's E-step.
 #include <math.h>
+
+#include <algorithm>
 
 #include "pgm_dbn.h"
 #include "pgm_hip_common.h"
@@ -446,6 +449,231 @@ __global__ __launch_bounds__(kDbnBlock) void k_dbn_viterbi(const DbnVitArgs va) 
   }
 }
 
+// ---------------------------------------------------------------------------------------------- expected counts
+// k_dbn_estep — the E-step of Baum-Welch (include/pgmhip.h "dynamic Bayesian networks: expected counts").  The
+// plan, the mapping and a sequence's LDS are k_dbn's; the forward pass is k_dbn's smoother's, statement by
+// statement (loglik and impossible are the same bits), and so are gamma and the beta update of the backward
+// pass.  What is new is between them: every term of gamma, and of the carried sum inside it, is added to the
+// entry of the count tables that the factor was read from.  tile: the fp64 copy of both table sets in LDS
+// (tables0, then tables1), or null: every add goes to global memory.
+struct DbnEstepArgs {
+  DbnArgs a;  // filter and smooth unused; scratch as for a smoother
+  double *tab0, *tab1;
+  int64_t groups;   // groups of spw sequences
+  int64_t tile_at;  // doubles into LDS where the tile begins; < 0: no tile
+  int32_t total0, total1;
+};
+
+namespace {
+
+// TILE is a template argument so that the tile's adds are LDS instructions, not flat ones
+template <bool TILE>
+struct Counts {
+  double *tile, *tab0, *tab1;
+  int32_t total0;
+  __device__ __forceinline__ void add(int set, int32_t at, double w) const {
+    if constexpr (TILE)
+      atomicAdd(&tile[(set ? total0 : 0) + at], w);
+    else
+      atomicAdd(&(set ? tab1 : tab0)[at], w);
+  }
+};
+
+// the adds of slice t >= 1 at x' for the families with a free slice-t parent: xi(i, x') / gs, a term of xi
+// built as the matching term of carried() and then as gamma is (local, / c, * beta)
+template <bool TILE>
+__device__ __forceinline__ void add_prev(const Seq &s, const Counts<TILE> &k, int x, double local, double c, double beta, double gs) {
+  const DbnLayout &L = s.a.L;
+  const int32_t *voff = s.a.tab + L.o_voff[1], *xoff = s.a.tab + L.o_xoff[1], *prev = s.a.tab + L.o_prev,
+                *ioff = s.a.tab + L.o_ioff;
+  if (L.n_prev > kDbnHoist) {
+    for (int i = 0; i < L.S; ++i) {
+      const double m = s.msg[i];
+      if (m == 0.0) continue;
+      const double xi = local * trans_factor(s, i, x, m) / c * beta;
+      if (xi == 0.0) continue;
+      const double w = xi / gs;
+      for (int l = 0; l < L.n_prev; ++l) {
+        const int f = prev[l];
+        k.add(1, voff[f] + s.cl[f] + xoff[f * L.J + x] + ioff[l * L.S + i], w);
+      }
+    }
+    return;
+  }
+  int32_t base[kDbnHoist];
+#pragma unroll
+  for (int l = 0; l < kDbnHoist; ++l) {
+    base[l] = 0;
+    if (l < L.n_prev) {
+      const int f = prev[l];
+      base[l] = voff[f] + s.cl[f] + xoff[f * L.J + x];
+    }
+  }
+  for (int i = 0; i < L.S; ++i) {
+    double p = s.msg[i];
+    if (p == 0.0) continue;
+#pragma unroll
+    for (int l = 0; l < kDbnHoist; ++l)
+      if (l < L.n_prev) p *= s.a.val1[base[l] + ioff[l * L.S + i]];
+    const double xi = local * p / c * beta;
+    if (xi == 0.0) continue;
+    const double w = xi / gs;
+#pragma unroll
+    for (int l = 0; l < kDbnHoist; ++l)
+      if (l < L.n_prev) k.add(1, base[l] + ioff[l * L.S + i], w);
+  }
+}
+
+}  // namespace
+
+template <bool TILE>
+__global__ __launch_bounds__(kDbnBlock) void k_dbn_estep(const DbnEstepArgs ea) {
+  extern __shared__ double lds[];
+  const DbnArgs &a = ea.a;
+  const DbnLayout &L = a.L;
+  const int lane = (int)threadIdx.x, P = L.P, J = L.J, S = L.S, n = L.n;
+  const int seg = lane / P;
+  const int32_t total = ea.total0 + ea.total1;
+  const Counts<TILE> k = {TILE ? lds + ea.tile_at : nullptr, ea.tab0, ea.tab1, ea.total0};
+  if constexpr (TILE) {
+    for (int32_t e = lane; e < total; e += kDbnBlock) k.tile[e] = 0.0;
+    __syncthreads();
+  }
+  int32_t *cl_all = reinterpret_cast<int32_t *>(lds + (size_t)L.spw * (J + 2 * S));
+  uint8_t *ev_all = reinterpret_cast<uint8_t *>(cl_all + (size_t)L.spw * n);
+  const int32_t *ix = a.tab + L.o_ix, *xperm = a.tab + L.o_xperm;
+  const int T1 = a.T1;
+
+  for (int64_t grp = blockIdx.x; grp < ea.groups; grp += gridDim.x) {
+    const int64_t seq = grp * L.spw + seg;
+    // a lane without a sequence computes on the first one's data and stores nothing
+    const bool live = seg < L.spw && seq < a.B;
+    const int sg = live ? seg : 0;
+    const Seq s = {a,
+                   lds + (size_t)sg * J,
+                   lds + (size_t)L.spw * J + (size_t)sg * S,
+                   lds + (size_t)L.spw * (J + S) + (size_t)sg * S,
+                   cl_all + (size_t)sg * n,
+                   ev_all + (size_t)sg * 2 * n,
+                   live ? seq : grp * L.spw,
+                   a.row0 + (live ? seq : grp * L.spw),
+                   lane % P,
+                   live};
+    const int xl = s.xl;
+    double *scr = a.scratch + s.seq * T1 * (S + 1);
+
+    // ---------------------------------------------------------------- forward (k_dbn's, with scratch)
+    double ll = 0.0;
+    bool dead = false;
+    for (int t = 0; t < T1; ++t) {
+      load_ev(s, t);
+      __syncthreads();
+      compute_cl(s, t ? 1 : 0);
+      if (t)
+        for (int i = xl; i < S; i += P) {
+          double m = 0.0;
+          for (int r = 0; r < L.R; ++r) m += s.A[xperm[i * L.R + r]];
+          if (live) {
+            s.msg[i] = m;
+            scr[(t - 1) * (S + 1) + i] = m;
+          }
+        }
+      __syncthreads();
+      double part = 0.0;
+      for (int x = xl; x < J; x += P) {
+        double v = 0.0;
+        if (consistent(s, x)) {
+          v = local_factor(s, x, t == 0);
+          if (t) v *= carried(s, x);
+        }
+        if (live) s.A[x] = v;
+        part += v;
+      }
+      const double c = seg_sum(part, P);
+      if (live)
+        for (int x = xl; x < J; x += P) s.A[x] /= c;
+      if (!(c > 0.0)) dead = true;
+      ll += log(c);
+      if (live && xl == 0) scr[t * (S + 1) + S] = c;
+      __syncthreads();
+    }
+    if (live && xl == 0) {
+      if (a.loglik) a.loglik[seq] = dead ? -INFINITY : ll;
+      if (a.impossible) a.impossible[seq] = dead ? 1 : 0;
+    }
+
+    // ---------------------------------------------------------------- backward
+    const bool counted = live && !dead;  // an impossible sequence adds nothing
+    if (live)
+      for (int i = xl; i < S; i += P) s.beta[i] = 1.0;
+    for (int t = T1 - 1; t >= 0; --t) {
+      load_ev(s, t);
+      if (t && live)
+        for (int i = xl; i < S; i += P) s.msg[i] = scr[(t - 1) * (S + 1) + i];
+      const double c = scr[t * (S + 1) + S];
+      __syncthreads();
+      compute_cl(s, t ? 1 : 0);
+      __syncthreads();
+      // gamma_t, as k_dbn builds it
+      double part = 0.0;
+      for (int x = xl; x < J; x += P) {
+        double g = 0.0;
+        if (consistent(s, x)) {
+          g = local_factor(s, x, t == 0);
+          if (t) g *= carried(s, x);
+          g = g / c * s.beta[ix[x]];
+        }
+        if (live) s.A[x] = g;
+        part += g;
+      }
+      const double gs = seg_sum(part, P);
+      // the adds: a lane's own x; g = 0 is an x that contradicts the evidence, or has no mass (then every term
+      // of its carried sum is 0 too: the terms are not negative)
+      if (counted)
+        for (int x = xl; x < J; x += P) {
+          const double g = s.A[x];
+          if (g == 0.0) continue;
+          const double w = g / gs;
+          if (!t) {
+            const int32_t *voff = a.tab + L.o_voff[0], *xoff = a.tab + L.o_xoff[0];
+            for (int f = 0; f < n; ++f) k.add(0, voff[f] + s.cl[f] + xoff[f * J + x], w);
+          } else {
+            const int32_t *voff = a.tab + L.o_voff[1], *xoff = a.tab + L.o_xoff[1], *cur = a.tab + L.o_cur;
+            for (int l = 0; l < L.n_cur; ++l) {
+              const int f = cur[l];
+              k.add(1, voff[f] + s.cl[f] + xoff[f * J + x], w);
+            }
+            if (L.n_prev) add_prev(s, k, x, local_factor(s, x, false), c, s.beta[ix[x]], gs);
+          }
+        }
+      if (!t) break;
+      // beta_t-1, as k_dbn builds it (a lane rewrites the A[x] it has just read: no barrier between)
+      for (int x = xl; x < J; x += P) {
+        const double w = consistent(s, x) ? local_factor(s, x, false) * s.beta[ix[x]] / c : 0.0;
+        if (live) s.A[x] = w;
+      }
+      __syncthreads();
+      for (int i = xl; i < S; i += P) {
+        double b = 0.0;
+        for (int x = 0; x < J; ++x) {
+          const double w = s.A[x];
+          if (w != 0.0) b += trans_factor(s, i, x, w);
+        }
+        if (live) s.beta[i] = b;
+      }
+      __syncthreads();
+    }
+    __syncthreads();  // the next group's codes go where this one's adds have read
+  }
+  if constexpr (TILE) {
+    __syncthreads();
+    for (int32_t e = lane; e < total; e += kDbnBlock) {
+      const double v = k.tile[e];
+      if (v != 0.0) atomicAdd(e < ea.total0 ? &ea.tab0[e] : &ea.tab1[e - ea.total0], v);
+    }
+  }
+}
+
 extern "C" {
 
 int pgm_dbn_plan_destroy(void *plan) { return pgm_plan_destroy<DbnHandle>(plan); }
@@ -510,6 +738,42 @@ int pgm_dbn_viterbi(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld
   if (rd != PGM_OK) return rd;
   if (bad)
     return pgmi_fail(PGM_EINVAL, "dbn_viterbi: a clamped cell is missing, or a code is >= its node's cardinality");
+  return PGM_OK;
+}
+
+int pgm_dbn_estep(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows, int32_t n_slices,
+                  const double *values0, const double *values1, double *tables0, double *tables1, double *loglik,
+                  uint8_t *impossible, double *scratch, int64_t scratch_bytes, uint32_t flags, void *stream) {
+  DbnHandle *h = static_cast<DbnHandle *>(plan);
+  bool launch = false;
+  const int st = dbn_estep_check(h, codes, n_cols, ld, row0, n_rows, n_slices, values0, values1, tables0, tables1, loglik, scratch,
+                                 scratch_bytes, flags, &launch);
+  if (st != PGM_OK || !launch) return st;
+  const DbnPlan &p = h->p;
+  const DbnEstepGeom g = dbn_estep_geom(p, flags);
+  const pgmdev::Slot base[] = {pgmdev::upload(h->d_tab, p.tab)};
+  int up = h->dev.use(kHipDevOps, base);
+  if (up == PGM_OK) up = flag_reset(h->dev, stream);
+  if (up != PGM_OK) return up;
+  // the attribute is a kernel's own, and this one's LDS is the plan's plus the tile
+  void (*const kernel)(DbnEstepArgs) = g.tile ? k_dbn_estep<true> : k_dbn_estep<false>;
+  if (g.lds_bytes > 65536)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)g.lds_bytes));
+  DbnEstepArgs ea = {};
+  DbnArgs &a = ea.a;
+  a.L = p.L, a.tab = h->d_tab, a.codes = codes, a.ld = ld, a.row0 = row0, a.B = n_rows, a.T1 = n_slices;
+  a.val0 = values0, a.val1 = values1, a.loglik = loglik, a.scratch = scratch, a.impossible = impossible, a.err = h->dev.flag();
+  ea.tab0 = tables0, ea.tab1 = tables1, ea.total0 = (int32_t)p.total[0], ea.total1 = (int32_t)p.total[1];
+  ea.groups = (n_rows + p.L.spw - 1) / p.L.spw;
+  ea.tile_at = g.tile ? g.tile_at : -1;
+  const int64_t blocks = g.tile ? std::min(ea.groups, g.max_blocks) : ea.groups;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kDbnBlock), (size_t)g.lds_bytes, S(stream), ea);
+  int32_t bad = 0;
+  const int rd = flag_read(h->dev, stream, &bad);
+  if (rd != PGM_OK) return rd;
+  if (bad)
+    return pgmi_fail(PGM_EINVAL, "dbn_estep: a clamped cell is missing, or a code is >= its node's cardinality");
   return PGM_OK;
 }
 }

@@ -89,6 +89,57 @@ class DbnPlan(Plan):
                                   N.stream_handle()), "dbn_run")
         return filt, smooth, loglik, impossible
 
+    def estep_info(self, direct=False):
+        """pgm_dbn_estep_info_t of an E-step over this plan: the accumulation path (N.DBN_ESTEP_TILE or
+        N.DBN_ESTEP_DIRECT), the LDS bytes of a workgroup and the cap of the grid.  Needs no device."""
+        L = N.load_library()
+        info = N.DbnEstepInfo()
+        N.check(L.pgm_dbn_estep_info(self._h, N.DBN_ESTEP_DIRECT if direct else 0, ctypes.byref(info)), "dbn_estep_info")
+        return info
+
+    def estep(self, codes, values0, values1, tables0=None, tables1=None, n_rows=None, row0=0, want_loglik=True,
+              scratch_bytes=SCRATCH_BYTES, direct=False):
+        """The E-step of Baum-Welch (pgm_dbn_estep) over the rows [row0, row0 + n_rows) of the device codes
+        [(T + 1) n, ld] (uint8): every sequence adds its expected family counts under the CPD values to the
+        fp64 device tables (zeroed flat buffers when None) in the layout of values0 / values1: slice 0 to
+        tables0, slices 1 .. T to tables1.  Returns (tables0, tables1, loglik, impossible): loglik fp64
+        [n_rows] (None when not asked for), impossible uint8 [n_rows]; an impossible sequence adds nothing.
+        A batch whose scratch would pass `scratch_bytes` runs in several launches over row windows.  `direct`
+        forces every add to be a global atomic.  Raises ValueError when a clamped cell is missing or a code
+        is no state; the tables are then unspecified."""
+        import torch
+
+        L = N.lib()
+        n_cols, ld, n_rows = codes_window(codes, n_rows, row0)
+        if n_cols % self.n:
+            raise ValueError(f"codes have {n_cols} columns, not a multiple of the {self.n} slice nodes")
+        n_slices = n_cols // self.n
+        flat_tensor("values0", values0, int(self.info.values0))
+        flat_tensor("values1", values1, int(self.info.values1))
+        dev = codes.device
+        tables = []
+        for name, t, size in (("tables0", tables0, int(self.info.values0)), ("tables1", tables1, int(self.info.values1))):
+            if t is None:
+                t = torch.zeros(size, dtype=torch.float64, device=dev)
+            else:
+                flat_tensor(name, t, size)
+            tables.append(t)
+        rows = max(n_rows, 0)
+        loglik = torch.empty(rows, dtype=torch.float64, device=dev) if want_loglik else None
+        impossible = torch.empty(rows, dtype=torch.uint8, device=dev)
+        chunk = max(1, min(rows, int(scratch_bytes) // max(self.scratch_bytes(1, n_slices), 1))) if rows else 0
+        scratch = torch.empty(max(self.scratch_bytes(chunk, n_slices) // 8, 1), dtype=torch.float64, device=dev)
+        flags = N.DBN_ESTEP_DIRECT if direct else 0
+        # an empty (or negative) window still goes to the library once: it checks the arguments
+        for r0 in range(0, rows, chunk) if rows else [0]:
+            nr = min(chunk, rows - r0) if rows else n_rows
+            N.check(L.pgm_dbn_estep(self._h, N.ptr(codes), n_cols, ld, int(row0) + r0, nr, n_slices, N.ptr(values0),
+                                    N.ptr(values1), N.ptr(tables[0]), N.ptr(tables[1]),
+                                    None if loglik is None else ctypes.c_void_p(loglik.data_ptr() + r0 * 8),
+                                    ctypes.c_void_p(impossible.data_ptr() + r0), N.ptr(scratch), scratch.numel() * 8, flags,
+                                    N.stream_handle()), "dbn_estep")
+        return tables[0], tables[1], loglik, impossible
+
     def viterbi_scratch_bytes(self, n_rows, n_slices):
         """Bytes of backpointers one launch of `viterbi` takes: a uint16 per state of every slice but the first."""
         return int(n_rows) * max(int(n_slices) - 1, 0) * int(self.info.n_configs) * 2

@@ -19,6 +19,8 @@ Three levels:
     and device tensors back.
 The most probable sequence (Viterbi, csrc/pgmdbn.hip k_dbn_viterbi) has the same three levels: ``map_query``,
 ``viterbi_batch``, ``viterbi_codes``; it maximises over every unobserved cell jointly.
+``expected_counts_codes`` (csrc/pgmdbn.hip k_dbn_estep) adds every sequence's expected family counts to fp64
+tables on the device: the E-step that ``DynamicBayesianNetwork.fit(estimator="EM")`` iterates on.
 There is no CPU path: without a device a compute call raises ``NativeUnavailable``.
 """
 import numpy as np
@@ -185,6 +187,19 @@ class DBNInference:
         plan = self.plan(observed, [])
         values0, values1 = self._tables()
         return plan.viterbi(codes, values0, values1, scratch_bytes=scratch_bytes)
+
+    @E.serialized
+    def expected_counts_codes(self, codes, observed=(), values=None, tables=None, scratch_bytes=SCRATCH_BYTES, direct=False):
+        """(tables0, tables1, loglik [B], impossible [B]) on the device: the expected family counts of every
+        sequence under the model's CPDs (the E-step of Baum-Welch, csrc/pgmdbn.hip k_dbn_estep), flat fp64
+        buffers in the layout of the CPD values: the slice-0 families of ``families0`` end to end, fed by
+        slice 0 alone, and the transition families of ``families1``, fed by slices 1 .. T.  An impossible
+        sequence adds nothing.  `values` (values0, values1) replaces the model's CPD values, `tables`
+        (tables0, tables1) are added to instead of new zeroed ones: what ``fit(estimator="EM")`` iterates on."""
+        plan = self.plan(observed, [])
+        values0, values1 = self._tables() if values is None else values
+        tables0, tables1 = (None, None) if tables is None else tables
+        return plan.estep(codes, values0, values1, tables0, tables1, scratch_bytes=scratch_bytes, direct=direct)
 
     # ------------------------------------------------------------------ frames
     def encode(self, data):

@@ -7,6 +7,9 @@ What computes runs on the device through the static network:
 * ``fit`` takes the constant network (``get_constant_bn``, a DiscreteBayesianNetwork) and calls its
   ``fit`` on slices (0, 1) and ``fit_update`` on every later pair, so the counts run in the family-count
   kernel.  As in the reference the result is an average of normalised CPDs, not pooled counts.
+* ``fit(estimator="EM")`` / ``fit_codes`` learn from incomplete sequences (Baum-Welch): an iteration is one
+  launch of the E-step kernel over the whole batch (csrc/pgmdbn.hip k_dbn_estep, through
+  ``DBNInference.expected_counts_codes``'s plan) and one ``pgm_fit_finish`` per slice set.
 * ``simulate`` / ``simulate_codes`` unroll the network over the slices asked for and call the device
   sampler once.  ``simulate_codes`` returns the resident uint8 code matrix in the layout
   ``DBNInference.smooth_codes`` reads: column ``t * n + v`` is node ``v`` (sorted name order) of slice t.
@@ -19,6 +22,7 @@ from itertools import combinations
 import networkx as nx
 import numpy as np
 
+from .. import engine as E
 from ..factors.discrete import TabularCPD
 
 
@@ -356,16 +360,36 @@ class DynamicBayesianNetwork(nx.DiGraph):
         return bn, columns
 
     # ------------------------------------------------------------------ learning and simulation
-    def fit(self, data, estimator="MLE"):
-        """Learn the CPDs of both slices from a frame with ``(name, time_slice)`` columns."""
+    def fit(self, data, estimator="MLE", max_iter=100, atol=1e-8, init_cpds=None, seed=None):
+        """Learn the CPDs of both slices from a frame with ``(name, time_slice)`` columns.
+
+        estimator="MLE" needs every cell observed: the two-slice network is fitted window by window.
+
+        estimator="EM" (Baum-Welch; max_iter, atol, init_cpds and seed are its alone) takes incomplete
+        sequences: a NaN cell is unobserved, a node whose columns are absent or all NaN is hidden.
+        Cardinalities, state names and the starting values come from the CPDs the model carries for both
+        slices; init_cpds="random" / "uniform" replaces the starting values of the nodes that are hidden or
+        have a hidden parent by TabularCPD.get_random(seed=seed) / get_uniform.  One iteration is one launch of
+        the E-step kernel and one pgm_fit_finish per slice set, the values staying on the device, until every
+        entry satisfies |old - new| <= atol + 1e-5 |new| or max_iter is reached.  The slice-0 CPDs are fitted
+        to slice 0 alone and the transition CPDs to slices 1 .. T: the maximum-likelihood estimate of the
+        unrolled network (the "MLE" path pools every window's first slice into the slice-0 CPDs instead).
+        Sets ``n_iter_`` and ``log_likelihoods_`` (per iteration, the log-likelihood of the sequences that
+        are possible under the parameters the iteration started from)."""
         import pandas as pd
 
         if not isinstance(data, pd.DataFrame):
             raise ValueError(f"data must be a pandas dataframe. Got: {type(data)}")
         if min(t for _, t in data.columns) != 0:
             raise ValueError("data column names must start from time slice 0.")
+        if estimator in {"EM", "em"}:
+            inf = self._em_start(max_iter, atol, init_cpds)
+            codes, observed = inf.encode(data)
+            seen = (codes != 255).reshape(-1, len(inf.names), codes.shape[1]).any(axis=(0, 2))
+            hidden = [name for name, s in zip(inf.names, seen) if not s]
+            return self._fit_em(inf, E.to_device_raw(codes), observed, hidden, max_iter, atol, init_cpds, seed)
         if estimator not in {"MLE", "mle"}:
-            raise ValueError("Only Maximum Likelihood Estimator is supported currently")
+            raise ValueError("Only Maximum Likelihood Estimator (\"MLE\") and expectation maximisation (\"EM\") are supported currently")
         n_samples = data.shape[0]
         last = max(t for _, t in data.columns)
         const_bn = self._static(cpds=False)
@@ -379,6 +403,93 @@ class DynamicBayesianNetwork(nx.DiGraph):
                 const_bn.fit_update(window, n_prev_samples=t * n_samples)
         back = {_flat(v): v for v in self._graph_nodes()}
         self.add_cpds(*[_renamed(cpd, [back[v] for v in cpd.variables]) for cpd in const_bn.cpds])
+
+    def fit_codes(self, codes, n_time_slices, observed=(), max_iter=100, atol=1e-8, init_cpds=None, seed=None):
+        """``fit(estimator="EM")`` on a resident uint8 code matrix ``[n_time_slices * n, B]`` in the layout of
+        ``simulate_codes`` (255: not observed): nothing leaves the device but one scalar per iteration and, at
+        the end, the CPD values.  `observed`: the names observed in every cell of the batch (a 255 in one of
+        their cells raises ValueError); with init_cpds="random" / "uniform" every other node counts as hidden."""
+        inf = self._em_start(max_iter, atol, init_cpds)
+        n = len(inf.names)
+        if codes.dim() != 2 or int(codes.shape[0]) != int(n_time_slices) * n:
+            raise ValueError(f"codes must be [n_time_slices * n, B] = [{int(n_time_slices)} * {n}, B]. Got {tuple(codes.shape)}")
+        observed = set(observed)
+        hidden = [name for name in inf.names if name not in observed]
+        return self._fit_em(inf, codes, observed, hidden, max_iter, atol, init_cpds, seed)
+
+    def _em_start(self, max_iter, atol, init_cpds):
+        """The checks of the EM path that need no data, and the DBNInference of the model (which names a
+        node without a CPD in either slice)."""
+        import numbers
+
+        from ..inference.dbn_inference import DBNInference
+
+        if not isinstance(max_iter, numbers.Integral) or max_iter < 1:
+            raise ValueError(f"max_iter must be a positive integer. Got: {max_iter}")
+        if not (isinstance(atol, numbers.Real) and atol >= 0):
+            raise ValueError(f"atol must be a non-negative number. Got: {atol}")
+        if init_cpds is not None and not (isinstance(init_cpds, str) and init_cpds in ("random", "uniform")):
+            raise ValueError(f"init_cpds must be None (start from the model's CPDs), 'random' or 'uniform'. Got: {init_cpds!r}")
+        return DBNInference(self)
+
+    @E.serialized
+    def _fit_em(self, inf, codes, observed, hidden, max_iter, atol, init_cpds, seed):
+        import torch
+
+        from ..estimators._fit import FitPlan
+        from ..inference._dbn import flat_values
+        from ..inference.batch import download
+
+        n = len(inf.names)
+        cpds = [list(inf.cpds0), list(inf.cpds1)]
+        if init_cpds is not None:
+            make = TabularCPD.get_random if init_cpds == "random" else TabularCPD.get_uniform
+            hidden = set(hidden)
+            for group in cpds:
+                for j, cpd in enumerate(group):
+                    scope = list(cpd.variables)
+                    if any(name in hidden for name, _ in scope):
+                        group[j] = make(variable=scope[0], evidence=scope[1:],
+                                        cardinality={v: int(k) for v, k in zip(scope, cpd.cardinality)},
+                                        state_names={v: cpd.state_names[v] for v in scope}, seed=seed)
+        plan = inf.plan(observed, [])
+        # a fit plan over the same family lists has the layout of the values: its finish is the M-step
+        fits = [FitPlan(inf.families0), FitPlan(inf.families1)]
+        assert fits[0].offsets == plan.offsets0 and fits[1].offsets == plan.offsets1
+        values = [E.to_device(flat_values(group)) for group in cpds]
+        new = [torch.empty_like(v) for v in values]
+        tables = [torch.empty_like(v) for v in values]
+        one_slice = int(codes.shape[0]) == n  # no transition is in the data: the transition CPDs stay
+        ll = torch.zeros(int(max_iter), dtype=torch.float64, device=values[0].device)
+        self.n_iter_ = 0
+        for it in range(int(max_iter)):
+            for t in tables:
+                t.zero_()
+            _, _, loglik, flags = plan.estep(codes, values[0], values[1], tables[0], tables[1])
+            fits[0].finish(tables[0], out=new[0])
+            if one_slice:
+                new[1].copy_(values[1])
+            else:
+                fits[1].finish(tables[1], out=new[1])
+            ll[it] = torch.where(flags != 0, torch.zeros_like(loglik), loglik).sum()
+            # np.allclose(old, new, atol=atol) over both sets: a NaN never converges
+            close = torch.stack([((v - w).abs() <= atol + 1e-5 * w.abs()).all() for v, w in zip(values, new)]).all()
+            values, new = new, values
+            self.n_iter_ = it + 1
+            if int(download(close.to(torch.uint8).reshape(1))[0]):
+                break
+        self.log_likelihoods_ = [float(x) for x in download(ll)[:self.n_iter_]]
+        fitted = []
+        for k, group in enumerate(cpds):
+            host = download(values[k])
+            for f, cpd in enumerate(group):
+                card = [int(c) for c in cpd.cardinality]
+                table = host[fits[k].offsets[f]:fits[k].offsets[f] + fits[k].sizes[f]].reshape(card[0], -1)
+                fitted.append(TabularCPD(cpd.variable, card[0], table, evidence=list(cpd.variables[1:]) or None,
+                                         evidence_card=card[1:] or None,
+                                         state_names={v: cpd.state_names[v] for v in cpd.variables}))
+        done = {c.variable for c in fitted}
+        self.cpds = [c for c in self.cpds if c.variable not in done] + fitted
 
     def _back(self, n_time_slices):
         return {_flat((name, t)): (name, t) for t in range(n_time_slices) for name in self._nodes()}
