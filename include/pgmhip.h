@@ -1421,6 +1421,105 @@ int pgm_lgs_score(void *handle, const double *G, const double *shift, int32_t d,
 /* *out = I_{1 - y}(a, 1/2) by the host build of the device's function (csrc/pgm_ibeta.h) */
 int pgm_lgs_ibeta_half(double a, double y, double *out);
 
+/* ---------------------------------------------------------------- conditional-Gaussian scores
+ * The structure scores of a frame with discrete AND continuous columns (estimators/StructureScore.py
+ * LogLikelihoodCondGauss, BICCondGauss, AICCondGauss; Andrews, Ramsey & Cooper 2018) from GROUPED MOMENTS:
+ * per configuration of a family's discrete columns the row count, the column sums of its continuous columns
+ * and their cross products.  The data is the resident uint8 code matrix codes[n_code_cols, ld_codes] of the
+ * parameter-learning calls and the resident fp64 value matrix X[n_value_cols, ld_x] of the linear-Gaussian
+ * calls, both column-major; a call reads the rows [row0, row0 + n_rows) of both.  An extension of ABI 25.
+ *
+ * A FAMILY (pgm_cg_family) names n_disc code columns with their cardinalities, the variable FIRST when it is
+ * discrete (var_discrete = 1), and n_cont value columns, the variable LAST when it is continuous.  C is the
+ * continuous parents, D the discrete parents.  Refused (PGM_EINVAL) before any HIP call: more than
+ * PGM_CG_MAX_CONT value columns, more than PGM_MAX_DIMS code columns, a cardinality outside 1 .. 255, a
+ * column named twice, a family without its variable, more than PGM_CG_MAX_ROWS operand rows (below).
+ *
+ * pgm_cg_moments.  With m = n_cont, mp = the smallest of 1, 2, 4, 8 that is >= m + 1 and Q = the product of
+ * the cardinalities, the padded row of a data row is [1, x_1 - c_1, .., x_m - c_m, 0 ..] (mp entries; c =
+ * shift[value column], the column means of pgm_lg_colsum: the cancellation control of pgm_lg_gram).  The
+ * configuration of a row is sum_d code_d stride_d, the first code column slowest.  The kernel is a product on
+ * v_mfma_f64_16x16x4_f64 with a one-hot-masked operand: operand row a of the A side stands for
+ * (configuration a / mp, padded column a % mp) and holds the row's entry where the row's configuration is
+ * a / mp, +0.0 elsewhere; the B side's 16 columns are the mp padded columns, zero after.  Q mp <=
+ * PGM_CG_MAX_ROWS operand rows, cut into tiles of 16: accumulator tile t holds for its 16 / mp configurations
+ * every [1, x]' [1, x] moment.  A wave owns (family, a block of up to PGM_CG_TILES_PER_WAVE tiles, one row
+ * slice): a lane loads its column's four consecutive rows once per step (a wave reads 128 contiguous bytes
+ * per column, two 16-byte loads per lane when X, ld_x and row0 allow, pgm_cg_moments_info tells) and reuses
+ * them for every tile, comparing the row's configuration with the tile's.  A row with PGM_EV_MISSING in a
+ * code column or NaN in a value column of the family matches no configuration and its B entries are zero
+ * too (0 x NaN reaches no accumulator); a code that is neither missing nor a state skips the row, and the
+ * call returns PGM_EINDEX after the moments are written.  A value of +-inf is not a missing cell: it makes
+ * the family's moments NaN.  Slice partials go to a stage of the plan, a second kernel adds a tile's slices
+ * in index order.  The slice length depends on n_rows alone (n_rows / PGM_CG_MAX_SLICES, at least
+ * PGM_CG_SLICE_MIN, a multiple of 16) or is the forced one (pgm_cg_plan_set_slice, raised to fit
+ * PGM_CG_MAX_SLICES); when the stage cannot hold every block's partials the blocks go in several passes.
+ * No floating-point atomics: a family's moments are bit-identical from run to run and whatever else the
+ * plan holds.  moments (device, info.moments_size doubles): family f's block starts at layout mom_off and is
+ * [Q][mp][mp] in C order, entry (q, i, j) the sum over the rows of configuration q of padded column i
+ * times padded column j.  n_rows == 0 writes zeros.
+ *
+ * pgm_cg_score.  L(g; cols), k = |cols|, n_g rows: 0 when k = 0 or n_g = 0; the identity-covariance value
+ * -n_g/2 k log 2pi - 1/2 sum_i scatter_ii when n_g = 1 or n_g < k; else -n_g/2 (r log 2pi + log det S_kept)
+ * - (n_g - 1) r / 2 with scatter the centred cross products G_ij - s_i s_j / n_g, S = scatter / (n_g - 1),
+ * factorised on its unit-diagonal scaling by the Cholesky of pgm_lgs_score (no pivoting, a pivot at or
+ * below 1e-11 drops its column), r the columns kept.  A column whose scatter_ii is at or below 4 u (n_g + 2)
+ * G_ii (u = 2^-53: the rounding G_ii - s_i^2 / n_g can carry) is constant in the group: its scatter_ii counts as
+ * 0 and it is dropped; a column whose group mean lies more than ~1 / sqrt(4 u n_g) standard deviations from
+ * the shift is taken for one.  One job per (family, configuration h of D):
+ *   continuous variable: L(h; C + [v]) - L(h; C), both from one factorisation (the leading pivots are C's),
+ *     the fallback and the drop rule applied to each on its own;
+ *   discrete variable: sum over v's states s, in order, of [L((s, h); C) + n_sh log(n_sh / n_h)] - L(h; C),
+ *     the moments of h being the sum of those of (s, h) in state order.  Summed over h this is the
+ *     definition's sum_g [L + n_g log(n_g / n)] - sum_h [L + n_h log(n_h / n)]: the log n terms cancel.
+ * A family's job terms are added per chunk of PGM_CG_SCORE_CHUNK jobs in a fixed tree and the chunks in index
+ * order by a second kernel.  Outputs (device, one entry per family): ll; n_complete, the rows counted;
+ * n_observed, the configurations of D with a row; n_dropped, the columns dropped over every factorisation
+ * that ran (a continuous variable: the joint one, or C's when the joint took the fallback; a discrete
+ * variable: every (s, h) and every h).  shift is not read (the scatter does not depend on it) and may be
+ * NULL.  pgm_cg_plan_create, _info, _set_slice and pgm_cg_moments_info need no device.  The handle follows
+ * the rules of the plan handles. */
+#define PGM_CG_MAX_CONT 7
+#define PGM_CG_MAX_ROWS 4096
+#define PGM_CG_TILES_PER_WAVE 16
+#define PGM_CG_MAX_SLICES 256
+#define PGM_CG_SLICE_MIN 1024
+#define PGM_CG_STAGE_TILES 65536 /* (tile, slice) partials the stage holds at most: 128 MiB */
+#define PGM_CG_SCORE_CHUNK 128   /* jobs per workgroup of the score kernel */
+typedef struct {
+  int32_t n_disc, n_cont, var_discrete, reserved;
+  int32_t dcol[PGM_MAX_DIMS]; /* code columns, the variable first when discrete */
+  int32_t card[PGM_MAX_DIMS]; /* 1 .. 255 */
+  int32_t ccol[PGM_CG_MAX_CONT + 1]; /* value columns, the variable last when continuous */
+} pgm_cg_family;
+typedef struct {
+  int32_t n_families;
+  int32_t n_code_cols;  /* 1 + the largest code column named */
+  int32_t n_value_cols; /* 1 + the largest value column named */
+  int32_t reserved;
+  int64_t total_tiles;
+  int64_t total_blocks; /* waves per slice of a moments launch */
+  int64_t total_jobs;
+  int64_t total_chunks; /* workgroups of a score launch */
+  int64_t moments_size; /* doubles */
+  int64_t stage_tiles;  /* (tile, slice) partials of the plan's stage */
+  int64_t slice_rows;   /* 0: chosen per call; else forced */
+} pgm_cg_info_t;
+#define PGM_CG_LAYOUT 6 /* int64 per family of pgm_cg_plan_info's layout: mp, Q, operand rows, tiles, mom_off, jobs */
+int pgm_cg_plan_create(const pgm_cg_family *families, int32_t n_families, void **plan);
+int pgm_cg_plan_destroy(void *plan);
+/* layout: PGM_CG_LAYOUT * n_families entries; either output may be NULL */
+int pgm_cg_plan_info(void *plan, pgm_cg_info_t *info, int64_t *layout);
+int pgm_cg_plan_set_slice(void *plan, int64_t slice_rows);
+/* rows per slice, slices, passes over the stage and whether the 16-byte loads apply for such a window */
+int pgm_cg_moments_info(void *plan, const void *X, int64_t ld_x, int64_t row0, int64_t n_rows, int64_t *slice_rows,
+                        int64_t *n_slices, int64_t *n_passes, int32_t *vec16);
+int pgm_cg_moments(void *plan, const uint8_t *codes, int32_t n_code_cols, int64_t ld_codes, const double *X,
+                   int32_t n_value_cols, int64_t ld_x, int64_t row0, int64_t n_rows, const double *shift, double *moments,
+                   void *stream);
+int pgm_cg_score(void *plan, const double *moments, const double *shift, double *ll, int64_t *n_complete,
+                 int64_t *n_observed, int64_t *n_dropped, void *stream);
+
 /* ---------------------------------------------------------------- dynamic Bayesian networks
  * Filtering, smoothing and the log-likelihood of MANY evidence sequences under one two-slice network
  * (DynamicBayesianNetwork / DBNInference, which rebuilds and calibrates a junction tree per slice of one

@@ -299,6 +299,27 @@ LGS_MAX_COND, LGS_LANE_MAX, LGS_MAX_TARGETS = 64, 7, 3
 LGS_LL, LGS_BIC, LGS_AIC = 0, 1, 2
 
 
+class CgFamily(ctypes.Structure):
+    """pgm_cg_family: the code columns and cardinalities (the variable first when discrete) and the value
+    columns (the variable last when continuous) of a conditional-Gaussian family."""
+    _fields_ = [("n_disc", ctypes.c_int32), ("n_cont", ctypes.c_int32), ("var_discrete", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("dcol", ctypes.c_int32 * PGM_MAX_DIMS), ("card", ctypes.c_int32 * PGM_MAX_DIMS),
+                ("ccol", ctypes.c_int32 * 8)]
+
+
+class CgInfo(ctypes.Structure):
+    """pgm_cg_info_t: the layout and launch geometry of a pgm_cg plan (host-only query)."""
+    _fields_ = [("n_families", ctypes.c_int32), ("n_code_cols", ctypes.c_int32), ("n_value_cols", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("total_tiles", ctypes.c_int64), ("total_blocks", ctypes.c_int64),
+                ("total_jobs", ctypes.c_int64), ("total_chunks", ctypes.c_int64), ("moments_size", ctypes.c_int64),
+                ("stage_tiles", ctypes.c_int64), ("slice_rows", ctypes.c_int64)]
+
+
+# PGM_CG_*: the caps and geometry of the conditional-Gaussian scores
+CG_MAX_CONT, CG_MAX_ROWS, CG_TILES_PER_WAVE, CG_MAX_SLICES, CG_SLICE_MIN = 7, 4096, 16, 256, 1024
+CG_STAGE_TILES, CG_SCORE_CHUNK, CG_LAYOUT = 65536, 128, 6
+
+
 class DbnInfo(ctypes.Structure):
     """pgm_dbn_info_t: the state spaces and launch geometry of a pgm_dbn plan (host-only query)."""
     _fields_ = [("n", ctypes.c_int32), ("n_free", ctypes.c_int32), ("n_configs", ctypes.c_int32),
@@ -572,6 +593,16 @@ _SIGS = {
     "pgm_lgs_pcorr": ([_P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
     "pgm_lgs_score": ([_P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
     "pgm_lgs_ibeta_half": ([ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+    "pgm_cg_plan_create": ([ctypes.POINTER(CgFamily), ctypes.c_int32, ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_cg_plan_destroy": ([_P], ctypes.c_int),
+    "pgm_cg_plan_info": ([_P, ctypes.POINTER(CgInfo), ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
+    "pgm_cg_plan_set_slice": ([_P, ctypes.c_int64], ctypes.c_int),
+    "pgm_cg_moments_info": ([_P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)],
+                            ctypes.c_int),
+    "pgm_cg_moments": ([_P, _P, ctypes.c_int32, ctypes.c_int64, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                        ctypes.c_int64, _P, _P, _P], ctypes.c_int),
+    "pgm_cg_score": ([_P, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     "pgm_dbn_plan_create": ([ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8),
                              ctypes.c_int32, ctypes.POINTER(FitFamily), ctypes.c_int32, ctypes.POINTER(FitFamily),
                              ctypes.c_int32, ctypes.POINTER(_P)], ctypes.c_int),

@@ -33,6 +33,8 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmlg_plan.cpp",    # linear-Gaussian networks: column / family validation, tile groups, slice choice, argument checks (host only)
     "pgmlgs.hip",        # Gaussian structure learning: partial correlations and Gaussian scores from the Gram matrix, their C-ABI
     "pgmlgs_plan.cpp",   # Gaussian structure learning: job validation, buckets, argument checks, the host p-value (host only)
+    "pgmcg.hip",         # conditional-Gaussian scores: the one-hot-masked fp64 MFMA moment kernel, the score kernels, their C-ABI
+    "pgmcg_plan.cpp",    # conditional-Gaussian scores: family validation, operand layout, slices and passes, argument checks (host only)
     "pgmdbn.hip",        # dynamic networks: the fused filter / smoother kernel and the Viterbi kernel for a batch of sequences, their C-ABI
     "pgmdbn_plan.cpp",   # dynamic networks: node / family validation, offset tables, launch geometry, argument checks (host only)
     "pgmdq.cpp",        # direct AQL dispatch (host code, HSA runtime)

@@ -10,7 +10,8 @@ the equivalent sample size are added on the host with math.lgamma, as the refere
 is `local_scores` of one family.
 
 Deviations: every column is discrete whatever its dtype; a variable with 255 or more states
-raises the encoders' ValueError; the conditional-Gaussian scores are not built.
+raises the encoders' ValueError; the conditional-Gaussian scores (LogLikelihoodCondGauss, BICCondGauss, AICCondGauss,
+:1192-1740) take the dtypes as they are and are built as classes only: their names stay closed.
 
 The Gaussian scores (LogLikelihoodGauss, BICGauss, AICGauss) score any number of families in one launch from
 the moment matrix of the continuous columns, computed once per scorer by the fp64 Gram kernel and left on
@@ -24,6 +25,7 @@ import numpy as np
 
 from .. import _native as N
 from .. import engine as E
+from ._cg import CondGaussData
 from ._fit import FitPlan
 from ._gauss import GaussData, cap_error
 from ._rounds import SCORE_BIN_BUDGET, rounds as _rounds  # noqa: F401  (module attributes the tests patch)
@@ -257,3 +259,35 @@ class BICGauss(LogLikelihoodGauss):
 class AICGauss(LogLikelihoodGauss):
     """llf - (df_model + 2) (:1107-1189)."""
     _kind = "aic"
+
+
+class LogLikelihoodCondGauss(CondGaussData, StructureScore):
+    """The conditional-Gaussian log-likelihood of `variable | parents` on mixed data (:1192-1560; the
+    definition is include/pgmhip.h "conditional-Gaussian scores", the deviations DESIGN.md): per round one plan,
+    one launch of the grouped-moment kernel over the resident codes and values (pgm_cg_moments), one score launch
+    (pgm_cg_score) and one download; the penalties of _get_num_parameters are added on the host."""
+
+    def __init__(self, data, state_names=None, **kwargs):
+        CondGaussData.__init__(self, data, state_names=state_names)
+
+    def _score(self, ll, k):
+        return ll
+
+    @E.serialized
+    def local_scores(self, families):
+        """The local score of every (variable, parents) family, as a list of floats."""
+        return [self._score(ll, k) for ll, _, _, _, k in self.run([(v, list(ps)) for v, ps in families])]
+
+
+class BICCondGauss(LogLikelihoodCondGauss):
+    """ll - k / 2 log(rows of the data) (:1563-1650)."""
+
+    def _score(self, ll, k):
+        return ll - 0.5 * k * log(self.n_rows)
+
+
+class AICCondGauss(LogLikelihoodCondGauss):
+    """ll - k (:1653-1740)."""
+
+    def _score(self, ll, k):
+        return ll - k

@@ -18,10 +18,12 @@ __all__ = ["structure_score", "log_likelihood_score", "BayesianModelProbability"
 def structure_score(model, data, scoring_method="bic-d", **kwargs):
     """The structure score of `model` (its graph only) on `data` (metrics.py:222-307): one of k2, bdeu,
     bds, bic-d, aic-d, ll-d; kwargs go to the score's constructor.  The default is "bic-d": the
-    reference's default "bic-g" is a Gaussian score, which is not built."""
+    reference's default "bic-g" is a Gaussian score, which is not built.  `scoring_method` may also be a
+    StructureScore instance (the Gaussian and conditional-Gaussian scores come only so): its own data is
+    scored, `data` serves the column check alone and kwargs are not used."""
     import pandas as pd
 
-    from ..estimators import AIC, BIC, K2, BDeu, BDs, LogLikeliHood
+    from ..estimators import AIC, BIC, K2, BDeu, BDs, LogLikeliHood, StructureScore
 
     classes = {"k2": K2, "bdeu": BDeu, "bds": BDs, "bic-d": BIC, "aic-d": AIC, "ll-d": LogLikeliHood}
     if not isinstance(model, nx.DiGraph):
@@ -31,6 +33,8 @@ def structure_score(model, data, scoring_method="bic-d", **kwargs):
     missing = set(model.nodes()) ^ set(data.columns)
     if missing:
         raise ValueError(f"Missing columns in data or variables in the model: {sorted(map(str, missing))}")
+    if isinstance(scoring_method, StructureScore):  # the Gaussian and conditional-Gaussian scores come as instances
+        return scoring_method.score(model)
     if scoring_method not in classes:
         raise ValueError(f"scoring method not supported: {scoring_method!r} (one of {sorted(classes)})")
     return classes[scoring_method](data, **kwargs).score(model)
