@@ -1699,6 +1699,111 @@ int pgm_dbn_estep(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, 
                   const double *values0, const double *values1, double *tables0, double *tables1, double *loglik,
                   uint8_t *impossible, double *scratch, int64_t scratch_bytes, uint32_t flags, void *stream);
 
+/* ---------------------------------------------------------------- dynamic Bayesian networks: the particle filter
+ * A bootstrap particle filter for two-slice networks whose joint is too large to enumerate (pgm_dbn_run stops at
+ * PGM_DBN_MAX_CONFIGS): N particles per sequence are drawn, weighted, histogrammed and resampled for every
+ * sequence of the batch in ONE launch, a sequence's particles living in the LDS of its workgroup.  What
+ * ApproxInference does with a DynamicBayesianNetwork (inference/ApproxInference.py:164-187).  Five more
+ * extension symbols of ABI 25; the other pgm_dbn_* calls are as they were.
+ *
+ * DATA.  codes[T n, ld] as in pgm_dbn_run: column t n + v is node v of slice t, a row is a sequence, T = n_slices.
+ * Any cell may be observed in one sequence and PGM_EV_MISSING in the next: there is no clamped / free split and
+ * no limit on the joint J.
+ *
+ * THE PLAN is made on the host from the cardinalities (1 .. 254), a `queried` flag per node and the two family
+ * sets of pgm_dbn_plan_create (column h n + v is node v of slice t - 1 + h), validated by its rules, n <= 255.
+ * Each set gets its own PLAN ORDER: Kahn's algorithm over the set's edges within the slice, always taking the
+ * lowest node index that is ready (a cycle is PGM_EINVAL).  Draws and weight products run in that order.  The
+ * INTERFACE is the nodes with a child in the next slice (a slice-t parent of a transition family), in node order.
+ *
+ * RUNNING SUMS.  pgm_dbn_pf_run first writes c_0 = p_0, c_s = c_{s-1} + p_s per CPD column in state order
+ * (pgm_sample_cdf's rule) for values0 and values1 into two buffers that belong to the handle.  A column whose
+ * total is not finite or not > 0 makes the call return PGM_EINVAL after the launch.
+ *
+ * ONE STEP of particle i of sequence b (the b-th of the call's rows) at slice t, node v in plan order, w = 1.0 at
+ * the start of the slice.  The CPD column is chosen by the parents' codes: slice t - 1 parents are those of the
+ * particle's ancestor, slice t parents the particle's own.  UNOBSERVED cell (PGM_EV_MISSING): the state is drawn
+ * with pgm_sample_forward's uniform and selection rule at stream row first_row + b N + i and code column t n + v.
+ * OBSERVED cell: the state is the code, and w = w * (value / c_{K-1}): one IEEE division and one IEEE
+ * multiplication per term, no addition anywhere in the chain (so nothing can be contracted into an fma and a
+ * float64 restatement reproduces w bit for bit).  BAD cell (neither a state nor PGM_EV_MISSING, anywhere in the
+ * sequence): the sequence is not run; flags = PGM_DBN_PF_BAD, filter / ess / loglik NaN, ancestors the identity,
+ * traj PGM_EV_MISSING; the call returns PGM_EINDEX after the launch and no other sequence is affected.
+ *
+ * QUANTISED WEIGHTS.  w_max is the sequence's largest w of the slice; q_i = (uint64) ldexp(w_i / w_max, 36),
+ * truncated; Q = sum q_i < 2^48 for N <= 4096.  Every sum below is an integer sum and has no order.  If w_max
+ * == 0 the sequence is impossible from this slice on: flags = PGM_DBN_PF_IMPOSSIBLE, loglik = -inf, filter and
+ * ess NaN at this and every later slice, ancestors the identity from this slice on, traj the drawn codes at this
+ * slice and PGM_EV_MISSING after it.
+ *
+ * OUTPUTS per slice, before resampling, each optional (NULL):
+ *   filter[b, t, .] = H[s] / Q for every state of every queried node, states end to end in node order (Q bins, as
+ *                     in pgm_dbn_run); H is the integer histogram of q; one fp64 division of the two converted sums
+ *   ess[b, t]       = S1 S1 / S2 in fp64 from S1 = sum q', S2 = sum q'^2, q' = q >> 16
+ *   loglik[b]      += log(w_max) + log((double) Q * 2^-36 / N), added in slice order starting from 0.0
+ *   flags[b]        uint8: 0, PGM_DBN_PF_IMPOSSIBLE or PGM_DBN_PF_BAD
+ *
+ * SYSTEMATIC RESAMPLING, every slice including the last, in integers.  One uniform per (sequence, slice): Philox
+ * at stream row R = first_row + b N with counter (R lo, R hi, t, PGM_DBN_PF_RESAMPLE) and the key of the seed;
+ * m = (x0 << 21) | (x1 >> 11) is its 53-bit integer.  Word 3 of every draw's counter is 0 and PGM_DBN_PF_RESAMPLE
+ * is not, so this counter is never a draw's.  r = umulhi64(m << 11, Q) = floor(m Q / 2^53) < Q.  With the inclusive
+ * prefix sums C_i of q, the ancestor of new particle j is a_j = min{i : N C_i > j Q + r}; it exists because
+ * N C_{N-1} = N Q > j Q + r for j < N, and both sides stay below 2^60.  The new particle j then carries the
+ * interface codes of particle a_j into slice t + 1.
+ *   A slice without an observed cell has w = 1.0 for every particle, so q_i = 2^36 =: q, C_i = (i + 1) q and
+ *   Q = N q.  N C_i > j Q + r  <=>  (i + 1) N q > j N q + r  <=>  i + 1 > j + r / (N q), and 0 <= r / (N q) < 1, so
+ *   i = j satisfies it and i = j - 1 does not: a_j = j, the identity.  A sequence without evidence is therefore
+ *   the forward sampler's rows first_row + b N + i of the same seed.
+ *
+ * TRAJECTORIES, optional: ancestors[n_rows, T, N] uint16 and traj[n_rows, T, n_queried_nodes, N] uint8, the
+ * queried nodes' codes of every particle at every slice before resampling (traj needs ancestors).
+ * pgm_dbn_pf_trace walks them backwards, one work-item per final particle j: i_{T-1} = a_{T-1}[j],
+ * i_{t-1} = a_{t-1}[i_t], and writes out[(t n_queried_nodes + k) ld_out + row0_out + b N + j] = traj[b, t, k, i_t]:
+ * a column-major code matrix [T n_queried_nodes, n_rows N] of equally weighted draws from the particle
+ * approximation of P(x_{0:T-1} | e_{0:T-1}).
+ *
+ * MAPPING.  One workgroup per sequence, min(N, 256) work-items, work-item l owns particles l, l + block, ...;
+ * N = 64 is a single wave and takes no cross-wave step.  LDS (pgm_dbn_pf_info_t.lds_bytes): the slice's codes
+ * and the interface codes of the slice before as [row][particle] bytes ((n + n_interface) N, rounded up to 8),
+ * w / q / the scan (8 N), the histogram (8 Q), a 128-byte pad, the slice's n evidence bytes (rounded up to 8).
+ * A sequence's outputs depend on (seed, first_row + b N, its codes) only: not on the batch around it.
+ *
+ * Checked on the host before any HIP call (PGM_EINVAL): null plan / codes / values, n_cols != n_slices n,
+ * n_slices outside 1 .. 65535, a row window outside ld, N not a power of two in 64 .. 4096, N past the LDS budget
+ * (the message names the largest N that fits), first_row < 0, a misaligned fp64 / uint16 pointer, traj without
+ * ancestors; for the trace null pointers and an output window outside ld_out.  n_rows = 0 is PGM_OK and launches
+ * nothing.  pgm_dbn_pf_plan_create and pgm_dbn_pf_plan_info need no device.  The handle follows the rules of
+ * the plan handles. */
+#define PGM_DBN_PF_RESAMPLE 0x52534d50u /* word 3 of the resampling uniform's Philox counter */
+#define PGM_DBN_PF_MIN_PARTICLES 64
+#define PGM_DBN_PF_MAX_PARTICLES 4096
+#define PGM_DBN_PF_IMPOSSIBLE 1 /* flags: some slice had w_max == 0 */
+#define PGM_DBN_PF_BAD 2        /* flags: a code that is neither a state nor PGM_EV_MISSING */
+typedef struct {
+  int32_t n;             /* slice nodes */
+  int32_t n_interface;   /* interface nodes */
+  int32_t n_query_nodes; /* queried nodes */
+  int32_t n_query;       /* Q = sum card(queried) */
+  int32_t block;         /* work-items per workgroup at this N: min(N, 256) */
+  int32_t max_particles; /* the largest N whose LDS fits */
+  int64_t lds_bytes;     /* LDS of a workgroup at this N */
+  int64_t values0;       /* entries of the slice-0 / the transition value buffer */
+  int64_t values1;
+} pgm_dbn_pf_info_t;
+int pgm_dbn_pf_plan_create(const int32_t *card, const uint8_t *queried, int32_t n, const pgm_fit_family *families0,
+                           int32_t n_families0, const pgm_fit_family *families1, int32_t n_families1, void **plan);
+int pgm_dbn_pf_plan_destroy(void *plan);
+/* order0 / order1: the plan order of a set [n]; off0 / off1: the table offset of every family of the set, in the
+ * order given; any output may be NULL */
+int pgm_dbn_pf_plan_info(void *plan, int32_t n_particles, pgm_dbn_pf_info_t *info, int32_t *order0, int32_t *order1,
+                         int64_t *off0, int64_t *off1);
+int pgm_dbn_pf_run(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
+                   int32_t n_slices, const double *values0, const double *values1, int32_t n_particles, int64_t first_row,
+                   uint64_t seed, double *filter, double *loglik, double *ess, uint8_t *flags, uint16_t *ancestors,
+                   uint8_t *traj, void *stream);
+int pgm_dbn_pf_trace(void *plan, const uint16_t *ancestors, const uint8_t *traj, int64_t n_rows, int32_t n_slices,
+                     int32_t n_particles, uint8_t *out, int64_t ld_out, int64_t row0_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -342,6 +342,18 @@ class DbnEstepInfo(ctypes.Structure):
 DBN_ESTEP_TILE, DBN_ESTEP_DIRECT = 0, 1  # PGM_DBN_ESTEP_*: the path of an info; DIRECT is also the flag that forces it
 DBN_LDS_MAX = 163840  # the LDS a workgroup of the dynamic-network kernels may take
 
+
+class DbnPfInfo(ctypes.Structure):
+    """pgm_dbn_pf_info_t: the geometry of a particle-filter plan at a particle count (host-only query)."""
+    _fields_ = [("n", ctypes.c_int32), ("n_interface", ctypes.c_int32), ("n_query_nodes", ctypes.c_int32),
+                ("n_query", ctypes.c_int32), ("block", ctypes.c_int32), ("max_particles", ctypes.c_int32),
+                ("lds_bytes", ctypes.c_int64), ("values0", ctypes.c_int64), ("values1", ctypes.c_int64)]
+
+
+# PGM_DBN_PF_*: the particle counts, the flags of a sequence, word 3 of the resampling counter, the kernel's LDS budget
+DBN_PF_MIN_PARTICLES, DBN_PF_MAX_PARTICLES, DBN_PF_IMPOSSIBLE, DBN_PF_BAD = 64, 4096, 1, 2
+DBN_PF_RESAMPLE, DBN_PF_LDS_MAX = 0x52534D50, 163840 - 256
+
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
 RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
@@ -616,6 +628,17 @@ _SIGS = {
     "pgm_dbn_estep_info": ([_P, ctypes.c_uint32, ctypes.POINTER(DbnEstepInfo)], ctypes.c_int),
     "pgm_dbn_estep": ([_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P,
                        _P, _P, _P, ctypes.c_int64, ctypes.c_uint32, _P], ctypes.c_int),
+    "pgm_dbn_pf_plan_create": ([ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32,
+                                ctypes.POINTER(FitFamily), ctypes.c_int32, ctypes.POINTER(FitFamily), ctypes.c_int32,
+                                ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_dbn_pf_plan_destroy": ([_P], ctypes.c_int),
+    "pgm_dbn_pf_plan_info": ([_P, ctypes.c_int32, ctypes.POINTER(DbnPfInfo), ctypes.POINTER(ctypes.c_int32),
+                              ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
+                             ctypes.c_int),
+    "pgm_dbn_pf_run": ([_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, _P, _P,
+                        ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
+    "pgm_dbn_pf_trace": ([_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int64, _P],
+                         ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

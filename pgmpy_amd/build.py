@@ -37,6 +37,8 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmcg_plan.cpp",    # conditional-Gaussian scores: family validation, operand layout, slices and passes, argument checks (host only)
     "pgmdbn.hip",        # dynamic networks: the fused filter / smoother kernel and the Viterbi kernel for a batch of sequences, their C-ABI
     "pgmdbn_plan.cpp",   # dynamic networks: node / family validation, offset tables, launch geometry, argument checks (host only)
+    "pgmdbn_pf.hip",     # dynamic networks: the particle filter's running-sum, draw / weight / histogram / resample and trace kernels, their C-ABI
+    "pgmdbn_pf_plan.cpp",  # dynamic networks: the particle filter's validation, plan order, interface, LDS geometry, argument checks (host only)
     "pgmdq.cpp",        # direct AQL dispatch (host code, HSA runtime)
     "pgmpm.cpp",         # plan-specialised batched-BP steps: hipRTC, code-object cache, bound launches (host code)
     "pgmpm_gen.cpp",     # plan-specialised batched-BP steps: planner + generators of the specialised sources (host only)

@@ -15,8 +15,15 @@ Deviations from the reference:
 * ``state_names=None`` means the model's states, all of them, in model order (the reference infers them
   from the samples, in order of appearance, and can miss states).
 
-A ``DynamicBayesianNetwork`` is not taken here (``DBNInference`` filters and smooths it exactly).  There is no
-CPU path: a query raises ``NativeUnavailable`` without the library or a device.
+A ``DynamicBayesianNetwork`` is taken with the reference's signature (variables and evidence keyed ``(name, t)``):
+``query`` / ``map_query`` run bootstrap particle filters over the slices 0 .. the largest slice named
+(pgm_dbn_pf_run, csrc/pgmdbn_pf.hip) and count their traced trajectories, so the answer conditions on ALL the
+evidence, as the reference's rejection sampling of the unrolled network does.  ``n_samples`` is served by
+R = ceil(n_samples / P) independent filters of P = min(4096, the next power of two >= n_samples) particles (64 at
+least, and no more than the model's plan fits into LDS: ``DbnPfPlan.max_particles``) on consecutive stream rows, pooled with the weights exp(loglik_r - max loglik): the combination of
+independent runs that keeps the estimate consistent.  Not built for it: ``virtual_evidence`` (NotImplementedError),
+``query_batch``, ``predict``.  There is no CPU path: a query raises ``NativeUnavailable`` without the library or
+a device.
 """
 import numpy as np
 
@@ -25,21 +32,96 @@ from .. import engine as E
 
 class ApproxInference:
     def __init__(self, model):
-        from ..models import DiscreteBayesianNetwork
+        from ..models import DiscreteBayesianNetwork, DynamicBayesianNetwork
 
-        if not isinstance(model, DiscreteBayesianNetwork):
+        if not isinstance(model, (DiscreteBayesianNetwork, DynamicBayesianNetwork)):
             raise ValueError(
                 f"model should either be a Bayesian Network or Dynamic Bayesian Network. Got {type(model)}.")
         model.check_model()
         self.model = model
+        self._dbn = None
+        if isinstance(model, DynamicBayesianNetwork):
+            from .dbn_inference import DBNInference
+
+            self._dbn = DBNInference(model)
+
+    # ------------------------------------------------------------------ a dynamic network
+    def _dbn_keys(self, variables, evidence):
+        inf = self._dbn
+        variables = [tuple(v) for v in variables]
+        evidence = {tuple(k): s for k, s in (evidence or {}).items()}
+        for name, t in variables + list(evidence):
+            if name not in inf.index:
+                raise ValueError(f"Node {name} not in the model")
+            if not isinstance(t, (int, np.integer)) or t < 0:
+                raise ValueError(f"({name}, {t}): the time slice must be a non-negative integer")
+        for (name, t), state in evidence.items():
+            if state not in inf.state_names[name]:
+                raise ValueError(f"Evidence state: {state} for {(name, t)} doesn't exist")
+        return variables, evidence
+
+    @staticmethod
+    def dbn_filters(n_samples, max_particles=4096):
+        """(R, P): the independent filters and the particles of each that serve `n_samples`; `max_particles` is
+        the most the model's plan fits into LDS (``DbnPfPlan.max_particles``): a larger model takes more filters
+        of fewer particles."""
+        P = min(4096, int(max_particles), max(64, 1 << (max(int(n_samples), 1) - 1).bit_length()))
+        return -(-max(int(n_samples), 1) // P), P
+
+    def _dbn_query(self, variables, n_samples, evidence, joint, state_names, seed):
+        from .batch import download
+
+        inf = self._dbn
+        variables, evidence = self._dbn_keys(variables, evidence)
+        n = len(inf.names)
+        T = 1 + max([t for _, t in variables] + [t for _, t in evidence], default=0)
+        plan = inf.pf_plan({name for name, _ in variables})
+        R, P = self.dbn_filters(n_samples, plan.max_particles)
+        codes = np.full((T * n, R), 255, dtype=np.uint8)
+        for (name, t), state in evidence.items():
+            codes[t * n + inf.index[name]] = inf.state_names[name].index(state)
+        names = [inf.names[v] for v in sorted(plan.query_slices)]  # the trace's rows: the queried nodes in node order
+        samples, loglik, _ = inf._posterior_sample(E.to_device_raw(codes), P, seed, names)
+        samples, loglik = download(samples.contiguous()).astype(np.int64), download(loglik)
+        # the filters are independent estimates of the same posterior: each one's trajectories weigh its evidence estimate
+        with np.errstate(invalid="ignore"):
+            weight = np.repeat(np.exp(loglik - loglik.max()), P)
+        row = {(name, t): samples[t * len(names) + k] for t in range(T) for k, name in enumerate(names)}
+        states = {v: inf.state_names[v[0]] for v in variables}
+        out = []
+        for group in ([variables] if joint else [[v] for v in variables]):
+            shape = [len(states[v]) for v in group]
+            flat = np.ravel_multi_index([row[v] for v in group], shape)
+            hist = np.bincount(flat, weights=weight, minlength=int(np.prod(shape)))
+            with np.errstate(invalid="ignore", divide="ignore"):
+                out.append(self._select(group, (hist / weight.sum()).reshape(shape), state_names, states))
+        return out[0] if joint else dict(zip(variables, out))
+
+    def _dbn_distribution(self, samples, variables, state_names, joint):
+        """get_distribution of a frame with (name, t) columns: counted on the device as the unrolled network's."""
+        from ..factors.discrete import DiscreteFactor
+        from ..models.DynamicBayesianNetwork import _flat
+
+        variables, _ = self._dbn_keys(variables, None)
+        bn, _ = self.model.unroll(1 + max(t for _, t in variables))
+        flat = samples.loc[:, variables]
+        flat.columns = [_flat(v) for v in variables]
+        names = None if state_names is None else {_flat(tuple(v)): s for v, s in state_names.items()}
+        got = ApproxInference(bn).get_distribution(flat, [_flat(v) for v in variables], state_names=names, joint=joint)
+
+        def back(f, group):
+            return DiscreteFactor(group, list(f.cardinality), np.asarray(f.values),
+                                  state_names={v: f.state_names[_flat(v)] for v in group})
+        return back(got, variables) if joint else {v: back(got[_flat(v)], [v]) for v in variables}
 
     # ------------------------------------------------------------------ helpers
-    def _select(self, variables, values, state_names):
+    def _select(self, variables, values, state_names, states=None):
         """A DiscreteFactor over `variables` from `values` [cards of the model's states]; state_names
-        selects and orders the states (a name the model does not know gets 0, as the reference's reindex)."""
+        selects and orders the states (a name the model does not know gets 0, as the reference's reindex).
+        states: {variable: the states of its axis}, the model's when None."""
         from ..factors.discrete import DiscreteFactor
 
-        states = self.model.states
+        states = self.model.states if states is None else states
         names = {}
         for axis, v in enumerate(variables):
             own = list(states[v])
@@ -106,6 +188,8 @@ class ApproxInference:
         from .batch import download, encode_states, upload_codes
 
         variables = list(variables)
+        if self._dbn is not None:
+            return self._dbn_distribution(samples, variables, state_names, joint)
         for v in variables:
             if v not in self.model.nodes():
                 raise ValueError(f"Node {v} not in the model")
@@ -129,10 +213,15 @@ class ApproxInference:
         """P(variables | evidence, virtual_evidence) by likelihood weighting over n_samples draws (one
         pgm_sample_posterior call with one evidence row), or the frequencies of `samples` when given.
         joint=True: one DiscreteFactor; else {variable: DiscreteFactor}.  show_progress is accepted and
-        ignored."""
+        ignored.  On a DynamicBayesianNetwork variables and evidence are keyed (name, t) and the estimate is
+        the pooled particle filters' (the module docstring)."""
         variables = list(variables)
         if samples is not None:
             return self.get_distribution(samples, variables, state_names=state_names, joint=joint)
+        if self._dbn is not None:
+            if virtual_evidence:
+                raise NotImplementedError("virtual_evidence on a DynamicBayesianNetwork is not built")
+            return self._dbn_query(variables, n_samples, evidence, joint, state_names, seed)
         from ..sampling import compiled
 
         for v in variables:
@@ -199,6 +288,8 @@ class ApproxInference:
         joint over `variables`, the frame of log_evidence and ess)."""
         import pandas as pd
 
+        if self._dbn is not None:
+            raise NotImplementedError("query_batch on a DynamicBayesianNetwork is not built: DBNInference.particle_filter_batch")
         codes, c = self._evidence_codes(data)
         if variables is None:
             variables = [v for v in self.model.nodes() if (codes[c.col[v]] == 255).any()]

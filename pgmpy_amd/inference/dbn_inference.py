@@ -21,6 +21,9 @@ The most probable sequence (Viterbi, csrc/pgmdbn.hip k_dbn_viterbi) has the same
 ``viterbi_batch``, ``viterbi_codes``; it maximises over every unobserved cell jointly.
 ``expected_counts_codes`` (csrc/pgmdbn.hip k_dbn_estep) adds every sequence's expected family counts to fp64
 tables on the device: the E-step that ``DynamicBayesianNetwork.fit(estimator="EM")`` iterates on.
+Where the joint of a slice's hidden nodes passes the 4,096 states those enumerate, ``particle_filter_codes`` /
+``particle_filter_batch`` / ``posterior_sample_codes`` (csrc/pgmdbn_pf.hip k_dbn_pf) estimate the filter with a
+bootstrap particle filter instead: no limit on the joint, no clamped nodes.
 There is no CPU path: without a device a compute call raises ``NativeUnavailable``.
 """
 import numpy as np
@@ -28,17 +31,20 @@ import numpy as np
 from .. import engine as E
 from ..factors.discrete import DiscreteFactor
 from ._dbn import SCRATCH_BYTES, DbnPlan, flat_values
+from ._dbn_pf import DbnPfPlan
 
 MISSING = 255
 
 
 class DBNResult:
     """What a batched call returns: ``marginal(name)`` [B, T + 1, card] (host), ``log_likelihood`` [B],
-    ``impossible`` [B] (bool); ``marginals``, ``loglik`` and ``flags`` are the device tensors."""
+    ``impossible`` [B] (bool); ``marginals``, ``loglik`` and ``flags`` are the device tensors.  A particle
+    filter's result has ``ess`` [B, T] as well, the effective sample size of every slice's weights."""
 
-    def __init__(self, names, plan, marginals, loglik, flags):
+    def __init__(self, names, plan, marginals, loglik, flags, ess=None):
         self._names, self._plan = names, plan
         self.marginals, self.loglik, self.flags = marginals, loglik, flags
+        self._ess = ess
         self._host = None
 
     def marginal(self, name):
@@ -63,6 +69,14 @@ class DBNResult:
         from .batch import download
 
         return download(self.flags).astype(bool)
+
+    @property
+    def ess(self):
+        from .batch import download
+
+        if self._ess is None:
+            raise ValueError("this result carries no effective sample sizes (it is not a particle filter's)")
+        return download(self._ess)
 
 
 class ViterbiResult:
@@ -200,6 +214,78 @@ class DBNInference:
         values0, values1 = self._tables() if values is None else values
         tables0, tables1 = (None, None) if tables is None else tables
         return plan.estep(codes, values0, values1, tables0, tables1, scratch_bytes=scratch_bytes, direct=direct)
+
+    # ------------------------------------------------------------------ the particle filter
+    def pf_plan(self, variables=None):
+        """The DbnPfPlan with `variables` (default: every node) queried.  No node is clamped and the joint of a
+        slice has no limit: any cell may be observed in one sequence and missing in the next."""
+        variables = set(self.names if variables is None else variables)
+        for name in variables:
+            if name not in self.index:
+                raise ValueError(f"Node {name} not in the model")
+        key = ("pf", tuple(name in variables for name in self.names))
+        plan = self._plans.get(key)
+        if plan is None:
+            if len(self._plans) >= 64:
+                self._plans.clear()
+            plan = self._plans[key] = DbnPfPlan(self.card, key[1], self.families0, self.families1)
+        return plan
+
+    @E.serialized
+    def particle_filter_codes(self, codes, n_particles=1024, seed=None, variables=None, first_row=0):
+        """(filter [B, T, Q], loglik [B], ess [B, T], impossible [B]) on the device from a bootstrap particle
+        filter with `n_particles` particles per sequence (csrc/pgmdbn_pf.hip k_dbn_pf; a power of two, 64 ..
+        4096): estimates of P(v_t | e_0:t) of the queried nodes laid out as ``filter_codes`` lays them out, of
+        log P(e_0:T-1), and the effective sample size of every slice's weights.  Sequence b draws from the
+        stream rows first_row + b n_particles + i of `seed` (None: fresh entropy), so its results do not depend
+        on the batch around it.  Works where ``filter_codes`` refuses the model: there is no limit on the joint."""
+        from ..sampling import fresh_seed
+
+        values0, values1 = self._tables()
+        filt, loglik, ess, flags, _, _ = self.pf_plan(variables).run(
+            codes, values0, values1, n_particles, fresh_seed() if seed is None else seed, first_row=first_row)
+        return filt, loglik, ess, flags
+
+    def particle_filter_batch(self, data, n_particles=1024, seed=None, variables=None):
+        """``particle_filter_codes`` for every sequence (row) of `data`: a ``DBNResult`` that carries ``ess`` too."""
+        codes, _ = self.encode(data)
+        filt, loglik, ess, flags = self.particle_filter_codes(E.to_device_raw(codes), n_particles, seed, variables)
+        return DBNResult(self.names, self.pf_plan(variables), filt, loglik, flags, ess=ess)
+
+    @E.serialized
+    def _posterior_sample(self, codes, n_particles, seed, variables=None, scratch_bytes=SCRATCH_BYTES, first_row=0):
+        """(samples, loglik [B], flags [B]) of ``posterior_sample_codes``."""
+        import torch
+
+        from ..sampling import fresh_seed
+
+        plan = self.pf_plan(variables)
+        values0, values1 = self._tables()
+        seed = fresh_seed() if seed is None else seed
+        T, B, P = int(codes.shape[0]) // len(self.names), int(codes.shape[1]), int(n_particles)
+        # ancestors (uint16) and traj (uint8 per queried node) of one sequence
+        per_row = max(T * P * (2 + plan.n_query_nodes), 1)
+        chunk = max(1, min(B, int(scratch_bytes) // per_row)) if B else 0
+        out = torch.empty((T * plan.n_query_nodes, max(B * P, 1)), dtype=torch.uint8, device=codes.device)
+        loglik = torch.empty(B, dtype=torch.float64, device=codes.device)
+        flags = torch.empty(B, dtype=torch.uint8, device=codes.device)
+        for r0 in range(0, B, chunk) if B else [0]:
+            nr = min(chunk, B - r0)
+            _, ll, _, fl, anc, traj = plan.run(codes, values0, values1, P, seed, first_row=first_row + r0 * P, n_rows=nr,
+                                               row0=r0, want_filter=False, want_traj=True)
+            plan.trace(anc, traj, out=out, row0_out=r0 * P)
+            loglik[r0:r0 + nr], flags[r0:r0 + nr] = ll, fl
+        return (out if B * P else out[:, :0]), loglik, flags
+
+    def posterior_sample_codes(self, codes, n_particles, seed, variables=None, scratch_bytes=SCRATCH_BYTES):
+        """The traced trajectories of the particle filter, a uint8 code matrix [T queried nodes, B n_particles] on
+        the device: column t queried + k is the k-th queried node of slice t in node order (the order of ``names``, that of
+        ``pf_plan(variables).query_slices``), row b n_particles
+        + j the j-th trajectory of sequence b.  A sequence's rows are equally weighted draws from the particle
+        approximation of P(x_0:T-1 | e_0:T-1).  The ancestors and the particles' codes of a launch take
+        T n_particles (2 + queried) bytes per sequence; the batch is split by rows so that they stay inside
+        `scratch_bytes`, and a sequence's rows do not depend on the split."""
+        return self._posterior_sample(codes, n_particles, seed, variables, scratch_bytes)[0]
 
     # ------------------------------------------------------------------ frames
     def encode(self, data):
