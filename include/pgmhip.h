@@ -1804,6 +1804,77 @@ int pgm_dbn_pf_run(void *plan, const uint8_t *codes, int32_t n_cols, int64_t ld,
 int pgm_dbn_pf_trace(void *plan, const uint16_t *ancestors, const uint8_t *traj, int64_t n_rows, int32_t n_slices,
                      int32_t n_particles, uint8_t *out, int64_t ld_out, int64_t row0_out, void *stream);
 
+/* ---------------------------------------------------------------- MAP by max-product linear programming
+ * MPLP (Globerson and Jaakkola 2007; Sontag et al. 2008) on a Markov network with additive terms theta: block
+ * coordinate descent on the dual of the MAP linear program, for a batch of instances that share the cluster terms
+ * and differ in their node terms, in ONE launch (csrc/pgmmplp.hip k_mplp): every iteration, the decode, the primal
+ * and dual values and the convergence test.
+ *
+ * A plan is made from the nodes' cardinalities and the clusters: each 2 or 3 nodes (cluster_vars [n_clusters][3]);
+ * the last n_triplets of them are tightening triplets.  An intersection set of a factor cluster is each of its
+ * nodes that two or more factor clusters hold, in the order of the cluster's variables; those of a triplet (a, b, c)
+ * are the pairwise clusters over (a, b), (a, c), (b, c), in that order, each of which must exist.  Two factor
+ * clusters may not have the same scope.
+ *
+ * STATE of an instance, state_len fp64 entries: the node objectives (n_unary = sum of card, at node_off), the
+ * cluster objectives (n_theta, C order over the cluster's variables, at n_unary + cluster_off), the messages
+ * (n_msg, in (cluster, set) order, each laid out like its set's objective), the best primal value, dual_lp, and the
+ * best codes as n_nodes fp64 values.  Without state_in a run starts from obj = the terms, zero messages, best =
+ * -inf, dual_lp = the sum of the maxima of the terms; with it from that state (the iteration count starts over).
+ *
+ * UPDATE of cluster c with k > 0 sets:  S = obj[c] + obj[s_0] + .. (added in that order, broadcast);  phi_s =
+ * (max over the variables of c outside s of S) * (1 / k);  msg'[c->s] = phi_s - (obj[s] - msg[c->s]);  obj[s] =
+ * phi_s;  obj[c] = theta_c - msg'[c->s_0] - ..  An ITERATION updates every cluster in the order given, then takes
+ * the first-index argmax of every node objective, primal = the node and cluster terms at that assignment (best
+ * keeps the largest seen and its codes), dual = the sum of the maxima of all objectives, dual_gap = |dual_lp -
+ * dual|, integrality_gap = |dual_lp - best|; converged = (dual_threshold != 0 and dual_gap < dual_threshold) or
+ * (gap_threshold != 0 and integrality_gap < gap_threshold); dual_lp = dual unless converged; the run ends after an
+ * iteration that converged when 17 or more have run.
+ *
+ * LEVELS.  The level of a cluster is one past the highest level of an earlier cluster that touches one of its
+ * tables (its objective, its sets' objectives); clusters of one level touch disjoint tables, so the kernel runs a
+ * level's clusters at once and the levels in order, with the bits of the sequential order.  The two sums are
+ * added on a fixed lattice of 256 work-items (pgmmplp.hip mplp_totals), so a result depends on the instance alone.
+ *
+ * MAPPING.  One workgroup of 256 work-items per instance; the state, a staging area for the phi of one level and,
+ * when it fits as well, theta live in LDS for the whole run (pgm_mplp_info_t.lds_bytes <= lds_max).
+ *
+ * pgm_mplp_run: unaries [n_rows][n_unary], theta [n_theta] (zeros for the triplets), state_in NULL or [n_rows]
+ * [state_len]; out: codes [n_rows][n_nodes], values [n_rows][4] (best primal, dual_lp, dual_gap, integrality_gap;
+ * the gaps are NaN when n_iter = 0), iters [n_rows], state_out NULL or [n_rows][state_len].  All device memory,
+ * all terms finite.  Checked on the host before any HIP call (PGM_EINVAL): at plan creation a cluster of fewer than
+ * 2 or more than 3 nodes, a cardinality outside 1 .. 254, a node out of range or listed twice, a repeated scope, a
+ * triplet without its pairwise clusters, a state and staging area past lds_max (the message names the bytes); at
+ * the run null pointers, negative counts, a negative or non-finite threshold, a misaligned pointer.  n_rows = 0 is
+ * PGM_OK and launches nothing.  pgm_mplp_plan_create and pgm_mplp_plan_info need no device.  The handle follows the
+ * rules of the plan handles. */
+#define PGM_MPLP_VALUES 4
+typedef struct {
+  int32_t n_nodes;
+  int32_t n_clusters;
+  int32_t n_sets;       /* (cluster, intersection set) pairs */
+  int32_t n_levels;     /* dependency levels of an iteration */
+  int32_t theta_in_lds; /* 1: theta is kept in LDS too */
+  int32_t block;        /* work-items per workgroup: 256 */
+  int64_t n_unary;      /* sum of the cardinalities: a row of unaries */
+  int64_t n_theta;      /* entries of theta */
+  int64_t n_msg;        /* entries of all messages */
+  int64_t n_stage;      /* entries of the staging area: the largest level's sets */
+  int64_t state_len;    /* n_unary + n_theta + n_msg + 2 + n_nodes */
+  int64_t lds_bytes;    /* LDS of a workgroup */
+  int64_t lds_max;      /* the most a workgroup may have */
+} pgm_mplp_info_t;
+int pgm_mplp_plan_create(const int32_t *card, int32_t n_nodes, const int32_t *cluster_nvars, const int32_t *cluster_vars,
+                         int32_t n_clusters, int32_t n_triplets, void **plan);
+int pgm_mplp_plan_destroy(void *plan);
+/* node_off [n_nodes + 1]; cluster_off [n_clusters + 1] (offsets in theta); set_count, level [n_clusters]; any
+ * output may be NULL */
+int pgm_mplp_plan_info(void *plan, pgm_mplp_info_t *info, int32_t *node_off, int32_t *cluster_off, int32_t *set_count,
+                       int32_t *level);
+int pgm_mplp_run(void *plan, const double *unaries, const double *theta, int64_t n_rows, int32_t n_iter,
+                 double dual_threshold, double gap_threshold, const double *state_in, uint8_t *codes, double *values,
+                 int32_t *iters, double *state_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

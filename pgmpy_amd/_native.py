@@ -343,6 +343,15 @@ DBN_ESTEP_TILE, DBN_ESTEP_DIRECT = 0, 1  # PGM_DBN_ESTEP_*: the path of an info;
 DBN_LDS_MAX = 163840  # the LDS a workgroup of the dynamic-network kernels may take
 
 
+class MplpInfo(ctypes.Structure):
+    """pgm_mplp_info_t: the sizes, levels and LDS of an Mplp plan (host-only query)."""
+    _fields_ = [("n_nodes", ctypes.c_int32), ("n_clusters", ctypes.c_int32), ("n_sets", ctypes.c_int32),
+                ("n_levels", ctypes.c_int32), ("theta_in_lds", ctypes.c_int32), ("block", ctypes.c_int32),
+                ("n_unary", ctypes.c_int64), ("n_theta", ctypes.c_int64), ("n_msg", ctypes.c_int64),
+                ("n_stage", ctypes.c_int64), ("state_len", ctypes.c_int64), ("lds_bytes", ctypes.c_int64),
+                ("lds_max", ctypes.c_int64)]
+
+
 class DbnPfInfo(ctypes.Structure):
     """pgm_dbn_pf_info_t: the geometry of a particle-filter plan at a particle count (host-only query)."""
     _fields_ = [("n", ctypes.c_int32), ("n_interface", ctypes.c_int32), ("n_query_nodes", ctypes.c_int32),
@@ -353,6 +362,7 @@ class DbnPfInfo(ctypes.Structure):
 # PGM_DBN_PF_*: the particle counts, the flags of a sequence, word 3 of the resampling counter, the kernel's LDS budget
 DBN_PF_MIN_PARTICLES, DBN_PF_MAX_PARTICLES, DBN_PF_IMPOSSIBLE, DBN_PF_BAD = 64, 4096, 1, 2
 DBN_PF_RESAMPLE, DBN_PF_LDS_MAX = 0x52534D50, 163840 - 256
+MPLP_VALUES = 4  # pgm_mplp_run's values per instance: best primal, dual_lp, dual_gap, integrality_gap
 
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
@@ -639,6 +649,13 @@ _SIGS = {
                         ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     "pgm_dbn_pf_trace": ([_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int64, _P],
                          ctypes.c_int),
+    "pgm_mplp_plan_create": ([ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                              ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_mplp_plan_destroy": ([_P], ctypes.c_int),
+    "pgm_mplp_plan_info": ([_P, ctypes.POINTER(MplpInfo), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "pgm_mplp_run": ([_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P, _P],
+                     ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -2,6 +2,7 @@ from .base import Inference
 from .ExactInference import BeliefPropagation, BeliefPropagationWithMessagePassing, VariableElimination
 from .ApproxInference import ApproxInference
 from .dbn_inference import DBNInference
+from .Mplp import Mplp
 
 __all__ = ["Inference", "VariableElimination", "BeliefPropagation", "BeliefPropagationWithMessagePassing",
-           "ApproxInference", "DBNInference"]
+           "ApproxInference", "DBNInference", "Mplp"]
