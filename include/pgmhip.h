@@ -1875,6 +1875,79 @@ int pgm_mplp_run(void *plan, const double *unaries, const double *theta, int64_t
                  double dual_threshold, double gap_threshold, const double *state_in, uint8_t *codes, double *values,
                  int32_t *iters, double *state_out, void *stream);
 
+/* ---------------------------------------------------------------- Marginals by loopy belief propagation
+ * Sum-product belief propagation with the flooding schedule on a Markov network (a factor graph) with
+ * multiplicative potentials psi >= 0, for a batch of instances that share the factor tables and differ in their node
+ * terms phi, in ONE launch (csrc/pgmlbp.hip k_lbp): every iteration, the convergence test, the node and factor
+ * beliefs and the Bethe estimate of log Z.  Exact on a forest once the messages have crossed it; an approximation on
+ * a graph with loops, which need not converge.
+ *
+ * A plan is made from the nodes' cardinalities and the factor scopes: each 1 to 3 distinct nodes (factor_vars
+ * [n_factors][3]); scopes may repeat and unary factors are factors like any other.  Factor f's table is row-major
+ * over its variables, at factor_off[f] of theta.  `theta` at plan creation is HOST memory, n_theta entries, or NULL:
+ * factors whose tables hold the same values (bit for bit, as flat arrays) then share one table in the kernel (a Potts
+ * grid has one table, not one per edge), which decides whether the tables fit in LDS beside the state.  The theta of
+ * a run must repeat those equalities; with NULL every factor keeps its own table.
+ *
+ * PAIRS.  One pair per (factor f, variable v of f), in (factor, position) order; the message f -> v, the cavity v ->
+ * f and the unnormalised new message each take card(v) cells at msg_off[pair]; n_msg is their sum and the STATE of an
+ * instance is the n_msg message cells.  Without state_in every message starts uniform (1 / card).
+ *
+ * ITERATION, three phases with a workgroup barrier after each.  (1) cavity(f, u)(x) = phi_u(x) times the messages
+ * g -> u of u's other pairs, in factor order: an explicit product, no division.  (2) raw(f, v)(x) = the sum over the
+ * joint states of f's other variables, in ascending flat order, of psi_f times their cavities.  (3) Z = the sum of
+ * the pair's raw cells in ascending order; new = (1 - damping) raw / Z + damping old; the residual of the iteration is
+ * the largest |new - old| over all cells.  An instance stops after the first iteration whose residual is < tol (tol
+ * = 0: exactly n_iter iterations).  Z = 0 is a CONTRADICTION: the instance ends with iters = -1 and NaN marginals,
+ * values and factor beliefs (its state is unspecified); the other instances are not affected.  A node or factor
+ * belief that sums to 0 counts as one too.
+ *
+ * AFTER the iterations: b_v = phi_v times all messages into v, normalised; b_f = psi_f times the cavities of its
+ * variables, normalised; value 0 = sum_f sum b_f log(psi_f / b_f) + sum_v sum b_v (log phi_v - (1 - deg_v) log b_v)
+ * with 0 log 0 = 0 and deg_v the pairs of v: the Bethe estimate of log Z (of log P~(evidence) when phi carries
+ * evidence).  Work-item l adds the shares of nodes l, l + 256, .. and then of factors l, l + 256, ..; a wave adds its
+ * 64 partial sums in a butterfly and the four wave totals are added in wave order, so a result depends on the
+ * instance alone.  value 1 = the residual of the last iteration (NaN when n_iter = 0).
+ *
+ * MAPPING.  One workgroup of 256 work-items per instance; the node terms, the messages, the cavities, the raw
+ * messages and, when they fit as well, the unique tables live in LDS for the whole run (pgm_lbp_info_t.lds_bytes <=
+ * lds_max); tables that do not fit are read from global memory through the caches.  There is no global-memory tier
+ * for the state.
+ *
+ * pgm_lbp_run: unaries [n_rows][n_unary], theta [n_theta], state_in NULL or [n_rows][state_len]; out: marginals
+ * [n_rows][n_unary], values [n_rows][2], iters [n_rows], factor_beliefs NULL or [n_rows][n_theta] (each factor at its
+ * own offset), state_out NULL or [n_rows][state_len].  All device memory; all terms finite and >= 0.  Checked on the
+ * host before any HIP call (PGM_EINVAL): at plan creation a factor of 0 or more than 3 nodes, a node out of range or
+ * listed twice in a scope, a cardinality outside 1 .. 254, more than 2^31 - 1 table entries, a state past lds_max
+ * (the message names the bytes); at the run null pointers, negative counts, a negative, NaN or infinite tolerance, a
+ * damping outside [0, 1), a misaligned pointer.  n_rows = 0 is PGM_OK and launches nothing.  pgm_lbp_plan_create and
+ * pgm_lbp_plan_info need no device.  The handle follows the rules of the plan handles. */
+#define PGM_LBP_VALUES 2
+typedef struct {
+  int32_t n_nodes;
+  int32_t n_factors;
+  int32_t n_pairs;         /* (factor, variable) pairs */
+  int32_t n_tables_unique; /* tables after deduplication by value */
+  int32_t theta_in_lds;    /* 1: the unique tables are kept in LDS too */
+  int32_t block;           /* work-items per workgroup: 256 */
+  int64_t n_unary;         /* sum of the cardinalities: a row of unaries and of marginals */
+  int64_t n_msg;           /* message cells: the sum of card(variable) over the pairs */
+  int64_t n_theta;         /* entries of theta */
+  int64_t n_theta_unique;  /* entries of the unique tables */
+  int64_t state_len;       /* n_msg */
+  int64_t lds_bytes;       /* LDS of a workgroup */
+  int64_t lds_max;         /* the most a workgroup may have */
+} pgm_lbp_info_t;
+int pgm_lbp_plan_create(const int32_t *card, int32_t n_nodes, const int32_t *factor_nvars, const int32_t *factor_vars,
+                        int32_t n_factors, const double *theta, void **plan);
+int pgm_lbp_plan_destroy(void *plan);
+/* node_off [n_nodes + 1]; factor_off [n_factors + 1] (offsets in theta); msg_off [n_pairs + 1]; any output may be
+ * NULL */
+int pgm_lbp_plan_info(void *plan, pgm_lbp_info_t *info, int32_t *node_off, int32_t *factor_off, int32_t *msg_off);
+int pgm_lbp_run(void *plan, const double *unaries, const double *theta, int64_t n_rows, int32_t n_iter, double tol,
+                double damping, const double *state_in, double *marginals, double *values, int32_t *iters,
+                double *factor_beliefs, double *state_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

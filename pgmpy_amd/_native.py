@@ -364,6 +364,18 @@ DBN_PF_MIN_PARTICLES, DBN_PF_MAX_PARTICLES, DBN_PF_IMPOSSIBLE, DBN_PF_BAD = 64, 
 DBN_PF_RESAMPLE, DBN_PF_LDS_MAX = 0x52534D50, 163840 - 256
 MPLP_VALUES = 4  # pgm_mplp_run's values per instance: best primal, dual_lp, dual_gap, integrality_gap
 
+
+class LbpInfo(ctypes.Structure):
+    """pgm_lbp_info_t: the sizes, the unique tables and the LDS of a loopy-BP plan (host-only query)."""
+    _fields_ = [("n_nodes", ctypes.c_int32), ("n_factors", ctypes.c_int32), ("n_pairs", ctypes.c_int32),
+                ("n_tables_unique", ctypes.c_int32), ("theta_in_lds", ctypes.c_int32), ("block", ctypes.c_int32),
+                ("n_unary", ctypes.c_int64), ("n_msg", ctypes.c_int64), ("n_theta", ctypes.c_int64),
+                ("n_theta_unique", ctypes.c_int64), ("state_len", ctypes.c_int64), ("lds_bytes", ctypes.c_int64),
+                ("lds_max", ctypes.c_int64)]
+
+
+LBP_VALUES = 2  # pgm_lbp_run's values per instance: the Bethe estimate of log Z, the last residual
+
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
 RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
@@ -656,6 +668,13 @@ _SIGS = {
                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "pgm_mplp_run": ([_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P, _P],
                      ctypes.c_int),
+    "pgm_lbp_plan_create": ([ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                             ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _P, ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_lbp_plan_destroy": ([_P], ctypes.c_int),
+    "pgm_lbp_plan_info": ([_P, ctypes.POINTER(LbpInfo), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                           ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "pgm_lbp_run": ([_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P, _P,
+                     _P], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -41,6 +41,8 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmdbn_pf_plan.cpp",  # dynamic networks: the particle filter's validation, plan order, interface, LDS geometry, argument checks (host only)
     "pgmmplp.hip",       # Markov-network MAP by max-product linear programming: the fused batch kernel, its C-ABI
     "pgmmplp_plan.cpp",  # Markov-network MAP: cluster validation, intersection sets, levels, item lists, LDS layout, argument checks (host only)
+    "pgmlbp.hip",        # Markov-network marginals by loopy belief propagation: the fused batch kernel, its C-ABI
+    "pgmlbp_plan.cpp",   # Markov-network marginals: scope validation, pairs, incidence lists, table deduplication, LDS layout, argument checks (host only)
     "pgmdq.cpp",        # direct AQL dispatch (host code, HSA runtime)
     "pgmpm.cpp",         # plan-specialised batched-BP steps: hipRTC, code-object cache, bound launches (host code)
     "pgmpm_gen.cpp",     # plan-specialised batched-BP steps: planner + generators of the specialised sources (host only)

@@ -3,6 +3,7 @@ from .ExactInference import BeliefPropagation, BeliefPropagationWithMessagePassi
 from .ApproxInference import ApproxInference
 from .dbn_inference import DBNInference
 from .Mplp import Mplp
+from .LoopyBeliefPropagation import LoopyBeliefPropagation
 
 __all__ = ["Inference", "VariableElimination", "BeliefPropagation", "BeliefPropagationWithMessagePassing",
-           "ApproxInference", "DBNInference", "Mplp"]
+           "ApproxInference", "DBNInference", "Mplp", "LoopyBeliefPropagation"]
