@@ -1948,6 +1948,66 @@ int pgm_lbp_run(void *plan, const double *unaries, const double *theta, int64_t 
                 double damping, const double *state_in, double *marginals, double *values, int32_t *iters,
                 double *factor_beliefs, double *state_out, void *stream);
 
+/* ---------------------------------------------------------------- Pseudo-likelihood of a Markov network
+ * The value and the gradient of Besag's log pseudo-likelihood of a discrete Markov network in its log-potentials
+ * theta, from count tables (csrc/pgmmnpl.hip k_mn_pl, k_mn_pl_gather):
+ *   PL(theta) = sum_rows sum_i log p(x_i | x_MB(i)),  p(x_i = s | .) prop. to exp sum_{f holds i} theta_f(s, x_{f\i}).
+ * A row enters only through the configuration of {i} + MB(i), so the rows are counted once (pgm_fit_count on the
+ * BLANKET FAMILIES below) and an evaluation reads tables only; it does not depend on the number of rows.
+ *
+ * A plan is made from the factors as pgm_gibbs_plan_create takes them (pgm_fit_family records in the C order of
+ * their tables, every column 0 .. n_cols - 1 in a factor, cardinalities <= 254); theta and grad have the flat layout
+ * of those factors, factor f at fac_off[f].  The blanket of column i is every other column of a factor that holds
+ * i; its blanket family is (i, the blanket columns ascending), 1 + blanket <= PGM_MAX_DIMS columns.  counts is the
+ * int64 buffer of a fit plan made from the n_cols blanket families in column order: n_i[s, c] at count_off[i] + s *
+ * n_cfg + c, c the mixed-radix number of the blanket's states, the last column fastest.
+ *
+ * k_mn_pl, one workgroup of 256 per node (so a node's work is split by its own table alone).  A work-item owns the
+ * configurations c = lane, lane + 256, ..: N_c = sum_s n[s, c]; the logits l[s] = sum of theta_f(s, x_{f\i}) over the
+ * incident factors in ascending order; lse = max + log sum exp(l - max); the residual r[s, c] = n[s, c] - N_c exp(l[s]
+ * - lse) goes to an LDS table and sum_s n[s, c] (l[s] - lse) to the work-item's partial (c ascending, s ascending).
+ * N_c = 0 writes zeros and computes nothing.  A wave adds its 64 partials in a butterfly, the four wave totals are
+ * added in wave order: node_values[i].  After the barrier, for every incident factor and every entry (s, x) of its
+ * table one work-item adds r[s, c] over the configurations c that agree with x, c ascending, and writes the sum to
+ * the entry of the (factor, member) SLOT of the parts buffer: slot (f, m) is size_f entries at part_off[f] + m *
+ * size_f, and has this one writer.  The incident tables are staged in LDS behind the residual table when both fit
+ * lds_max, and read through the caches otherwise.  k_mn_pl_gather: grad[e] = the sum of the entry's parts in member
+ * order - l2 * theta[e]; value = the node values added in node order, then - l2 / 2 * theta[e]^2 in entry order.
+ * No atomic, no order that depends on the launch: a node's value and a factor's gradient are the same bits whatever
+ * else the plan holds, and on every launch.
+ *
+ * Checked on the host before any HIP call (PGM_EINVAL): what pgm_gibbs_plan_create checks; a blanket family of more
+ * than PGM_MAX_DIMS columns; a node whose residual table and pad exceed lds_max (the message names the node, its
+ * blanket columns and the bytes: there is no global-memory tier); at the evaluation null plan / counts / theta /
+ * value, a negative, NaN or infinite l2, a misaligned pointer.  grad and node_values may be NULL.
+ * pgm_mnpl_plan_create and pgm_mnpl_plan_info need no device.  The handle follows the rules of the plan handles
+ * (the parts buffer belongs to it: calls on one plan must not overlap). */
+typedef struct {
+  int32_t n_nodes;
+  int32_t n_factors;
+  int32_t n_incidences;    /* (factor, member) pairs = part slots */
+  int32_t block;           /* work-items per workgroup: 256 */
+  int32_t max_node;        /* the node whose workgroup needs the most LDS */
+  int32_t max_degree;      /* its blanket columns */
+  int32_t theta_lds_nodes; /* nodes whose incident tables are staged in LDS */
+  int32_t reserved;
+  int64_t n_theta;         /* entries of theta and grad */
+  int64_t n_counts;        /* entries of the count buffer */
+  int64_t n_parts;         /* entries of the parts buffer */
+  int64_t lds_bytes;       /* LDS of the launch: node max_node's */
+  int64_t lds_max;         /* the most a workgroup may have */
+} pgm_mnpl_info_t;
+int pgm_mnpl_plan_create(const pgm_fit_family *factors, int32_t n_factors, const int32_t *card, int32_t n_cols,
+                         void **plan);
+int pgm_mnpl_plan_destroy(void *plan);
+/* families [n_cols]: the blanket families; count_off [n_cols + 1]; fac_off, part_off [n_factors + 1]; node_lds
+ * [n_cols]: the LDS bytes of each node's workgroup; slots [n_incidences][3]: (factor, member, offset in parts) in the
+ * order the kernel walks them (by node, factors ascending).  Any output may be NULL */
+int pgm_mnpl_plan_info(void *plan, pgm_mnpl_info_t *info, pgm_fit_family *families, int64_t *count_off,
+                       int64_t *fac_off, int64_t *part_off, int64_t *node_lds, int64_t *slots);
+int pgm_mnpl_eval(void *plan, const int64_t *counts, const double *theta, double l2, double *value, double *grad,
+                  double *node_values, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

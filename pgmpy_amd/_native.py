@@ -376,6 +376,15 @@ class LbpInfo(ctypes.Structure):
 
 LBP_VALUES = 2  # pgm_lbp_run's values per instance: the Bethe estimate of log Z, the last residual
 
+
+class MnplInfo(ctypes.Structure):
+    """pgm_mnpl_info_t: the sizes and the LDS of a pseudo-likelihood plan (host-only query)."""
+    _fields_ = [("n_nodes", ctypes.c_int32), ("n_factors", ctypes.c_int32), ("n_incidences", ctypes.c_int32),
+                ("block", ctypes.c_int32), ("max_node", ctypes.c_int32), ("max_degree", ctypes.c_int32),
+                ("theta_lds_nodes", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_theta", ctypes.c_int64),
+                ("n_counts", ctypes.c_int64), ("n_parts", ctypes.c_int64), ("lds_bytes", ctypes.c_int64),
+                ("lds_max", ctypes.c_int64)]
+
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
 RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
@@ -675,6 +684,12 @@ _SIGS = {
                            ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "pgm_lbp_run": ([_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P, _P,
                      _P], ctypes.c_int),
+    "pgm_mnpl_plan_create": ([ctypes.POINTER(FitFamily), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                              ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_mnpl_plan_destroy": ([_P], ctypes.c_int),
+    "pgm_mnpl_plan_info": ([_P, ctypes.POINTER(MnplInfo), ctypes.POINTER(FitFamily)] + [ctypes.POINTER(ctypes.c_int64)] * 5,
+                           ctypes.c_int),
+    "pgm_mnpl_eval": ([_P, _P, _P, ctypes.c_double, _P, _P, _P, _P], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

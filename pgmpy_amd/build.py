@@ -43,6 +43,8 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmmplp_plan.cpp",  # Markov-network MAP: cluster validation, intersection sets, levels, item lists, LDS layout, argument checks (host only)
     "pgmlbp.hip",        # Markov-network marginals by loopy belief propagation: the fused batch kernel, its C-ABI
     "pgmlbp_plan.cpp",   # Markov-network marginals: scope validation, pairs, incidence lists, table deduplication, LDS layout, argument checks (host only)
+    "pgmmnpl.hip",       # Markov-network pseudo-likelihood: the value / residual / gradient-part kernel, the gather kernel, their C-ABI
+    "pgmmnpl_plan.cpp",  # Markov-network pseudo-likelihood: scope validation, blanket families, digits, part slots, LDS sizing, argument checks (host only)
     "pgmdq.cpp",        # direct AQL dispatch (host code, HSA runtime)
     "pgmpm.cpp",         # plan-specialised batched-BP steps: hipRTC, code-object cache, bound launches (host code)
     "pgmpm_gen.cpp",     # plan-specialised batched-BP steps: planner + generators of the specialised sources (host only)

@@ -25,6 +25,10 @@ string names "pearsonr", "ll-g", "bic-g", "aic-g" stay closed.
 Mixed data: LogLikelihoodCondGauss, BICCondGauss, AICCondGauss score all the families of a hill-climb step
 over discrete and continuous columns in one grouped-moment launch on the fp64 matrix units and one score
 launch (pgm_cg_moments, pgm_cg_score); HillClimbSearch takes an instance.
+
+Markov networks: PseudoLikelihoodEstimator fits the potentials by maximum pseudo-likelihood: one count launch on the
+nodes' blanket families, then one launch pair per evaluation of the objective and its gradient on the count tables
+(pgm_mnpl_eval) under L-BFGS.
 """
 from .base import BaseEstimator, ParameterEstimator
 from .MLE import MaximumLikelihoodEstimator
@@ -37,9 +41,10 @@ from .CITests import CITester, GaussCITester
 from .PC import PC
 from .EM import ExpectationMaximization
 from .TreeSearch import TreeSearch
+from .PseudoLikelihood import PseudoLikelihoodEstimator
 
 __all__ = ["BaseEstimator", "ParameterEstimator", "MaximumLikelihoodEstimator", "BayesianEstimator",
            "StructureScore", "K2", "BDeu", "BDs", "LogLikeliHood", "BIC", "AIC", "get_scoring_method",
            "LogLikelihoodGauss", "BICGauss", "AICGauss", "LogLikelihoodCondGauss", "BICCondGauss", "AICCondGauss",
            "HillClimbSearch", "ExpertKnowledge", "CITests", "CITester",
-           "GaussCITester", "PC", "ExpectationMaximization", "TreeSearch"]
+           "GaussCITester", "PC", "ExpectationMaximization", "TreeSearch", "PseudoLikelihoodEstimator"]

@@ -1,6 +1,7 @@
 """Model metrics (mirror of pgmpy/metrics/metrics.py and pgmpy/metrics/bn_inference.py).  Built:
 structure_score, log_likelihood_score and BayesianModelProbability (one device pass over the codes,
-bn_inference.py), correlation_score and fisher_c (their tests batched through one CITester), SHD.  Not
+bn_inference.py), correlation_score and fisher_c (their tests batched through one CITester), SHD,
+pseudo_log_likelihood (a Markov network's held-out score: the project's own, the reference has none).  Not
 built: implied_cis (it needs DAG.minimal_dseparator, which is not built), the Gaussian scores of
 structure_score."""
 import math
@@ -12,7 +13,7 @@ import numpy as np
 from .bn_inference import BayesianModelProbability
 
 __all__ = ["structure_score", "log_likelihood_score", "BayesianModelProbability", "correlation_score", "fisher_c",
-           "SHD", "f1_score", "chi2_sf_even"]
+           "SHD", "f1_score", "chi2_sf_even", "pseudo_log_likelihood"]
 
 
 def structure_score(model, data, scoring_method="bic-d", **kwargs):
@@ -61,6 +62,24 @@ def log_likelihood_score(model, data):
     _check_model_and_frame(model, data, "log_likelihood_score")
     model.check_model()
     return BayesianModelProbability(model).score(data)
+
+
+def pseudo_log_likelihood(model, data):
+    """sum_rows sum_i log p(x_i | x_MB(i)) of `data` (a DataFrame, or resident uint8 device codes [n_nodes, n_rows]
+    in column_order(model)) under a DiscreteMarkovNetwork's own potentials: a held-out score that needs no partition
+    function.  One count launch and one pgm_mnpl_eval with theta = log(potentials); a zero potential is -inf."""
+    import torch
+
+    from ..estimators import PseudoLikelihoodEstimator
+
+    if not model.factors:
+        raise ValueError("pseudo_log_likelihood: the model has no factors")
+    if isinstance(data, torch.Tensor):
+        est = PseudoLikelihoodEstimator.from_codes(model, data)
+    else:
+        est = PseudoLikelihoodEstimator(model, data)
+    theta = torch.log(torch.cat([f._d().reshape(-1) for f in model.factors]))
+    return float(est.value_and_grad(theta, want_grad=False)[0])
 
 
 def f1_score(y_true, y_pred):

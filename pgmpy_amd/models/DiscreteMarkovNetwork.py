@@ -288,6 +288,34 @@ class DiscreteMarkovNetwork(nx.Graph):
         total = contract_factors([(f._d(), list(f.variables)) for f in self.factors], [])
         return float(to_host(total))
 
+    # ------------------------------------------------------------------ learning
+    def fit(self, data, estimator="pseudo-likelihood", state_names=None, scopes=None, **kwargs):
+        """Estimate the potentials from the DataFrame `data` and replace the model's factors with them, as
+        DiscreteBayesianNetwork.fit replaces CPDs.  estimator: "pseudo-likelihood" (PseudoLikelihoodEstimator; the
+        keyword arguments go to its estimate: l2, max_iter, tol, init).  Returns the model."""
+        from ..estimators import PseudoLikelihoodEstimator
+
+        if estimator != "pseudo-likelihood":
+            raise ValueError(f"estimator {estimator!r} is not supported (\"pseudo-likelihood\")")
+        return self._take(PseudoLikelihoodEstimator(self, data, state_names, scopes), kwargs)
+
+    def fit_codes(self, codes, nodes=None, card=None, estimator="pseudo-likelihood", state_names=None, scopes=None,
+                  **kwargs):
+        """`fit` on resident data: the uint8 device codes [n_nodes, n_rows] that GibbsSampling.sample_codes returns
+        (rows in the order of `nodes`, default column_order(model)); nothing is copied to the host."""
+        from ..estimators import PseudoLikelihoodEstimator
+
+        if estimator != "pseudo-likelihood":
+            raise ValueError(f"estimator {estimator!r} is not supported (\"pseudo-likelihood\")")
+        return self._take(PseudoLikelihoodEstimator.from_codes(self, codes, nodes, card, state_names, scopes), kwargs)
+
+    def _take(self, est, kwargs):
+        factors = est.estimate(**kwargs)
+        for factor in factors:  # a factor's scope must be a clique of the graph
+            self.add_edges_from(itertools.combinations(factor.variables, 2))
+        self.factors = list(factors)
+        return self
+
     def copy(self):
         clone = DiscreteMarkovNetwork(self.edges())
         clone.add_nodes_from(self.nodes())
