@@ -875,6 +875,68 @@ int pgm_fit_estep(void *plan, const int32_t *latent_cols, int32_t n_latent, cons
                   const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0, int64_t n_rows,
                   double *tables, double *loglik, void *stream);
 
+/* ---------------------------------------------------------------- the E-step on rows with missing cells
+ * (an extension of ABI 25.)  True missing-data EM, and the exact log P(observed cells) of a row: where
+ * pgm_fit_estep drops a row with PGM_EV_MISSING in an observed column, pgm_fit_estep_rows marginalises the
+ * missing cells.  plan is an ordinary fit plan, one family per CPD that EM re-estimates (or every family of the
+ * network, for scoring); every code column must have one cardinality in all its families.  values, tables,
+ * codes, the window and latent_cols are pgm_fit_estep's; n_latent may be 0.  For a row r:
+ *   U(r)       the plan's columns whose code is PGM_EV_MISSING in r, plus latent_cols (virtual, never read).
+ *   touched    a family whose scope meets U(r).
+ *   C(r)       the connected components of U(r), two members linked when one family holds both.
+ *   per component c with L_c = product of its cardinalities joint configurations l:
+ *     p_l = product over the families touched by c of values[entry(x_obs, l)], each value floored at
+ *           PGM_EM_FLOOR unless PGM_EMR_NO_FLOOR;  Z_c = sum_l p_l;  w_l = p_l / Z_c;
+ *     tables[entry(x_obs, l)] += w_l for every l, in every family touched by c (all unobserved members of a
+ *           family lie in one component).
+ *   An untouched family adds NOTHING here: its share is the integer count pgm_fit_count produces (it skips a
+ *   row per family on a missing cell) and does not depend on the parameters, so the caller counts it once and
+ *   adds it to the fractional tables of every iteration.
+ *   loglik[row0 + r] (optional, device, fp64, ld entries) = sum_c log Z_c + sum over the untouched families of
+ *   log(value, floored unless NO_FLOOR): log P(x_obs) restricted to the plan's families.  With loglik NULL a
+ *   complete row costs only the scan.  tables may be NULL when only loglik is wanted (scoring).
+ *   With NO_FLOOR and some Z_c = 0, or a zero entry in an untouched family, P(x_obs) = 0 and the row is impossible: it
+ *   adds nothing to any table and its loglik is -inf.  (A complete row that no wave takes, loglik being NULL, has
+ *   status COMPLETE without its entries being read.)
+ * Limits per row: |U(r)| <= PGM_EMR_MAX_UNOBSERVED; L_c <= PGM_EM_MAX_CONFIGS and at most PGM_EM_MAX_FAMILIES
+ * families per component (so p_l >= 1e-320 under the floor, as above); at most PGM_EMR_MAX_ROW_FAMILIES touched
+ * families per row.  A row past a limit is decided before its first add: it adds nothing, its loglik is NaN
+ * and it is counted in *n_skipped (host, optional; the call synchronises the stream for the flag word anyway).
+ * That is not an error.  A code that is neither missing nor a state: the row adds nothing, its loglik is NaN
+ * and the call returns PGM_EINDEX after the launch.  status (optional, device, uint8, ld entries indexed by
+ * buffer row): PGM_EMR_COMPLETE, _MARGINALISED, _SKIPPED, _IMPOSSIBLE, _BAD_CODE.
+ *
+ * Determinism: a row's loglik and status are bit-identical wherever the row sits and whatever else is in the
+ * window (configuration l is taken by lane l % 64 in ascending l, the families of a component multiply in a
+ * fixed order, Z_c is a fixed butterfly).  tables are added with fp64 atomics in no fixed order, as in
+ * pgm_fit_estep: they are not bit-identical from run to run.
+ *
+ * Every argument is checked on the host before any HIP call: PGM_EINVAL for a null plan / values / codes, tables
+ * and loglik both NULL, n_latent outside 0 .. PGM_EMR_MAX_UNOBSERVED, a latent column listed twice, in no family
+ * or with two cardinalities, any column with two cardinalities, an unknown flag, an observed column >= n_cols
+ * and a window outside ld.  pgm_fit_estep_rows_info needs no device. */
+#define PGM_EMR_NO_FLOOR 1             /* flags: values are taken as they are, a zero stays zero */
+#define PGM_EMR_MAX_UNOBSERVED 32      /* unobserved cells of a row, latents included */
+#define PGM_EMR_MAX_ROW_FAMILIES 128   /* families a row touches */
+#define PGM_EMR_COMPLETE 0
+#define PGM_EMR_MARGINALISED 1
+#define PGM_EMR_SKIPPED 2
+#define PGM_EMR_IMPOSSIBLE 3
+#define PGM_EMR_BAD_CODE 4
+typedef struct {
+  int32_t block, rows_per_block;    /* work-items per workgroup (four waves), rows it takes */
+  int32_t lds_bytes, blocks_per_cu; /* static + dynamic LDS of the launch; workgroups per CU: the fewer of what its registers (3) and its LDS allow */
+  int32_t tile, tile_bins;          /* 1: total_bins <= tile_bins, the tables are privatised in LDS; 0: global atomics */
+  int32_t n_columns, n_latent, n_families, reserved;
+  int32_t max_unobserved, max_configs, max_component_families, max_row_families; /* the caps */
+  int64_t total_bins;
+} pgm_emr_info_t;
+int pgm_fit_estep_rows_info(void *plan, const int32_t *latent_cols, int32_t n_latent, pgm_emr_info_t *info);
+int pgm_fit_estep_rows(void *plan, const int32_t *latent_cols, int32_t n_latent, int32_t flags,
+                       const double *values, const uint8_t *codes, int32_t n_cols, int64_t ld, int64_t row0,
+                       int64_t n_rows, double *tables, double *loglik, uint8_t *status, int64_t *n_skipped,
+                       void *stream);
+
 /* ---------------------------------------------------------------- per-row log-probability
  * (an extension of ABI 25.)  The log-density of complete rows under a Bayesian network, for the reference's
  * BayesianModelProbability (metrics/bn_inference.py:23-148: per node, np.unique(axis=0) over the parent

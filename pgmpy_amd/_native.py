@@ -213,6 +213,18 @@ class EmInfo(ctypes.Structure):
                 ("lds_bytes", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+EMR_NO_FLOOR, EMR_MAX_UNOBSERVED, EMR_MAX_ROW_FAMILIES = 1, 32, 128  # PGM_EMR_*
+EMR_COMPLETE, EMR_MARGINALISED, EMR_SKIPPED, EMR_IMPOSSIBLE, EMR_BAD_CODE = range(5)  # the per-row status
+
+
+class EmrInfo(ctypes.Structure):
+    """pgm_emr_info_t: launch geometry, accumulation tier and caps of a pgm_fit_estep_rows call (host-only query)."""
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        "block", "rows_per_block", "lds_bytes", "blocks_per_cu", "tile", "tile_bins", "n_columns", "n_latent",
+        "n_families", "reserved", "max_unobserved", "max_configs", "max_component_families", "max_row_families")] + [
+        ("total_bins", ctypes.c_int64)]
+
+
 class LogpInfo(ctypes.Structure):
     """pgm_logp_info_t: launch geometry and kernel path of a pgm_fit_logprob call (host-only query)."""
     _fields_ = [("block", ctypes.c_int32), ("rows_per_block", ctypes.c_int32), ("vec4", ctypes.c_int32),
@@ -569,6 +581,10 @@ _SIGS = {
     "pgm_fit_estep_info": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(EmInfo)], ctypes.c_int),
     "pgm_fit_estep": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_int64,
                        ctypes.c_int64, ctypes.c_int64, _P, _P, _P], ctypes.c_int),
+    "pgm_fit_estep_rows_info": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(EmrInfo)], ctypes.c_int),
+    "pgm_fit_estep_rows": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32,
+                            ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, ctypes.POINTER(ctypes.c_int64), _P],
+                           ctypes.c_int),
     "pgm_fit_logprob_info": ([_P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(LogpInfo)],
                              ctypes.c_int),
     "pgm_fit_log_values": ([_P, _P, _P, _P], ctypes.c_int),

@@ -78,6 +78,16 @@ struct PGM_FIT_LOCAL FitPlan {
   int n_cols = 0;  // 1 + the largest code column read
 };
 
+// What the rows E-step (pgm_fit_estep_rows: pgm_emrows.h) reads of a plan beside its families, built by its
+// first call: the plan's code columns ascending, each with its cardinality, and per column the families
+// that hold it (a CSR over the positions of cols; a family that lists a column twice is there once).
+struct EmrLists {
+  std::vector<int32_t> cols, card, inc_off, inc_fam;
+  int32_t two_card = -1;  // first column that two families give two cardinalities, or -1
+  bool built = false;
+  std::mutex mu;  // two first calls on one plan may come from two threads
+};
+
 // the handle behind pgm_fit_plan_create: the plan plus its lazily uploaded device copy (dev owns what the
 // d_* point to and sets them: pgmfit.hip fit_use)
 struct PGM_FIT_LOCAL FitHandle {
@@ -98,11 +108,15 @@ struct PGM_FIT_LOCAL FitHandle {
   // the log-probability stage: one fp64 partial + one int32 count of skipped rows per workgroup
   double *d_logp_part = nullptr;
   int32_t *d_logp_skip = nullptr;
+  // the rows E-step stage: the column lists, and the launch's count of skipped rows
+  EmrLists emr;
+  const int32_t *d_emr_cols = nullptr, *d_emr_card = nullptr, *d_emr_inc_off = nullptr, *d_emr_inc_fam = nullptr;
+  unsigned long long *d_emr_skipped = nullptr;
 };
 
 // The descriptors on the current device, and with a stage what only the score / CI / log-probability
 // launches need (pgmfit.hip; pgmlogp.hip shares it).
-enum { kFitNoStage = -1, kFitScore = 0, kFitCi = 1, kFitLogp = 2 };
+enum { kFitNoStage = -1, kFitScore = 0, kFitCi = 1, kFitLogp = 2, kFitEmRows = 3 };
 PGM_FIT_LOCAL int fit_use(FitHandle *h, int stage = kFitNoStage);
 
 // validate the families and lay the tables out; PGM_OK, or PGM_EINVAL with pgm_last_error set

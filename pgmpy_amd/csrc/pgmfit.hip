@@ -636,6 +636,13 @@ int fit_use(FitHandle *h, int stage) {
     const pgmdev::Slot logp[] = {scratch(h->d_logp_part, (size_t)kLogpMaxBlocks), scratch(h->d_logp_skip, (size_t)kLogpMaxBlocks)};
     return h->dev.use(kHipDevOps, base, stage, logp);
   }
+  if (stage == kFitEmRows) {  // h->emr is built by the entry point's host check (pgmemrows_plan.cpp)
+    const EmrLists &e = h->emr;
+    const pgmdev::Slot emr[] = {upload(h->d_emr_cols, e.cols), upload(h->d_emr_card, e.card),
+                                upload(h->d_emr_inc_off, e.inc_off), upload(h->d_emr_inc_fam, e.inc_fam),
+                                scratch(h->d_emr_skipped, 1)};
+    return h->dev.use(kHipDevOps, base, stage, emr);
+  }
   return h->dev.use(kHipDevOps, base);
 }
 

@@ -12,6 +12,13 @@ iteration; the CPD objects are built once at the end.
 Extensions: `n_iter_` (iterations run) and `log_likelihoods_` (per iteration, the log-likelihood of the data
 under the parameters the iteration started from, with the reference's floor of 1e-10 per CPD entry).
 
+`incomplete="marginalize"` (default "drop", the reference's rule) keeps the rows with a missing cell: the E-step is
+then pgm_fit_estep_rows, which sums each row's missing cells and the latents out per connected component and adds
+the weights to the families that hold one; the integer counts of the families a row leaves untouched are one
+pgm_fit_count before the loop.  A model without latents is accepted when the data have a missing cell, every
+family with a latent or a partially missing column is re-estimated, and `n_skipped_` is the number of rows past
+the kernel's limits (left out, with a warning).
+
 Deviations: this project has no DAG class, its DAGs are CPD-less DiscreteBayesianNetworks; at
 most 8 latent variables with at most 4,096 joint configurations and 32 families with a latent in scope;
 with apply_smoothing the CPDs estimated once get the prior of **kwargs (the reference gives them
@@ -34,13 +41,17 @@ RTOL = 1e-5  # np.allclose's default, which TabularCPD.__eq__(atol=) leaves as i
 
 
 class ExpectationMaximization(ParameterEstimator):
-    def __init__(self, model, data, **kwargs):
+    def __init__(self, model, data, incomplete="drop", **kwargs):
         from ..models import DiscreteBayesianNetwork
 
         if not isinstance(model, DiscreteBayesianNetwork):
             raise NotImplementedError(
                 "Expectation Maximization is only implemented for DAG or DiscreteBayesianNetwork"
             )
+        if incomplete not in ("drop", "marginalize"):
+            raise ValueError(f"incomplete must be 'drop' or 'marginalize'. Got: {incomplete!r}")
+        self.incomplete = incomplete
+        self.n_skipped_ = 0
         # fully missing columns are latents (EM.py:80-91)
         original_cols = set(data.columns)
         data = data.dropna(axis=1, how="all")
@@ -54,7 +65,8 @@ class ExpectationMaximization(ParameterEstimator):
             model.latents.update(new_latents)
         # rows with any missing value are dropped (EM.py:93-102)
         original_rows_count = data.shape[0]
-        data = data.dropna()
+        if incomplete == "drop":
+            data = data.dropna()
         dropped_rows_count = original_rows_count - data.shape[0]
         if dropped_rows_count:
             logger.warning(
@@ -136,7 +148,12 @@ class ExpectationMaximization(ParameterEstimator):
             raise ValueError(f"max_iter must be a positive integer. Got: {max_iter}")
         if not (isinstance(atol, numbers.Real) and atol >= 0):
             raise ValueError(f"atol must be a non-negative number. Got: {atol}")
-        if not latents:
+        data_columns = [v for v in self.variables if v != "_weight"]
+        # incomplete="marginalize": the columns with a missing cell, whose families EM re-estimates too.  Without
+        # one there is nothing to marginalise but the latents, which the lane-per-row kernel does 12 x faster
+        partial = {v for v in data_columns if self.incomplete == "marginalize" and bool(self.data[v].isna().any())}
+        marginalize = bool(partial)
+        if not latents and not partial:
             raise ValueError("The model has no latent variable: use MaximumLikelihoodEstimator or BayesianEstimator")
         if latent_card is None:
             latent_card = {var: 2 for var in latents}
@@ -175,19 +192,22 @@ class ExpectationMaximization(ParameterEstimator):
 
         latent_children = set(chain(*[model.get_children(var) for var in latents]))
         fixed_nodes = [v for v in model.nodes()
-                       if v not in self.model_copy.latents and v not in latent_children and v not in init_cpds]
+                       if v not in self.model_copy.latents and v not in latent_children and v not in init_cpds
+                       and not partial.intersection([v] + model.get_parents(v))]
         em_nodes = [v for v in model.nodes() if v not in fixed_nodes]
         fixed_families, em_families = self._families(fixed_nodes), self._families(em_nodes)
 
         # the code columns: the data's own, then one virtual column per latent
-        data_columns = [v for v in self.variables if v != "_weight"]
         col_of = {v: j for j, v in enumerate(data_columns)}
         latent_cols = []
         for var in latents:
             col_of[var] = len(col_of)
             latent_cols.append(col_of[var])
         plan = FitPlan([self._family(v, ps, col_of) for v, ps in em_families])
-        plan.estep_info(latent_cols)  # the limits of pgm_fit_estep, before any compute
+        if marginalize:
+            plan.estep_rows_info(latent_cols)  # the checks of pgm_fit_estep_rows, before any compute
+        else:
+            plan.estep_info(latent_cols)  # the limits of pgm_fit_estep, before any compute
 
         host = np.empty(plan.total_bins, dtype=np.float64)
         for f, (node, parents) in enumerate(em_families):
@@ -219,9 +239,20 @@ class ExpectationMaximization(ParameterEstimator):
         pseudo = self._pseudo_buffer(plan, em_prior) if apply_smoothing else None
         ll = torch.zeros(int(max_iter), dtype=torch.float64, device=values.device)
         self.n_iter_ = 0
+        if marginalize:
+            # the families a row leaves untouched: exact integer counts, once (a latent's virtual column reads
+            # as missing, so pgm_fit_count leaves its families alone)
+            virtual = torch.full((len(latent_cols), codes.shape[1]), 255, dtype=torch.uint8, device=codes.device)
+            counts = plan.count(torch.cat([codes, virtual]) if latent_cols else codes).to(torch.float64)
+            skipped = 0
         for it in range(int(max_iter)):
-            tables.zero_()
-            _, loglik = plan.estep(latent_cols, values, codes, tables=tables, want_loglik=True)
+            if marginalize:
+                tables.copy_(counts)
+                out = plan.estep_rows(latent_cols, values, codes, tables=tables, want_loglik=True)
+                loglik, skipped = torch.nan_to_num(out["loglik"], nan=0.0, neginf=float("-inf")), out["n_skipped"]
+            else:
+                tables.zero_()
+                _, loglik = plan.estep(latent_cols, values, codes, tables=tables, want_loglik=True)
             plan.finish(tables, pseudo=pseudo, bayes=bool(apply_smoothing), out=new_values)
             ll[it] = loglik.sum()
             # np.allclose(old, new, atol=atol): a NaN never converges
@@ -230,5 +261,10 @@ class ExpectationMaximization(ParameterEstimator):
             self.n_iter_ = it + 1
             if int(download(close.to(torch.uint8).reshape(1))[0]):
                 break
+        if marginalize:
+            self.n_skipped_ = skipped
+            if skipped:
+                logger.warning(f"{skipped} rows with missing values past the limits of the E-step "
+                               "were left out of the expected counts.")
         self.log_likelihoods_ = [float(x) + ll_const for x in download(ll)[:self.n_iter_]]
         return fixed_cpds + self._cpds(plan, em_families, values)

@@ -91,6 +91,45 @@ class FitPlan(Plan):
                                 N.ptr(tables), N.ptr(loglik), N.stream_handle()), "fit_estep")
         return (tables, loglik) if want_loglik else tables
 
+    def estep_rows_info(self, latent_cols=()):
+        """pgm_emr_info_t of a rows E-step over this plan: block, rows per block, LDS bytes, whether the
+        tables are privatised in LDS, and the caps per row.  Needs no device."""
+        L = N.load_library()
+        arr, n = self._latent_array(latent_cols)
+        info = N.EmrInfo()
+        N.check(L.pgm_fit_estep_rows_info(self._h, arr, n, ctypes.byref(info)), "fit_estep_rows_info")
+        return info
+
+    def estep_rows(self, latent_cols, values, codes, n_rows=None, row0=0, tables=None, want_tables=True,
+                   want_loglik=False, want_status=False, no_floor=False):
+        """The E-step on rows with missing cells (pgm_fit_estep_rows) over the rows [row0, row0 + n_rows) of
+        the device codes [n_cols, ld] (uint8): a row's 255 cells and the latent code columns `latent_cols`
+        (virtual, may be empty) are marginalised per connected component, and the posterior weights are
+        added to the fp64 `tables` (a zeroed flat buffer when None; not at all with want_tables=False) of
+        the families that hold an unobserved variable.  The other families add nothing: their share is
+        count()'s.  Returns a dict: tables, loglik (fp64 [ld], NaN outside the window and for skipped
+        rows; with want_loglik), status (uint8 [ld]; with want_status) and n_skipped, the rows past a
+        limit.  Raises IndexError when a code is neither 255 nor a state."""
+        import torch
+
+        L = N.lib()
+        n_cols, ld, n_rows = codes_window(codes, n_rows, row0)
+        flat_tensor("values", values, self.total_bins)
+        if not want_tables:
+            tables = None
+        elif tables is None:
+            tables = torch.zeros(self.total_bins, dtype=torch.float64, device=codes.device)
+        else:
+            flat_tensor("tables", tables, self.total_bins, label="torch.float64")
+        arr, n = self._latent_array(latent_cols)
+        loglik = torch.full((ld,), float("nan"), dtype=torch.float64, device=codes.device) if want_loglik else None
+        status = torch.zeros(ld, dtype=torch.uint8, device=codes.device) if want_status else None
+        skipped = ctypes.c_int64(0)
+        N.check(L.pgm_fit_estep_rows(self._h, arr, n, N.EMR_NO_FLOOR if no_floor else 0, N.ptr(values), N.ptr(codes),
+                                     n_cols, ld, int(row0), n_rows, N.ptr(tables), N.ptr(loglik), N.ptr(status),
+                                     ctypes.byref(skipped), N.stream_handle()), "fit_estep_rows")
+        return {"tables": tables, "loglik": loglik, "status": status, "n_skipped": int(skipped.value)}
+
     def finish(self, counts, pseudo=None, bayes=False, out=None):
         """Every CPD's values from the count tables (+ fp64 pseudo-counts of the same layout): each
         column divided by its sum; MLE (bayes=False) fills an all-zero column uniformly, Bayes keeps

@@ -55,13 +55,13 @@ def _check_model_and_frame(model, data, what):
                          f" {set(model.nodes()) - set(data.columns)}")
 
 
-def log_likelihood_score(model, data):
+def log_likelihood_score(model, data, incomplete="raise"):
     """log P(data | model) (metrics.py:176-219): the reference's checks (the model's type, a DataFrame
     whose columns are the model's nodes, check_model), then BayesianModelProbability(model).score(data):
     one pass over the codes on the device."""
     _check_model_and_frame(model, data, "log_likelihood_score")
     model.check_model()
-    return BayesianModelProbability(model).score(data)
+    return BayesianModelProbability(model).score(data, incomplete=incomplete)
 
 
 def pseudo_log_likelihood(model, data):

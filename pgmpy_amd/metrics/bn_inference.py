@@ -16,10 +16,14 @@ topological order (the reference's own code for that case fails); every CPD colu
 total before the logarithm, as the reference does for the nodes that have parents (it leaves a root's
 values as they are).  There is no CPU path.
 """
+import logging
+
 import networkx as nx
 import numpy as np
 
 from .. import engine as E
+
+logger = logging.getLogger("pgmpy")
 
 
 class BayesianModelProbability:
@@ -48,22 +52,37 @@ class BayesianModelProbability:
             # Each CPD column divided by its total, as the reference's _reduce_marg does (sampling/base.py:98):
             # a column that a file rounded to a sum of 0.9999999 (alarm's HREKG, HRSAT) is a distribution
             # again.  The total is the last running sum the sampler already holds; the entry -> total index
-            # is built once per model.  The quotient is written into the log tables' buffer, then logged in place.
+            # is built once per model.  The quotient is kept beside its logarithm: incomplete="marginalize" multiplies it.
             at = np.empty(plan.total_bins, dtype=np.int64)
             for (_, cards), off, size in zip(plan.families, plan.offsets, plan.sizes):
                 ncol = size // cards[0]
                 at[off:off + size] = off + size - ncol + np.arange(size, dtype=np.int64) % ncol
-            logv = values / cdf[E.to_device_raw(at)]
-            hit = c._logp = (plan, plan.log_values(logv, out=logv))
-        return (c,) + hit
+            norm = values / cdf[E.to_device_raw(at)]
+            hit = c._logp = (plan, plan.log_values(norm), norm)
+        return (c,) + hit[:2]
 
     @E.serialized
-    def log_probability_codes(self, codes, n_rows=None, row0=0):
+    def log_probability_codes(self, codes, n_rows=None, row0=0, incomplete="raise"):
         """(device logp [ld], device total [1]) of the rows [row0, row0 + n_rows) of the device codes
         [n_nodes, ld] (uint8), columns in sorted(model.nodes()) order: what forward_sample_codes and
         GibbsSampling.sample_codes return.  Nothing is encoded, uploaded or downloaded but the status.
-        Raises ValueError when a row holds 255 (missing), IndexError for any other code that is no state."""
+        Raises ValueError when a row holds 255 (missing), IndexError for any other code that is no state.
+        incomplete="marginalize": a row's 255 cells are summed out instead (pgm_fit_estep_rows over every family,
+        values as they are): logp is the exact log P(observed cells), -inf for an impossible row and NaN, with a
+        warning, for a row past the limits of that call; total is the sum of the rows that are not NaN."""
+        import torch
+
+        if incomplete not in ("raise", "marginalize"):
+            raise ValueError(f"incomplete must be 'raise' or 'marginalize'. Got: {incomplete!r}")
         c, plan, logv = self._tables()
+        if incomplete == "marginalize":
+            with c.lock:
+                out = plan.estep_rows([], c._logp[2], codes, n_rows=n_rows, row0=row0, want_tables=False,
+                                      want_loglik=True, no_floor=True)
+            if out["n_skipped"]:
+                logger.warning(f"{out['n_skipped']} rows with missing values past the limits of the E-step "
+                               "have no log-probability (NaN).")
+            return out["loglik"], torch.nansum(out["loglik"]).reshape(1)
         with c.lock:
             logp, total, skipped = plan.logprob(logv, codes, n_rows=n_rows, row0=row0, total=True)
         if skipped:
@@ -92,25 +111,26 @@ class BayesianModelProbability:
             raise ValueError(f"data has no column for the variables {sorted(map(str, missing))}")
         return ingest_states(self.model.states, frame, nodes).codes
 
-    def _run(self, data, ordering):
+    def _run(self, data, ordering, incomplete="raise"):
         codes = self._encode(data, ordering)
         if codes.shape[1] == 0:
             return None, None
-        return self.log_probability_codes(codes)
+        return self.log_probability_codes(codes, incomplete=incomplete)
 
     # ------------------------------------------------------------------ the reference's entry points
-    def log_probability(self, data, ordering=None):
+    def log_probability(self, data, ordering=None, incomplete="raise"):
         """The log-probability of each row: a numpy (n_samples,) array.  `data` is a DataFrame of state
         names (columns in any order), or an array with `ordering` naming its columns (default: the model's
-        topological order).  A category that is not a state raises KeyError."""
+        topological order).  A category that is not a state raises KeyError.  incomplete="marginalize": a row
+        with missing cells gets the log-probability of its observed cells (log_probability_codes)."""
         from ..inference.batch import download
 
-        logp, _ = self._run(data, ordering)
+        logp, _ = self._run(data, ordering, incomplete)
         return np.zeros(0, dtype=np.float64) if logp is None else download(logp)
 
-    def score(self, data, ordering=None):
+    def score(self, data, ordering=None, incomplete="raise"):
         """The total log-probability of the rows: the device's fixed-order sum."""
         from ..inference.batch import download
 
-        _, total = self._run(data, ordering)
+        _, total = self._run(data, ordering, incomplete)
         return 0.0 if total is None else float(download(total)[0])

@@ -285,7 +285,9 @@ class DiscreteBayesianNetwork(nx.DiGraph):
             estimator = MaximumLikelihoodEstimator
         elif not (isinstance(estimator, type) and issubclass(estimator, BaseEstimator)):
             raise TypeError("Estimator object should be a valid pgmpy estimator.")
-        _estimator = estimator(self, data, state_names=state_names)
+        # ExpectationMaximization(incomplete=): what becomes of rows with a missing cell
+        init = {"incomplete": kwargs.pop("incomplete")} if "incomplete" in kwargs else {}
+        _estimator = estimator(self, data, state_names=state_names, **init)
         cpds_list = _estimator.get_parameters(n_jobs=n_jobs, **kwargs)
         self.add_cpds(*cpds_list)
         return self
