@@ -2070,6 +2070,83 @@ int pgm_mnpl_plan_info(void *plan, pgm_mnpl_info_t *info, pgm_fit_family *famili
 int pgm_mnpl_eval(void *plan, const int64_t *counts, const double *theta, double l2, double *value, double *grad,
                   double *node_values, void *stream);
 
+/* ---------------------------------------------------------------- Exact structure search
+ * The highest-scoring DAG over n <= PGM_XS_MAX_NODES nodes under a decomposable score, by the dynamic programme of
+ * Silander and Myllymaki over the subset lattice (csrc/pgmxs.hip).  Nodes are 0 .. n - 1 and a set is a bitmask.
+ * The input is n_fam families (v, P, s): fam_node[f] = v, fam_mask[f] = P, a parent mask without bit v and without a
+ * bit at or above n, fam_score[f] = s, a finite fp64 score or -inf.  A family with s = -inf counts as not given.
+ *
+ * 1. Best parents.  For every v and every S within V \ {v}: Q[v][S] = the maximum of s(v, P) over the given families
+ *    with P within S, and A[v][S] the winning P; (-inf, PGM_XS_NONE) where there is none.  The order is total: the
+ *    larger score, then the fewer parents, then the numerically smaller mask (PGM_XS_NONE, 32 bits, loses to every
+ *    mask).  A maximum over a total order is associative and commutative, so the tables do not depend on how the
+ *    passes are tiled or ordered.
+ * 2. Best sink.  R[empty] = 0, K[empty] = PGM_XS_NONE; R[S] = the maximum over v in S, ascending, of
+ *    R[S \ v] + Q[v][S \ v], one fp64 add each (nothing is multiplied, so nothing can fuse), and K[S] the winning v:
+ *    the larger value, then the smaller v (so a set whose candidates are all -inf keeps its smallest member).
+ * 3. Read-back.  From S = V: v = K[S], parents[v] = A[v][S \ v], S = S \ v, n times.  order[i] is the v of step i
+ *    (a sink first: every parent of order[i] comes later in it); score = R[V]; infeasible = 1 when R[V] = -inf: no
+ *    DAG can be made of the given families, and parents / order then hold the walk along the smallest members.
+ *
+ * Layout.  Q[v] is stored over the index T of S with bit v squeezed out, (S mod 2^v) | (S >> (v + 1)) << v, so a
+ * row has 2^(n-1) cells and cell (v, T) is at v * 2^(n-1) + T; R and K have 2^n cells.  Values are fp64, winners
+ * uint32, in separate arrays.  pgm_xs_run's optional `values` receives Q then R (n * 2^(n-1) + 2^n doubles) and
+ * `winners` A then K in the same order: device buffers of the caller, for tests.
+ *
+ * Kernels.  k_xs_fill and k_xs_scatter put the families into their cells (duplicates were rejected: one writer per
+ * cell).  k_xs_zeta runs the n - 1 passes f[T] = better(f[T], f[T without bit j]) of step 1 through an LDS tile of
+ * 2^tile_log2 cells (value and winner, 12 bytes a cell): one launch does the low min(tile_log2, n - 1) bits on tiles
+ * of consecutive cells, and every further launch does up to high_bits of the remaining bits on a tile of 2^hh
+ * strided groups of 2^(tile_log2 - hh) consecutive cells, with one barrier per pass and one trip through memory per
+ * launch.  k_xs_sink gives a workgroup the 2^tile_log2 sets that share their high bits; their R stays in LDS while
+ * the workgroup walks the popcount layers of the low bits with one barrier per layer, R[S \ v] from LDS for a low v
+ * and from memory for a high one, and the launches go by the popcount of the high part: n - tile_log2 + 1 of them
+ * (one when n <= tile_log2).  Launch order alone carries the dependency: no grid-wide barrier, no waiting on memory.
+ * k_xs_readback is one wave.  Plain stores, no atomic: two runs, or two tilings (pgm_xs_set_tiling: 1 <= high_bits
+ * <= tile_log2 <= 12; the default is 12 and 4), give bit-identical tables.
+ *
+ * pgm_xs_run takes the family arrays and `out` from host memory, checks them on the host before any HIP call, stages
+ * the families, launches on `stream` and synchronises it before it returns (the result record is the only download).
+ * PGM_EINVAL: null handle / out / family arrays, n_fam < 0, a node outside 0 .. n - 1, a mask with bit v or a bit at
+ * or above n, a NaN or +inf score, a (v, P) given twice, a misaligned table pointer; at creation n outside 1 ..
+ * PGM_XS_MAX_NODES; a tiling outside its range.  A failed allocation is PGM_ENOMEM (at 24 nodes Q and A take 2.4 GB,
+ * R and K 0.2 GB).  pgm_xs_create, pgm_xs_info, pgm_xs_set_tiling and pgm_xs_phase_ms need no device.  When a run fails
+ * after its first launch it still synchronises the stream before it returns: nothing enqueued outlives the call.  The handle follows the rules of
+ * the plan handles (the tables belong to it: calls on one handle must not overlap). */
+#define PGM_XS_MAX_NODES 24
+#define PGM_XS_NONE 0xFFFFFFFFu
+#define PGM_XS_PHASES 3 /* pgm_xs_phase_ms: fill and scatter (with the staging copies); the zeta launches; the sink launches */
+typedef struct {
+  double score;       /* R[V] */
+  int32_t infeasible; /* 1: R[V] = -inf */
+  int32_t n;
+  uint32_t parents[PGM_XS_MAX_NODES]; /* the parent mask of every node; PGM_XS_NONE past n */
+  int32_t order[PGM_XS_MAX_NODES];    /* the sinks in the order they were taken; -1 past n */
+} pgm_xs_result_t;
+typedef struct {
+  int32_t n;
+  int32_t tile_log2;       /* L: log2 of the cells of the largest LDS tile */
+  int32_t high_bits;       /* h: high zeta bits per launch */
+  int32_t block;           /* work-items per workgroup: 256 */
+  int32_t zeta_tile_log2;  /* min(L, n - 1) */
+  int32_t sink_tile_log2;  /* min(L, n) */
+  int32_t zeta_low_passes; /* passes of the first zeta launch */
+  int32_t zeta_high_trips; /* ceil((n - 1 - L) / h), or 0 */
+  int32_t zeta_launches;   /* 0 when n = 1 */
+  int32_t sink_launches;   /* n - sink_tile_log2 + 1 */
+  int64_t q_bytes, a_bytes, r_bytes, k_bytes; /* the four tables */
+  int64_t zeta_lds, sink_lds;                 /* LDS bytes of a workgroup */
+} pgm_xs_info_t;
+int pgm_xs_create(int32_t n, void **handle);
+int pgm_xs_destroy(void *handle);
+int pgm_xs_info(void *handle, pgm_xs_info_t *info);
+int pgm_xs_set_tiling(void *handle, int32_t tile_log2, int32_t high_bits);
+int pgm_xs_run(void *handle, const int32_t *fam_node, const uint32_t *fam_mask, const double *fam_score, int64_t n_fam,
+               pgm_xs_result_t *out, double *values, uint32_t *winners, void *stream);
+/* ms [PGM_XS_PHASES]: the device time of each phase of the handle's last completed run, between HIP events that
+ * every run records on its stream; PGM_EINVAL before the first one.  Host only. */
+int pgm_xs_phase_ms(void *handle, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -397,6 +397,27 @@ class MnplInfo(ctypes.Structure):
                 ("n_counts", ctypes.c_int64), ("n_parts", ctypes.c_int64), ("lds_bytes", ctypes.c_int64),
                 ("lds_max", ctypes.c_int64)]
 
+XS_MAX_NODES = 24
+XS_NONE = 0xFFFFFFFF
+XS_PHASES = 3  # pgm_xs_phase_ms: scatter, zeta, sink
+
+
+class XsResult(ctypes.Structure):
+    """pgm_xs_result_t: the best DAG's score, parent masks and sink order."""
+    _fields_ = [("score", ctypes.c_double), ("infeasible", ctypes.c_int32), ("n", ctypes.c_int32),
+                ("parents", ctypes.c_uint32 * XS_MAX_NODES), ("order", ctypes.c_int32 * XS_MAX_NODES)]
+
+
+class XsInfo(ctypes.Structure):
+    """pgm_xs_info_t: the tiling, the launch counts and the table sizes of an exact search (host-only query)."""
+    _fields_ = [("n", ctypes.c_int32), ("tile_log2", ctypes.c_int32), ("high_bits", ctypes.c_int32),
+                ("block", ctypes.c_int32), ("zeta_tile_log2", ctypes.c_int32), ("sink_tile_log2", ctypes.c_int32),
+                ("zeta_low_passes", ctypes.c_int32), ("zeta_high_trips", ctypes.c_int32),
+                ("zeta_launches", ctypes.c_int32), ("sink_launches", ctypes.c_int32), ("q_bytes", ctypes.c_int64),
+                ("a_bytes", ctypes.c_int64), ("r_bytes", ctypes.c_int64), ("k_bytes", ctypes.c_int64),
+                ("zeta_lds", ctypes.c_int64), ("sink_lds", ctypes.c_int64)]
+
+
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
 RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
@@ -706,6 +727,12 @@ _SIGS = {
     "pgm_mnpl_plan_info": ([_P, ctypes.POINTER(MnplInfo), ctypes.POINTER(FitFamily)] + [ctypes.POINTER(ctypes.c_int64)] * 5,
                            ctypes.c_int),
     "pgm_mnpl_eval": ([_P, _P, _P, ctypes.c_double, _P, _P, _P, _P], ctypes.c_int),
+    "pgm_xs_create": ([ctypes.c_int32, ctypes.POINTER(_P)], ctypes.c_int),
+    "pgm_xs_destroy": ([_P], ctypes.c_int),
+    "pgm_xs_info": ([_P, ctypes.POINTER(XsInfo)], ctypes.c_int),
+    "pgm_xs_set_tiling": ([_P, ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
+    "pgm_xs_phase_ms": ([_P, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+    "pgm_xs_run": ([_P, _P, _P, _P, ctypes.c_int64, ctypes.POINTER(XsResult), _P, _P, _P], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

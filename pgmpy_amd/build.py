@@ -47,6 +47,8 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmlbp_plan.cpp",   # Markov-network marginals: scope validation, pairs, incidence lists, table deduplication, LDS layout, argument checks (host only)
     "pgmmnpl.hip",       # Markov-network pseudo-likelihood: the value / residual / gradient-part kernel, the gather kernel, their C-ABI
     "pgmmnpl_plan.cpp",  # Markov-network pseudo-likelihood: scope validation, blanket families, digits, part slots, LDS sizing, argument checks (host only)
+    "pgmxs.hip",         # exact structure search: the scatter, max-zeta, best-sink and read-back kernels of the subset-lattice DP, their C-ABI
+    "pgmxs_plan.cpp",    # exact structure search: tiling, popcount-ordered lists, launch counts, family-list checks (host only)
     "pgmdq.cpp",        # direct AQL dispatch (host code, HSA runtime)
     "pgmpm.cpp",         # plan-specialised batched-BP steps: hipRTC, code-object cache, bound launches (host code)
     "pgmpm_gen.cpp",     # plan-specialised batched-BP steps: planner + generators of the specialised sources (host only)

@@ -13,7 +13,7 @@ get_callable_ci_test, CITester) and PC (orig / stable / parallel; a PDAG from pg
 ExpectationMaximization (every row complete in its observed columns); TreeSearch (Chow-Liu and TAN: the
 tables of every pair of columns from one int8 MFMA launch, pgm_pair_count, and the pair statistics from
 pgm_pair_mi / pgm_pair_emi).  Not built: MarginalEstimator / IPF
-(MaximumLikelihoodEstimator on a JunctionTree), GES, MMHC, ExhaustiveSearch, the mixed CI
+(MaximumLikelihoodEstimator on a JunctionTree), GES, MMHC, the mixed CI
 tests (gcm, pillai) and independence_match (DESIGN.md).
 
 Continuous data: CITests.pearsonr / GaussCITester (partial correlations) and LogLikelihoodGauss, BICGauss,
@@ -29,6 +29,10 @@ launch (pgm_cg_moments, pgm_cg_score); HillClimbSearch takes an instance.
 Markov networks: PseudoLikelihoodEstimator fits the potentials by maximum pseudo-likelihood: one count launch on the
 nodes' blanket families, then one launch pair per evaluation of the objective and its gradient on the count tables
 (pgm_mnpl_eval) under L-BFGS.
+
+Exact search: ExhaustiveSearch returns the highest-scoring DAG over up to 24 variables.  The families are scored in
+batches by any StructureScore; the dynamic programme over the subset lattice (best parents by a max-zeta transform
+through LDS tiles, best sinks by popcount layers, a read-back walk) runs on the device (pgm_xs_run).
 """
 from .base import BaseEstimator, ParameterEstimator
 from .MLE import MaximumLikelihoodEstimator
@@ -42,9 +46,11 @@ from .PC import PC
 from .EM import ExpectationMaximization
 from .TreeSearch import TreeSearch
 from .PseudoLikelihood import PseudoLikelihoodEstimator
+from .ExhaustiveSearch import ExhaustiveSearch
 
 __all__ = ["BaseEstimator", "ParameterEstimator", "MaximumLikelihoodEstimator", "BayesianEstimator",
            "StructureScore", "K2", "BDeu", "BDs", "LogLikeliHood", "BIC", "AIC", "get_scoring_method",
            "LogLikelihoodGauss", "BICGauss", "AICGauss", "LogLikelihoodCondGauss", "BICCondGauss", "AICCondGauss",
            "HillClimbSearch", "ExpertKnowledge", "CITests", "CITester",
-           "GaussCITester", "PC", "ExpectationMaximization", "TreeSearch", "PseudoLikelihoodEstimator"]
+           "GaussCITester", "PC", "ExpectationMaximization", "TreeSearch", "PseudoLikelihoodEstimator",
+           "ExhaustiveSearch"]
