@@ -2147,6 +2147,100 @@ int pgm_xs_run(void *handle, const int32_t *fam_node, const uint32_t *fam_mask, 
  * every run records on its stream; PGM_EINVAL before the first one.  Host only. */
 int pgm_xs_phase_ms(void *handle, double *ms);
 
+/* ---------------------------------------------------------------- Junction-tree potentials by mirror descent
+ * The log-potentials theta of the cliques of a junction tree, fitted so that chosen low-order marginals of the tree's
+ * distribution match measured vectors y, by entropic mirror descent (McKenna, Sheldon and Miklau 2019, Appendix A.1)
+ * for a batch of instances in ONE launch (csrc/pgmmd.hip k_md): every iteration, every line-search trial and the
+ * calibration of every trial.  An instance is a row of targets with its total n; the tree is shared.
+ *
+ * A plan is made from the variables' cardinalities, the cliques (1 to PGM_MD_MAX_VARS distinct variables each,
+ * clique_vars [n_cliques][PGM_MD_MAX_VARS]; clique i's table is C-ordered in that order at clique_off[i] of a row of
+ * n_cells), the n_cliques - 1 edges of the tree (pairs of clique indices; the running-intersection property is the
+ * caller's) and the marginals' scopes (marginal_vars [n_marginals][PGM_MD_MAX_VARS]; marginal j is C-ordered in its
+ * own order at y_off[j] of a row of n_y).  The tree is rooted at clique 0, breadth first in the order of the edge list.
+ * The separator of a clique and its parent holds their shared variables in the child's order.  Marginal j belongs to
+ * the first clique that holds its scope.
+ *
+ * CALIBRATION of theta, in log space (LSE = log sum exp, maximum first): from the deepest level up, m_up(c)(s) = LSE
+ * over the cells of c that share s of [theta_c + the up messages of c's children]; log Z = LSE of the root's sum; from
+ * the root down, m_down(c)(s) = LSE over the cells of c's parent p that share s of [theta_p + every message into p
+ * but c's own]; b_i = theta_i + every message into i; mu_i = exp(b_i + log n - log Z).  mu2_j = the sum of mu over
+ * the cells of j's clique that share a cell of j, d_j = mu2_j - y_j.  PGM_MD_L2: loss = sum 1/2 d^2, g = d.
+ * PGM_MD_L1: loss = sum |d|, g = sign(d), sign(0) = 0.  dL_c(x) = the sum over c's marginals, in their order, of g_j
+ * at x's cell of j.
+ *
+ * THE LOOP, in the three step modes the reference's `stepsize` argument has.  PGM_MD_STEP_FIXED (a float): alpha =
+ * stepsize, any finite value, 0 and negative ones included, and no line search.  PGM_MD_STEP_SEARCH (None): alpha =
+ * 1 / n^2 and the line search.  PGM_MD_STEP_DEFAULT (anything else): alpha = 1 / n^2 and no line search; stepsize is
+ * not read in the last two.  The start is calibrated once.  An iteration: alpha *= 2 (line search only); a trial is
+ * theta = omega - alpha dL, its calibration and its loss; it is accepted without a line search, or when loss(omega) -
+ * loss(theta) >= 1/2 alpha sum_j g_j . (nu2_j - mu2_j) (nu2: the marginals at omega); a rejected trial halves alpha;
+ * after PGM_MD_TRIALS rejected trials the last one is kept all the same (and alpha has been halved once more).
+ *
+ * MAPPING.  One workgroup of 256 work-items per instance.  A phase of a calibration is one item list over all the
+ * edges of a tree level (or all the marginals): an output cell whose residual set has 64 cells or more is reduced by
+ * a whole wave (lane l takes cells l, l + 64, .., a butterfly joins them), a smaller one by one work-item in ascending
+ * order.  Loss and dot product: work-item l adds cells l, l + 256, .., a butterfly per wave, the four wave totals in
+ * wave order.  A result depends on the instance alone.  PGM_MD_TIER_LDS: omega, the trial log-beliefs, both message
+ * arrays and the vectors y, g, nu2, mu2 live in LDS for the whole run (lds_bytes <= lds_max).  PGM_MD_TIER_GLOBAL:
+ * the first four live in the instance's slice of `scratch` [n_rows][scratch_len], the vectors and the pad in LDS.
+ * The plan picks the LDS tier when it fits; pgm_md_set_tier forces one (tests) or goes back to automatic.
+ *
+ * pgm_md_run: targets [n_rows][n_y], totals [n_rows] (> 0), theta_in [theta_rows][n_cells] with theta_rows 1 (shared)
+ * or n_rows, all finite; out: theta_out and mu_out [n_rows][n_cells], values [n_rows][PGM_MD_VALUES] (the loss, the
+ * final alpha), trials [n_rows][2] (trials taken, trials rejected).  All device memory.  Checked on the host before
+ * any HIP call (PGM_EINVAL): at plan creation no variable / clique / marginal, a clique or marginal of 0 or more than
+ * PGM_MD_MAX_VARS variables, a variable out of range or listed twice, a cardinality outside 1 .. 254, edges that are
+ * no tree over the cliques, a marginal no clique holds, a clique, a marginal or all tables together of more than
+ * 2^30 - 1 cells (checked before the product is formed), vectors past lds_max; a tier outside 0 .. 2 or an LDS tier
+ * that does not fit; at the run null pointers, a negative count, theta_rows other than 1 or n_rows, another metric, a
+ * step mode outside 0 .. 2, a NaN or infinite step size in PGM_MD_STEP_FIXED, the global tier without scratch, a
+ * misaligned pointer.  The plan's item list takes 4 bytes per separator and marginal cell (PGM_ENOMEM when the host
+ * cannot hold it).  n_rows = 0 is PGM_OK and launches nothing.  pgm_md_plan_create,
+ * pgm_md_plan_info and pgm_md_set_tier need no device.  The handle follows the rules of the plan handles. */
+#define PGM_MD_MAX_VARS 8
+#define PGM_MD_TRIALS 25
+#define PGM_MD_VALUES 2
+#define PGM_MD_L1 1
+#define PGM_MD_L2 2
+#define PGM_MD_STEP_FIXED 0
+#define PGM_MD_STEP_SEARCH 1
+#define PGM_MD_STEP_DEFAULT 2
+#define PGM_MD_TIER_AUTO 0
+#define PGM_MD_TIER_LDS 1
+#define PGM_MD_TIER_GLOBAL 2
+typedef struct {
+  int32_t n_vars;
+  int32_t n_cliques;
+  int32_t n_edges;
+  int32_t n_marginals;
+  int32_t depth;       /* the deepest level; the root is level 0 */
+  int32_t tier;        /* PGM_MD_TIER_LDS or PGM_MD_TIER_GLOBAL: what a run would use */
+  int32_t block;       /* work-items per workgroup: 256 */
+  int32_t n_phases;    /* barrier-separated phases of a calibration */
+  int64_t n_cells;     /* table cells of all cliques: a row of theta and of mu */
+  int64_t n_sep;       /* separator cells of all edges */
+  int64_t n_y;         /* cells of all marginals: a row of targets */
+  int64_t state_len;   /* 2 (n_cells + n_sep) */
+  int64_t scratch_len; /* fp64 per instance of the scratch slab: state_len in the global tier, else 0 */
+  int64_t lds_bytes;   /* LDS of a workgroup */
+  int64_t lds_max;     /* the most a workgroup may have */
+} pgm_md_info_t;
+int pgm_md_plan_create(const int32_t *card, int32_t n_vars, const int32_t *clique_nvars, const int32_t *clique_vars,
+                       int32_t n_cliques, const int32_t *edges, int32_t n_edges, const int32_t *marginal_nvars,
+                       const int32_t *marginal_vars, int32_t n_marginals, void **plan);
+int pgm_md_plan_destroy(void *plan);
+/* clique_off, sep_off [n_cliques + 1] (sep_off by child clique; the root has no cells); parent, level [n_cliques]
+ * (parent -1 at the root); sep_strides [n_cliques][2][PGM_MD_MAX_VARS]: the separator's variables' strides in the
+ * child's table and in the parent's; owner [n_marginals]; y_off [n_marginals + 1]; marginal_strides [n_marginals]
+ * [PGM_MD_MAX_VARS]: in the owner's table.  Any output may be NULL */
+int pgm_md_plan_info(void *plan, pgm_md_info_t *info, int32_t *clique_off, int32_t *parent, int32_t *level,
+                     int32_t *sep_off, int32_t *sep_strides, int32_t *owner, int32_t *y_off, int32_t *marginal_strides);
+int pgm_md_set_tier(void *plan, int32_t tier);
+int pgm_md_run(void *plan, const double *targets, const double *totals, const double *theta_in, int64_t theta_rows,
+               int64_t n_rows, int32_t metric, int32_t iterations, double stepsize, int32_t step_mode, double *scratch,
+               double *theta_out, double *mu_out, double *values, int32_t *trials, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -418,6 +418,19 @@ class XsInfo(ctypes.Structure):
                 ("zeta_lds", ctypes.c_int64), ("sink_lds", ctypes.c_int64)]
 
 
+class MdInfo(ctypes.Structure):
+    """pgm_md_info_t: the sizes, the tier and the LDS of a mirror-descent plan (host-only query)."""
+    _fields_ = [("n_vars", ctypes.c_int32), ("n_cliques", ctypes.c_int32), ("n_edges", ctypes.c_int32),
+                ("n_marginals", ctypes.c_int32), ("depth", ctypes.c_int32), ("tier", ctypes.c_int32),
+                ("block", ctypes.c_int32), ("n_phases", ctypes.c_int32), ("n_cells", ctypes.c_int64),
+                ("n_sep", ctypes.c_int64), ("n_y", ctypes.c_int64), ("state_len", ctypes.c_int64),
+                ("scratch_len", ctypes.c_int64), ("lds_bytes", ctypes.c_int64), ("lds_max", ctypes.c_int64)]
+
+
+# PGM_MD_*: variables of a clique, values per instance, the metrics, the tiers, the step modes
+MD_MAX_VARS, MD_VALUES, MD_L1, MD_L2, MD_TIER_AUTO, MD_TIER_LDS, MD_TIER_GLOBAL = 8, 2, 1, 2, 0, 1, 2
+MD_STEP_FIXED, MD_STEP_SEARCH, MD_STEP_DEFAULT = 0, 1, 2
+
 _P = ctypes.c_void_p
 RK_NONE, RK_JIT, RK_JIT2, RK_AFFINE, RK_TABLE = -1, 0, 1, 2, 3  # enum pgm_rows_kernel
 RK_NAMES = {RK_NONE: "NONE", RK_JIT: "JIT", RK_JIT2: "JIT2", RK_AFFINE: "AFFINE", RK_TABLE: "TABLE"}
@@ -733,6 +746,15 @@ _SIGS = {
     "pgm_xs_set_tiling": ([_P, ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
     "pgm_xs_phase_ms": ([_P, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
     "pgm_xs_run": ([_P, _P, _P, _P, ctypes.c_int64, ctypes.POINTER(XsResult), _P, _P, _P], ctypes.c_int),
+    "pgm_md_plan_create": ([ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                            ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(_P)],
+                           ctypes.c_int),
+    "pgm_md_plan_destroy": ([_P], ctypes.c_int),
+    "pgm_md_plan_info": ([_P, ctypes.POINTER(MdInfo)] + [ctypes.POINTER(ctypes.c_int32)] * 8, ctypes.c_int),
+    "pgm_md_set_tier": ([_P, ctypes.c_int32], ctypes.c_int),
+    "pgm_md_run": ([_P, _P, _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                    ctypes.c_int32, _P, _P, _P, _P, _P, _P], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -49,6 +49,8 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmmnpl_plan.cpp",  # Markov-network pseudo-likelihood: scope validation, blanket families, digits, part slots, LDS sizing, argument checks (host only)
     "pgmxs.hip",         # exact structure search: the scatter, max-zeta, best-sink and read-back kernels of the subset-lattice DP, their C-ABI
     "pgmxs_plan.cpp",    # exact structure search: tiling, popcount-ordered lists, launch counts, family-list checks (host only)
+    "pgmmd.hip",         # junction-tree potentials by mirror descent: the fused optimisation kernel with its log-space calibration, its C-ABI
+    "pgmmd_plan.cpp",    # junction-tree potentials: clique / tree / marginal validation, levels, jobs, projections, item lists, tier, argument checks (host only)
     "pgmdq.cpp",        # direct AQL dispatch (host code, HSA runtime)
     "pgmpm.cpp",         # plan-specialised batched-BP steps: hipRTC, code-object cache, bound launches (host code)
     "pgmpm_gen.cpp",     # plan-specialised batched-BP steps: planner + generators of the specialised sources (host only)

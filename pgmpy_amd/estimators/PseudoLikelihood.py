@@ -1,6 +1,7 @@
 """PseudoLikelihoodEstimator: the potentials of a DiscreteMarkovNetwork from data, by maximum pseudo-likelihood.
 
-The reference's only undirected learner (MirrorDescentEstimator) needs a junction tree; Besag's pseudo-likelihood
+The reference's undirected learner (MirrorDescentEstimator, built here too) needs a junction tree; Besag's
+pseudo-likelihood
 
     PL(theta) = sum_rows sum_i log p(x_i | x_MB(i); theta),   p(x_i = s | .) prop. to exp sum_{f holds i} theta_f(s, x_{f\\i})
 

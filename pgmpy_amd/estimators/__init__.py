@@ -12,7 +12,7 @@ forbidden edges); CITests (chi_square, g_sq, log_likelihood, modified_log_likeli
 get_callable_ci_test, CITester) and PC (orig / stable / parallel; a PDAG from pgmpy_amd.base);
 ExpectationMaximization (every row complete in its observed columns); TreeSearch (Chow-Liu and TAN: the
 tables of every pair of columns from one int8 MFMA launch, pgm_pair_count, and the pair statistics from
-pgm_pair_mi / pgm_pair_emi).  Not built: MarginalEstimator / IPF
+pgm_pair_mi / pgm_pair_emi); MarginalEstimator and MirrorDescentEstimator (below).  Not built: IPF
 (MaximumLikelihoodEstimator on a JunctionTree), GES, MMHC, the mixed CI
 tests (gcm, pillai) and independence_match (DESIGN.md).
 
@@ -30,11 +30,15 @@ Markov networks: PseudoLikelihoodEstimator fits the potentials by maximum pseudo
 nodes' blanket families, then one launch pair per evaluation of the objective and its gradient on the count tables
 (pgm_mnpl_eval) under L-BFGS.
 
+Junction trees: MirrorDescentEstimator (on the MarginalEstimator base) fits the clique potentials so that chosen
+marginals match the data, or a batch of measured marginal vectors: every iteration, line-search trial and log-space
+calibration of the entropic mirror descent runs in one launch, one workgroup per row of targets (pgm_md_run).
+
 Exact search: ExhaustiveSearch returns the highest-scoring DAG over up to 24 variables.  The families are scored in
 batches by any StructureScore; the dynamic programme over the subset lattice (best parents by a max-zeta transform
 through LDS tiles, best sinks by popcount layers, a read-back walk) runs on the device (pgm_xs_run).
 """
-from .base import BaseEstimator, ParameterEstimator
+from .base import BaseEstimator, MarginalEstimator, ParameterEstimator
 from .MLE import MaximumLikelihoodEstimator
 from .BayesianEstimator import BayesianEstimator
 from .StructureScore import (AIC, BIC, K2, AICCondGauss, AICGauss, BDeu, BDs, BICCondGauss, BICGauss, LogLikeliHood,
@@ -47,8 +51,10 @@ from .EM import ExpectationMaximization
 from .TreeSearch import TreeSearch
 from .PseudoLikelihood import PseudoLikelihoodEstimator
 from .ExhaustiveSearch import ExhaustiveSearch
+from .MirrorDescentEstimator import MirrorDescentEstimator
 
 __all__ = ["BaseEstimator", "ParameterEstimator", "MaximumLikelihoodEstimator", "BayesianEstimator",
+           "MarginalEstimator", "MirrorDescentEstimator",
            "StructureScore", "K2", "BDeu", "BDs", "LogLikeliHood", "BIC", "AIC", "get_scoring_method",
            "LogLikelihoodGauss", "BICGauss", "AICGauss", "LogLikelihoodCondGauss", "BICCondGauss", "AICCondGauss",
            "HillClimbSearch", "ExpertKnowledge", "CITests", "CITester",

@@ -176,6 +176,69 @@ class BaseEstimator(object):
         return P.weight_matrix(len(variables), values)
 
 
+class MarginalEstimator(BaseEstimator):
+    """Base of the estimators that fit a junction tree to marginals of the data (base.py:300-427): the junction tree
+    of `model` (through BeliefPropagation, as the reference holds it) and the fitted log-potentials `theta`.  The
+    loss and gradient below are the reference's host API; MirrorDescentEstimator's optimisation does not call them
+    (it runs in one launch of k_md)."""
+
+    def __init__(self, model, data, **kwargs):
+        from ..inference import BeliefPropagation
+
+        super().__init__(data, **kwargs)
+        self.belief_propagation = BeliefPropagation(model=model)
+        self.theta = None
+
+    @staticmethod
+    def _clique_to_marginal(marginals, clique_nodes):
+        """{clique: [marginal factors]}: every marginal goes to the first clique that holds its scope."""
+        from collections import defaultdict
+
+        clique_to_marginal = defaultdict(lambda: [])
+        for marginal_clique, marginal in marginals.items():
+            for clique in clique_nodes:
+                if set(marginal_clique) <= set(clique):
+                    clique_to_marginal[clique].append(marginal)
+                    break
+            else:
+                raise ValueError("Could not find a corresponding clique for" + f" marginal: {marginal_clique}"
+                                 + f" out of cliques: {clique_nodes}")
+        return clique_to_marginal
+
+    def _marginal_loss(self, marginals, clique_to_marginal, metric):
+        """(loss, FactorDict of its gradient in the clique beliefs) of the clique beliefs `marginals` against the
+        measured marginals of `clique_to_marginal`, on the host."""
+        from ..factors import FactorDict
+        from ..factors.discrete import DiscreteFactor
+
+        loss, gradient = 0.0, FactorDict({})
+        for clique, mu in marginals.items():
+            values, grad = np.asarray(mu.values), np.zeros(tuple(int(c) for c in mu.cardinality))
+            for y in clique_to_marginal[clique]:
+                axes = [mu.variables.index(v) for v in y.variables]
+                rest = tuple(a for a in range(values.ndim) if a not in axes)
+                mu2 = np.transpose(values.sum(axis=rest), np.argsort(np.argsort(axes)))  # y's variable order
+                diff = mu2 - np.asarray(y.values)
+                if metric == "L1":
+                    loss += float(np.abs(diff).sum())
+                    g = np.sign(diff)
+                elif metric == "L2":
+                    loss += 0.5 * float((diff * diff).sum())
+                    g = diff
+                else:
+                    raise ValueError("Metric must be one of L1 or L2.")
+                shape = [1] * values.ndim
+                for a, n in zip(axes, g.shape):
+                    shape[a] = n
+                grad = grad + np.transpose(g, np.argsort(axes)).reshape(shape)
+            gradient[clique] = DiscreteFactor(list(mu.variables), [int(c) for c in mu.cardinality], grad,
+                                              state_names={v: list(mu.state_names[v]) for v in mu.variables})
+        return loss, gradient
+
+    def estimate(self):
+        pass
+
+
 class ParameterEstimator(BaseEstimator):
     def __init__(self, model, data, **kwargs):
         self.model = model

@@ -1,4 +1,5 @@
 from .base import BaseFactor, factor_divide, factor_product, factor_sum_product
 from .continuous import LinearGaussianCPD
+from .FactorDict import FactorDict
 
-__all__ = ["BaseFactor", "factor_product", "factor_sum_product", "factor_divide", "LinearGaussianCPD"]
+__all__ = ["BaseFactor", "factor_product", "factor_sum_product", "factor_divide", "LinearGaussianCPD", "FactorDict"]
