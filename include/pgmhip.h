@@ -2144,8 +2144,53 @@ int pgm_xs_set_tiling(void *handle, int32_t tile_log2, int32_t high_bits);
 int pgm_xs_run(void *handle, const int32_t *fam_node, const uint32_t *fam_mask, const double *fam_score, int64_t n_fam,
                pgm_xs_result_t *out, double *values, uint32_t *winners, void *stream);
 /* ms [PGM_XS_PHASES]: the device time of each phase of the handle's last completed run, between HIP events that
- * every run records on its stream; PGM_EINVAL before the first one.  Host only. */
+ * every run records on its stream; PGM_EINVAL before the first one.  Host only.  (When the last completed call was
+ * pgm_xs_posterior, below, ms must hold PGM_XS_POST_PHASES numbers.) */
 int pgm_xs_phase_ms(void *handle, double *ms);
+
+/* Exact edge posteriors (Koivisto and Sood), on the handle and the lattice of the search, with a sum where the search
+ * has a maximum.  The inputs are pgm_xs_run's: n nodes and families (v, P, s_v(P)); a family that is absent or given
+ * with -inf has weight 0.  Every table is fp64 natural logs; lse is the log of a sum of exponentials, built from
+ * lse2(a, b) = max(a, b) + log1p(exp(-|a - b|)), which is the other operand when one is -inf and -inf for two of them
+ * (never NaN).
+ *
+ * 1. alpha[v][S] = lse over the given P within S of s_v(P), for S within V \ {v}; stored as Q is (bit v squeezed out,
+ *    2^(n-1) cells a row).  The passes run over the row's bits in ascending order, hi = lse2(hi, lo).
+ * 2. Forward.  F[empty] = 0; F[S] = lse over v in S, ascending, of alpha[v][S \ v] + F[S \ v].  log Z = F[V].
+ * 3. Backward.  B[empty] = 0; B[T] = lse over v in T, ascending, of alpha[v][V \ T] + B[T \ v].  B[V] = F[V] up to
+ *    rounding; both are returned.
+ * 4. gamma[v][S] = F[S] + B[V \ S \ {v}] for S within V \ {v}: the weight of every order in which the nodes before v
+ *    are exactly S, without v's own term.
+ * 5. Gamma[v][P] = lse over S with P within S within V \ {v} of gamma[v][S]: the passes in ascending order of the
+ *    row's bits, lo = lse2(lo, hi).
+ * 6. post(u -> v) = the sum over the given families (v, P) with u in P of exp(s_v(P) + Gamma[v][P] - log Z), and
+ *    mass[v] the same sum over all of v's families, which is 1 up to rounding.
+ *
+ * This is the posterior under the order-modular prior: uniform over the n! linear orders, times whatever prior the
+ * family scores carry, so a DAG consistent with more orders weighs more than under a uniform prior over DAGs.
+ *
+ * Kernels.  k_xsp_zeta is k_xs_zeta's geometry (the handle's tiling, one barrier per pass) on 8-byte cells, 32 KiB of
+ * LDS at tile_log2 = 12, in either direction.  k_xsp_paths is k_xs_sink's geometry with a running lse2 over the
+ * candidates; F and B share its launches (blockIdx.y).  Steps 4 to 6 take post_rows = min(n, 2^23 >> (n - 1)) rows
+ * at a time through one workspace (64 MiB at most; no second lattice table): k_xsp_gamma fills the rows, k_xsp_zeta
+ * runs the superset sums, and k_xsp_edges, one workgroup of 256 per node v, reads Gamma at v's families only:
+ * work-item l takes the families l, l + 256, ... of v in ascending order of their cell, a butterfly adds the 64 lanes
+ * of a wave, and the four wave totals are added in wave order.  No atomic, and every cell's operations come in an
+ * order that the tiling does not touch: two runs, or two tilings, give bit-identical outputs.
+ *
+ * pgm_xs_posterior checks its arguments as pgm_xs_run does (host memory, before any HIP call, the same PGM_EINVAL
+ * cases; edge_post, log_z, mass and infeasible must not be null), launches on `stream` and synchronises it.  It writes
+ * edge_post [n][n] (row = parent u, column = child v; the diagonal is 0), log_z [2] = F[V], B[V], mass [n], and
+ * *infeasible = 1 when F[V] = -inf: no order admits a DAG, and edge_post and mass are then NaN.  The optional `values`
+ * (a device buffer of the caller, for tests) receives alpha, F, B: n * 2^(n-1) + 2 * 2^n doubles.  The device holds
+ * alpha and F where a search holds Q and R (the same allocations), B, the workspace and the staged families (16 bytes
+ * each, allocated per call): 1.9 GB at 24 nodes, against the search's 2.6 GB; a failed allocation is PGM_ENOMEM.
+ * After it pgm_xs_phase_ms writes PGM_XS_POST_PHASES numbers: fill and scatter; the alpha passes; F and B; steps 4 to
+ * 6.  After pgm_xs_run it writes PGM_XS_PHASES, as before. */
+#define PGM_XS_POST_PHASES 4
+int pgm_xs_posterior(void *handle, const int32_t *fam_node, const uint32_t *fam_mask, const double *fam_score,
+                     int64_t n_fam, double *edge_post, double *log_z, double *mass, int32_t *infeasible, double *values,
+                     void *stream);
 
 /* ---------------------------------------------------------------- Junction-tree potentials by mirror descent
  * The log-potentials theta of the cliques of a junction tree, fitted so that chosen low-order marginals of the tree's

@@ -400,6 +400,7 @@ class MnplInfo(ctypes.Structure):
 XS_MAX_NODES = 24
 XS_NONE = 0xFFFFFFFF
 XS_PHASES = 3  # pgm_xs_phase_ms: scatter, zeta, sink
+XS_POST_PHASES = 4  # after pgm_xs_posterior: scatter, alpha, paths, edges
 
 
 class XsResult(ctypes.Structure):
@@ -746,6 +747,7 @@ _SIGS = {
     "pgm_xs_set_tiling": ([_P, ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
     "pgm_xs_phase_ms": ([_P, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
     "pgm_xs_run": ([_P, _P, _P, _P, ctypes.c_int64, ctypes.POINTER(XsResult), _P, _P, _P], ctypes.c_int),
+    "pgm_xs_posterior": ([_P, _P, _P, _P, ctypes.c_int64, _P, _P, _P, ctypes.POINTER(ctypes.c_int32), _P, _P], ctypes.c_int),
     "pgm_md_plan_create": ([ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                             ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(_P)],

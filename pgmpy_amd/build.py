@@ -47,7 +47,7 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "pgmlbp_plan.cpp",   # Markov-network marginals: scope validation, pairs, incidence lists, table deduplication, LDS layout, argument checks (host only)
     "pgmmnpl.hip",       # Markov-network pseudo-likelihood: the value / residual / gradient-part kernel, the gather kernel, their C-ABI
     "pgmmnpl_plan.cpp",  # Markov-network pseudo-likelihood: scope validation, blanket families, digits, part slots, LDS sizing, argument checks (host only)
-    "pgmxs.hip",         # exact structure search: the scatter, max-zeta, best-sink and read-back kernels of the subset-lattice DP, their C-ABI
+    "pgmxs.hip",         # exact structure search: the scatter, max-zeta, best-sink and read-back kernels of the subset-lattice DP, the log-space kernels of the edge posteriors, their C-ABI
     "pgmxs_plan.cpp",    # exact structure search: tiling, popcount-ordered lists, launch counts, family-list checks (host only)
     "pgmmd.hip",         # junction-tree potentials by mirror descent: the fused optimisation kernel with its log-space calibration, its C-ABI
     "pgmmd_plan.cpp",    # junction-tree potentials: clique / tree / marginal validation, levels, jobs, projections, item lists, tier, argument checks (host only)

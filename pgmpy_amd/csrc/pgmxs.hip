@@ -8,6 +8,12 @@
 // (tiling, lists, launch counts, checks, pgm_xs_create, pgm_xs_info) is pgmxs_plan.cpp.  Compares and single fp64
 // adds only: no matrix instruction has anything to multiply, no atomic, and launch order alone carries the
 // dependencies (no grid-wide barrier, no waiting on memory).
+//
+// On the same handle, lists and tiling, the exact edge posteriors (include/pgmhip.h "Exact edge posteriors";
+// pgm_xs_posterior): the lattice with a log-sum-exp where the search has a maximum.  k_xsp_zeta (subset and superset
+// sums of 8-byte cells through the same LDS tiles), k_xsp_paths (the forward and backward path sums F and B by popcount
+// layers), k_xsp_gamma and k_xsp_edges (a few rows of gamma at a time, and a fixed-order reduction of the listed
+// families into a column of the n x n matrix).  fp64 exp and log1p; still no matrix instruction and no atomic.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -144,18 +150,24 @@ __global__ __launch_bounds__(64) void k_xs_readback(const uint32_t *a, const dou
 }
 
 // ---------------------------------------------------------------------------- the handle's device side
-static int xs_use(XsHandle *h) {
+// The base serves both entry points (the value tables, the lists, the staging of a chunk); stage 0 is the winners of a
+// search, stage 1 what only a posterior needs.
+static int xs_use(XsHandle *h, bool posterior) {
   const XsPlan &p = h->p;
-  const pgmdev::Slot base[] = {pgmdev::scratch(h->d_q, (size_t)p.q_cells),     pgmdev::scratch(h->d_a, (size_t)p.q_cells),
-                               pgmdev::scratch(h->d_r, (size_t)p.r_cells),     pgmdev::scratch(h->d_k, (size_t)p.r_cells),
+  const pgmdev::Slot base[] = {pgmdev::scratch(h->d_q, (size_t)p.q_cells),     pgmdev::scratch(h->d_r, (size_t)p.r_cells),
                                pgmdev::upload(h->d_hi_list, p.hi_list),        pgmdev::upload(h->d_lo_list, p.lo_list),
                                pgmdev::scratch(h->d_fam_cell, (size_t)kXsChunk), pgmdev::scratch(h->d_fam_mask, (size_t)kXsChunk),
                                pgmdev::scratch(h->d_fam_score, (size_t)kXsChunk), pgmdev::scratch(h->d_rec, 1)};
-  return h->dev.use(kHipDevOps, base);
+  if (posterior) {
+    const pgmdev::Slot post[] = {pgmdev::scratch(h->d_b, (size_t)p.r_cells), pgmdev::scratch(h->d_g, (size_t)p.post_rows << p.W),
+                                 pgmdev::scratch(h->d_post, (size_t)(p.n * p.n + p.n + 2))};
+    return h->dev.use(kHipDevOps, base, 1, post);
+  }
+  const pgmdev::Slot search[] = {pgmdev::scratch(h->d_a, (size_t)p.q_cells), pgmdev::scratch(h->d_k, (size_t)p.r_cells)};
+  return h->dev.use(kHipDevOps, base, 0, search);
 }
 
-// the four events of a run (start, after the scatter, after the zeta launches, after the sink launches), made on the
-// handle's device by the first run there
+// the events of a run (start, then the end of each phase), made on the handle's device by the first run there
 static int xs_events(XsHandle *h) {
   if (h->ev_device == h->dev.device()) return PGM_OK;
   for (void *&e : h->ev) {
@@ -231,6 +243,235 @@ static int xs_enqueue(XsHandle *h, const std::vector<uint32_t> &cell, const std:
   return PGM_OK;
 }
 
+// ---------------------------------------------------------------------------- edge posteriors: the same lattice in log space
+// include/pgmhip.h "Exact edge posteriors".  log(e^a + e^b).  |a - b| is +inf when one operand is -inf and NaN when
+// both are: either way the larger operand is the answer, and no NaN leaves.  Scores are finite or -inf (the host
+// rejected +inf and NaN), so +inf never enters.
+__device__ __forceinline__ double xsp_lse2(double a, double b) {
+  const double m = fmax(a, b), d = fabs(a - b);
+  if (!(d < INFINITY)) return m;
+  return m + log1p(exp(-d));
+}
+
+__global__ __launch_bounds__(kXsBlock) void k_xsp_fill(double *q, int64_t cells) {
+  const int64_t step = (int64_t)gridDim.x * kXsBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kXsBlock + threadIdx.x; i < cells; i += step) q[i] = -INFINITY;
+}
+
+__global__ __launch_bounds__(kXsBlock) void k_xsp_scatter(double *q, const uint32_t *cell, const double *score, uint32_t n_fam) {
+  const uint32_t step = gridDim.x * kXsBlock;
+  for (uint32_t f = blockIdx.x * kXsBlock + threadIdx.x; f < n_fam; f += step) q[cell[f]] = score[f];
+}
+
+struct XspZetaArgs {
+  double *g;      // rows of 2^W cells; the grid covers whole rows
+  int32_t W, Lz;  // bits of a row's index; log2 of the tile
+  int32_t up;     // 0: subset sums, hi = lse2(hi, lo); 1: superset sums, lo = lse2(lo, hi)
+  XsTrip t;
+};
+
+// k_xs_zeta's tile and passes (the comment there) on a value alone, 8 bytes a cell.  A pass reads both cells of a pair
+// and writes one of them; pairs are disjoint, and the passes over the row's bits come in ascending order whatever the
+// tiling, so a cell sees the same operands in the same order under every tiling.
+__global__ __launch_bounds__(kXsBlock) void k_xsp_zeta(XspZetaArgs z) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double *val = reinterpret_cast<double *>(smem);
+  const uint32_t tid = threadIdx.x, cells = 1u << z.Lz, tile_bits = (uint32_t)(z.W - z.Lz);
+  const uint32_t v = blockIdx.x >> tile_bits, f = blockIdx.x & ((1u << tile_bits) - 1u);
+  const uint32_t c = (uint32_t)z.t.c, b0 = (uint32_t)z.t.b0, mid = b0 - c;
+  const uint32_t base = ((f & ((1u << mid) - 1u)) << c) | ((f >> mid) << (b0 + (uint32_t)z.t.hh));
+  double *g = z.g + ((size_t)v << z.W);
+  for (uint32_t i = tid; i < cells; i += kXsBlock) val[i] = g[base | ((i >> c) << b0) | (i & ((1u << c) - 1u))];
+  __syncthreads();
+  for (uint32_t j = (uint32_t)z.t.p0; j < (uint32_t)z.t.p1; ++j) {
+    for (uint32_t p = tid; p < cells >> 1; p += kXsBlock) {
+      const uint32_t lo = ((p >> j) << (j + 1u)) | (p & ((1u << j) - 1u)), hi = lo | (1u << j);
+      const double x = xsp_lse2(val[lo], val[hi]);
+      val[z.up ? lo : hi] = x;
+    }
+    __syncthreads();
+  }
+  for (uint32_t i = tid; i < cells; i += kXsBlock) g[base | ((i >> c) << b0) | (i & ((1u << c) - 1u))] = val[i];
+}
+
+struct XspPathArgs {
+  const double *alpha;
+  double *f, *b;
+  const uint32_t *hi_list;
+  const uint16_t *lo_list;
+  int32_t W, Ls, hi0;
+  uint32_t all;  // V
+  int32_t lo_off[kXsMaxTile + 2];
+};
+
+// k_xs_sink's ownership and layers; blockIdx.y = 0 walks F and 1 walks B, which differ in the alpha cell a candidate
+// reads: F takes alpha[v] at S \ v, B at V \ S.  The candidates come in ascending v under a running lse2 that starts
+// at -inf, so a cell does not depend on the tile.  F and B of the sets one smaller come from LDS for a low v and
+// from the table an earlier launch wrote for a high one.
+__global__ __launch_bounds__(kXsBlock) void k_xsp_paths(XspPathArgs s) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double *R = reinterpret_cast<double *>(smem);
+  const bool back = blockIdx.y != 0;
+  double *tab = back ? s.b : s.f;
+  const uint32_t tid = threadIdx.x, Ls = (uint32_t)s.Ls;
+  const uint32_t base = s.hi_list[s.hi0 + (int32_t)blockIdx.x] << Ls;
+  for (uint32_t layer = 0; layer <= Ls; ++layer) {
+    for (int32_t e = s.lo_off[layer] + (int32_t)tid; e < s.lo_off[layer + 1]; e += kXsBlock) {
+      const uint32_t l = s.lo_list[e], S = base | l;
+      if (S == 0) {
+        R[0] = 0.0;
+        continue;
+      }
+      double acc = -INFINITY;
+      for (uint32_t rem = S; rem; rem &= rem - 1u) {
+        const uint32_t v = (uint32_t)__ffs((int)rem) - 1u, prev = S ^ (1u << v);
+        const double before = v < Ls ? R[l ^ (1u << v)] : tab[prev];
+        acc = xsp_lse2(acc, s.alpha[((size_t)v << s.W) + xs_squeeze(back ? s.all ^ S : prev, v)] + before);
+      }
+      R[l] = acc;
+    }
+    __syncthreads();
+  }
+  for (uint32_t i = tid; i < (1u << Ls); i += kXsBlock) tab[base + i] = R[i];
+}
+
+// gamma of the rows v0 .. v0 + rows - 1: cell (r, T) is F[S] + B[V \ S \ v] for v = v0 + r and S = T with a clear bit
+// put in at v.  -inf + -inf is -inf; +inf does not occur.
+__global__ __launch_bounds__(kXsBlock) void k_xsp_gamma(const double *f, const double *b, double *g, int32_t W, int32_t v0,
+                                                       uint32_t all, int64_t cells) {
+  const int64_t step = (int64_t)gridDim.x * kXsBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kXsBlock + threadIdx.x; i < cells; i += step) {
+    const uint32_t v = (uint32_t)v0 + (uint32_t)(i >> W), T = (uint32_t)i & ((1u << W) - 1u);
+    const uint32_t S = (T & ((1u << v) - 1u)) | ((T >> v) << (v + 1u));
+    g[i] = f[S] + b[all ^ S ^ (1u << v)];
+  }
+}
+
+struct XspEdgeArgs {
+  const double *g, *f, *b;  // Gamma of the rows v0 ..; F and B
+  const uint32_t *cell, *mask;
+  const double *score;
+  double *out;  // edge_post [n][n], mass [n], log_z [2]
+  int32_t *flag;
+  int32_t n, W, v0;
+  uint32_t off[PGM_XS_MAX_NODES + 1];  // where each node's families start
+};
+
+// Workgroup b: column v = v0 + b of edge_post and mass[v].  Work-item l adds the terms of v's families l, l + 256, ...
+// into one sum per possible parent and one for the mass (a family adds +0.0 to the parents it does not hold, which
+// changes nothing); the indices are compile-time constants, so the 25 sums stay in registers.  A butterfly adds the
+// 64 lanes of a wave, then the four wave totals are added in wave order: one fixed order, no atomic.
+__global__ __launch_bounds__(kXsBlock) void k_xsp_edges(XspEdgeArgs e) {
+  constexpr int kSums = PGM_XS_MAX_NODES + 1;
+  __shared__ double part[kXsBlock / 64][kSums];
+  const uint32_t tid = threadIdx.x, v = (uint32_t)e.v0 + blockIdx.x, all = (1u << e.n) - 1u;
+  const double *g = e.g + ((size_t)blockIdx.x << e.W);
+  const double log_z = e.f[all];
+  double acc[kSums];
+#pragma unroll
+  for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
+  for (uint32_t i = e.off[v] + tid; i < e.off[v + 1]; i += kXsBlock) {
+    const uint32_t m = e.mask[i];
+    const double term = exp(e.score[i] + g[e.cell[i] - (v << e.W)] - log_z);
+#pragma unroll
+    for (int u = 0; u < PGM_XS_MAX_NODES; ++u) acc[u] += (m >> u & 1u) ? term : 0.0;
+    acc[PGM_XS_MAX_NODES] += term;
+  }
+#pragma unroll
+  for (int k = 0; k < kSums; ++k)
+    for (int o = 32; o; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
+  if ((tid & 63u) == 0) {
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) part[tid >> 6][k] = acc[k];
+  }
+  __syncthreads();
+  if (tid < (uint32_t)kSums) {
+    double t = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+    if (log_z == -INFINITY) t = NAN;  // no order admits a DAG
+    if (tid < (uint32_t)e.n) e.out[tid * (uint32_t)e.n + v] = t;
+    if (tid == PGM_XS_MAX_NODES) e.out[e.n * e.n + (int32_t)v] = t;
+  }
+  if (v == 0 && tid == 0) {
+    e.out[e.n * e.n + e.n] = log_z, e.out[e.n * e.n + e.n + 1] = e.b[all];
+    if (log_z == -INFINITY) *e.flag = 1;
+  }
+}
+
+// Everything a posterior puts on the stream, in order; nothing here waits (xs_enqueue's rule).  `fam` is the call's
+// device allocation of 16 bytes a family; `got` receives the outputs as k_xsp_edges lays them out.
+static int xsp_enqueue(XsHandle *h, XspEdgeArgs e, char *fam, const std::vector<uint32_t> &cell,
+                       const std::vector<uint32_t> &mask, const std::vector<double> &score, double *values, double *got,
+                       void *stream) {
+  const XsPlan &p = h->p;
+  const size_t m = cell.size();
+  const uint32_t all = (uint32_t)(p.r_cells - 1);
+  auto blocks_for = [](int64_t items) { return (unsigned)std::min<int64_t>((items + kXsBlock - 1) / kXsBlock, 65536); };
+  if (const int st = flag_reset(h->dev, stream)) return st;
+  if (const int st = xs_mark(h, 0, stream)) return st;
+
+  double *d_score = reinterpret_cast<double *>(fam);
+  uint32_t *d_cell = reinterpret_cast<uint32_t *>(fam + 8 * m), *d_mask = d_cell + m;
+  hipLaunchKernelGGL(k_xsp_fill, dim3(blocks_for(p.q_cells)), dim3(kXsBlock), 0, S(stream), h->d_q, p.q_cells);
+  HIP_TRY(hipGetLastError());
+  if (m) {
+    HIP_TRY(hipMemcpyAsync(d_score, score.data(), 8 * m, hipMemcpyHostToDevice, S(stream)));
+    HIP_TRY(hipMemcpyAsync(d_cell, cell.data(), 4 * m, hipMemcpyHostToDevice, S(stream)));
+    HIP_TRY(hipMemcpyAsync(d_mask, mask.data(), 4 * m, hipMemcpyHostToDevice, S(stream)));
+    hipLaunchKernelGGL(k_xsp_scatter, dim3(blocks_for((int64_t)m)), dim3(kXsBlock), 0, S(stream), h->d_q, d_cell, d_score, (uint32_t)m);
+    HIP_TRY(hipGetLastError());
+  }
+  if (const int st = xs_mark(h, 1, stream)) return st;
+
+  // alpha: the subset sums of every node's row
+  const size_t lds = (size_t)xs_post_lds(p.Lz);
+  for (const XsTrip &t : p.trips) {
+    XspZetaArgs z = {h->d_q, p.W, p.Lz, 0, t};
+    hipLaunchKernelGGL(k_xsp_zeta, dim3((unsigned)(p.q_cells >> p.Lz)), dim3(kXsBlock), lds, S(stream), z);
+    HIP_TRY(hipGetLastError());
+  }
+  if (const int st = xs_mark(h, 2, stream)) return st;
+
+  // F and B, by the popcount of the high part
+  XspPathArgs s = {};
+  s.alpha = h->d_q, s.f = h->d_r, s.b = h->d_b, s.hi_list = h->d_hi_list, s.lo_list = h->d_lo_list;
+  s.W = p.W, s.Ls = p.Ls, s.all = all;
+  std::copy(p.lo_off, p.lo_off + kXsMaxTile + 2, s.lo_off);
+  for (int32_t c = 0; c + 1 < (int32_t)p.hi_off.size(); ++c) {
+    s.hi0 = p.hi_off[(size_t)c];
+    const unsigned blocks = (unsigned)(p.hi_off[(size_t)c + 1] - s.hi0);
+    hipLaunchKernelGGL(k_xsp_paths, dim3(blocks, 2), dim3(kXsBlock), (size_t)xs_post_lds(p.Ls), S(stream), s);
+    HIP_TRY(hipGetLastError());
+  }
+  if (const int st = xs_mark(h, 3, stream)) return st;
+
+  // gamma, its superset sums and the edge sums, post_rows rows at a time through the one workspace
+  e.g = h->d_g, e.f = h->d_r, e.b = h->d_b, e.cell = d_cell, e.mask = d_mask, e.score = d_score, e.out = h->d_post;
+  e.flag = h->dev.flag(), e.n = p.n, e.W = p.W;
+  for (int32_t v0 = 0; v0 < p.n; v0 += p.post_rows) {
+    const int32_t rows = std::min(p.post_rows, p.n - v0);
+    const int64_t cells = (int64_t)rows << p.W;
+    hipLaunchKernelGGL(k_xsp_gamma, dim3(blocks_for(cells)), dim3(kXsBlock), 0, S(stream), h->d_r, h->d_b, h->d_g, p.W, v0, all, cells);
+    HIP_TRY(hipGetLastError());
+    for (const XsTrip &t : p.trips) {
+      XspZetaArgs z = {h->d_g, p.W, p.Lz, 1, t};
+      hipLaunchKernelGGL(k_xsp_zeta, dim3((unsigned)(cells >> p.Lz)), dim3(kXsBlock), lds, S(stream), z);
+      HIP_TRY(hipGetLastError());
+    }
+    e.v0 = v0;
+    hipLaunchKernelGGL(k_xsp_edges, dim3((unsigned)rows), dim3(kXsBlock), 0, S(stream), e);
+    HIP_TRY(hipGetLastError());
+  }
+  if (const int st = xs_mark(h, 4, stream)) return st;
+
+  if (values) {
+    HIP_TRY(hipMemcpyAsync(values, h->d_q, 8 * (size_t)p.q_cells, hipMemcpyDeviceToDevice, S(stream)));
+    HIP_TRY(hipMemcpyAsync(values + p.q_cells, h->d_r, 8 * (size_t)p.r_cells, hipMemcpyDeviceToDevice, S(stream)));
+    HIP_TRY(hipMemcpyAsync(values + p.q_cells + p.r_cells, h->d_b, 8 * (size_t)p.r_cells, hipMemcpyDeviceToDevice, S(stream)));
+  }
+  HIP_TRY(hipMemcpyAsync(got, h->d_post, 8 * (size_t)(p.n * p.n + p.n + 2), hipMemcpyDeviceToHost, S(stream)));
+  return PGM_OK;
+}
+
 extern "C" {
 
 int pgm_xs_destroy(void *handle) {
@@ -256,14 +497,14 @@ int pgm_xs_run(void *handle, const int32_t *fam_node, const uint32_t *fam_mask, 
   XsHandle *h = static_cast<XsHandle *>(handle);
   std::vector<uint32_t> cell, mask;
   std::vector<double> score;
-  int st = xs_run_check(h, fam_node, fam_mask, fam_score, n_fam, out, cell, mask, score);
+  int st = xs_run_check("xs_run", h, fam_node, fam_mask, fam_score, n_fam, out != nullptr, cell, mask, score);
   if (st != PGM_OK) return st;
   if ((values && (uintptr_t)values % 8) || (winners && (uintptr_t)winners % 4))
     return pgmi_fail(PGM_EINVAL, "xs_run: a table pointer is misaligned");
-  if ((st = xs_use(h)) != PGM_OK || (st = xs_events(h)) != PGM_OK) return st;
+  if ((st = xs_use(h, false)) != PGM_OK || (st = xs_events(h)) != PGM_OK) return st;
   XsRecord rec;
   int32_t bits = 0;
-  h->timed = false;
+  h->timed = 0;
   st = xs_enqueue(h, cell, mask, score, values, winners, &rec, stream);
   if (st == PGM_OK) st = flag_read(h->dev, stream, &bits);  // synchronises the stream
   if (st != PGM_OK) {
@@ -275,10 +516,49 @@ int pgm_xs_run(void *handle, const int32_t *fam_node, const uint32_t *fam_mask, 
     HIP_TRY(hipEventElapsedTime(&ms, static_cast<hipEvent_t>(h->ev[i]), static_cast<hipEvent_t>(h->ev[i + 1])));
     h->phase_ms[i] = ms;
   }
-  h->timed = true;
+  h->timed = PGM_XS_PHASES;
   out->score = rec.score, out->infeasible = bits != 0, out->n = h->p.n;
   memcpy(out->parents, rec.parents, sizeof rec.parents);
   memcpy(out->order, rec.order, sizeof rec.order);
+  return PGM_OK;
+}
+
+int pgm_xs_posterior(void *handle, const int32_t *fam_node, const uint32_t *fam_mask, const double *fam_score,
+                     int64_t n_fam, double *edge_post, double *log_z, double *mass, int32_t *infeasible, double *values,
+                     void *stream) {
+  XsHandle *h = static_cast<XsHandle *>(handle);
+  std::vector<uint32_t> cell, mask;
+  std::vector<double> score;
+  int st = xs_run_check("xs_posterior", h, fam_node, fam_mask, fam_score, n_fam, edge_post && log_z && mass && infeasible,
+                        cell, mask, score);
+  if (st != PGM_OK) return st;
+  if (values && (uintptr_t)values % 8) return pgmi_fail(PGM_EINVAL, "xs_posterior: the table pointer is misaligned");
+  const XsPlan &p = h->p;
+  XspEdgeArgs e = {};
+  xs_by_node(p, cell, mask, score, e.off);
+  if ((st = xs_use(h, true)) != PGM_OK || (st = xs_events(h)) != PGM_OK) return st;
+  // the families of this call: the scores, then the cells, then the masks, in one allocation
+  const size_t m = cell.size();
+  char *fam = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&fam), 16 * std::max<size_t>(m, 1)));
+  std::vector<double> got((size_t)(p.n * p.n + p.n + 2));
+  int32_t bits = 0;
+  h->timed = 0;
+  st = xsp_enqueue(h, e, fam, cell, mask, score, values, got.data(), stream);
+  if (st == PGM_OK) st = flag_read(h->dev, stream, &bits);  // synchronises the stream
+  if (st != PGM_OK) (void)hipStreamSynchronize(S(stream));  // what was enqueued reads the vectors above and writes got
+  (void)hipFree(fam);
+  if (st != PGM_OK) return st;
+  for (int i = 0; i < PGM_XS_POST_PHASES; ++i) {
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, static_cast<hipEvent_t>(h->ev[i]), static_cast<hipEvent_t>(h->ev[i + 1])));
+    h->phase_ms[i] = ms;
+  }
+  h->timed = PGM_XS_POST_PHASES;
+  std::copy(got.begin(), got.begin() + p.n * p.n, edge_post);
+  std::copy(got.begin() + p.n * p.n, got.end() - 2, mass);
+  log_z[0] = got[got.size() - 2], log_z[1] = got[got.size() - 1];
+  *infeasible = bits != 0;
   return PGM_OK;
 }
 }

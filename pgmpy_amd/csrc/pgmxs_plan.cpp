@@ -31,6 +31,7 @@ int xs_plan_build(int32_t n, int32_t L, int32_t h, XsPlan &out) {
   p.n = n, p.W = n - 1, p.L = L, p.h = h;
   p.Lz = std::min(L, p.W), p.Ls = std::min(L, n);
   p.q_cells = (int64_t)n << p.W, p.r_cells = (int64_t)1 << n;
+  p.post_rows = std::min(n, std::max(1, kXsPostCells >> p.W));
   if (p.W > 0) p.trips.push_back(XsTrip{p.Lz, p.Lz, 0, 0, p.Lz});
   for (int32_t b0 = p.Lz; b0 < p.W; b0 += h) {
     const int32_t hh = std::min(h, p.W - b0);
@@ -43,15 +44,15 @@ int xs_plan_build(int32_t n, int32_t L, int32_t h, XsPlan &out) {
   return PGM_OK;
 }
 
-int xs_run_check(const XsHandle *h, const int32_t *fam_node, const uint32_t *fam_mask, const double *fam_score,
-                 int64_t n_fam, const pgm_xs_result_t *out, std::vector<uint32_t> &cell, std::vector<uint32_t> &mask,
-                 std::vector<double> &score) {
-  if (!h) return pgmi_fail(PGM_EINVAL, "xs_run: null handle");
-  if (!out) return pgmi_fail(PGM_EINVAL, "xs_run: null result");
+int xs_run_check(const char *who, const XsHandle *h, const int32_t *fam_node, const uint32_t *fam_mask,
+                 const double *fam_score, int64_t n_fam, bool out, std::vector<uint32_t> &cell,
+                 std::vector<uint32_t> &mask, std::vector<double> &score) {
+  if (!h) return pgmi_failf(PGM_EINVAL, "%s: null handle", who);
+  if (!out) return pgmi_failf(PGM_EINVAL, "%s: null result", who);
   if (n_fam < 0 || (n_fam > 0 && (!fam_node || !fam_mask || !fam_score)))
-    return pgmi_fail(PGM_EINVAL, "xs_run: null family arrays / a negative count");
+    return pgmi_failf(PGM_EINVAL, "%s: null family arrays / a negative count", who);
   const XsPlan &p = h->p;
-  if (n_fam > p.q_cells) return pgmi_failf(PGM_EINVAL, "xs_run: %lld families, more than there are (node, parent set) pairs", (long long)n_fam);
+  if (n_fam > p.q_cells) return pgmi_failf(PGM_EINVAL, "%s: %lld families, more than there are (node, parent set) pairs", who, (long long)n_fam);
   const uint32_t all = (1u << p.n) - 1;
   std::vector<uint32_t> seen((size_t)n_fam);
   cell.clear(), mask.clear(), score.clear();
@@ -59,11 +60,11 @@ int xs_run_check(const XsHandle *h, const int32_t *fam_node, const uint32_t *fam
     const int32_t v = fam_node[f];
     const uint32_t P = fam_mask[f];
     const double s = fam_score[f];
-    if (v < 0 || v >= p.n) return pgmi_failf(PGM_EINVAL, "xs_run: family %lld: node %d of %d", (long long)f, v, p.n);
-    if (P & ~all) return pgmi_failf(PGM_EINVAL, "xs_run: family %lld: parent mask 0x%x has a bit at or above %d", (long long)f, P, p.n);
-    if (P >> v & 1) return pgmi_failf(PGM_EINVAL, "xs_run: family %lld: node %d is among its own parents", (long long)f, v);
+    if (v < 0 || v >= p.n) return pgmi_failf(PGM_EINVAL, "%s: family %lld: node %d of %d", who, (long long)f, v, p.n);
+    if (P & ~all) return pgmi_failf(PGM_EINVAL, "%s: family %lld: parent mask 0x%x has a bit at or above %d", who, (long long)f, P, p.n);
+    if (P >> v & 1) return pgmi_failf(PGM_EINVAL, "%s: family %lld: node %d is among its own parents", who, (long long)f, v);
     if (std::isnan(s) || (std::isinf(s) && s > 0))
-      return pgmi_failf(PGM_EINVAL, "xs_run: family %lld: score %g (finite or -inf)", (long long)f, s);
+      return pgmi_failf(PGM_EINVAL, "%s: family %lld: score %g (finite or -inf)", who, (long long)f, s);
     const uint32_t T = (P & ((1u << v) - 1)) | ((P >> (v + 1)) << v);
     const uint32_t c = ((uint32_t)v << p.W) + T;
     seen[(size_t)f] = c;
@@ -74,10 +75,23 @@ int xs_run_check(const XsHandle *h, const int32_t *fam_node, const uint32_t *fam
   const auto dup = std::adjacent_find(seen.begin(), seen.end());
   if (dup != seen.end()) {
     const uint32_t v = *dup >> p.W, T = *dup & ((1u << p.W) - 1);
-    return pgmi_failf(PGM_EINVAL, "xs_run: node %u is given the parent mask 0x%x twice", v,
+    return pgmi_failf(PGM_EINVAL, "%s: node %u is given the parent mask 0x%x twice", who, v,
                       (T & ((1u << v) - 1)) | ((T >> v) << (v + 1)));
   }
   return PGM_OK;
+}
+
+void xs_by_node(const XsPlan &p, std::vector<uint32_t> &cell, std::vector<uint32_t> &mask, std::vector<double> &score,
+                uint32_t *off) {
+  std::vector<uint32_t> at(cell.size());
+  for (size_t i = 0; i < at.size(); ++i) at[i] = (uint32_t)i;
+  std::sort(at.begin(), at.end(), [&](uint32_t x, uint32_t y) { return cell[x] < cell[y]; });  // no two cells are equal
+  std::vector<uint32_t> c(at.size()), m(at.size());
+  std::vector<double> s(at.size());
+  for (size_t i = 0; i < at.size(); ++i) c[i] = cell[at[i]], m[i] = mask[at[i]], s[i] = score[at[i]];
+  cell.swap(c), mask.swap(m), score.swap(s);
+  for (int32_t v = 0; v <= p.n; ++v)
+    off[v] = (uint32_t)(std::lower_bound(cell.begin(), cell.end(), (uint32_t)v << p.W) - cell.begin());
 }
 
 extern "C" {
@@ -104,7 +118,7 @@ int pgm_xs_phase_ms(void *handle, double *ms) {
   if (!handle || !ms) return pgmi_fail(PGM_EINVAL, "xs_phase_ms: null handle / ms");
   const XsHandle *h = static_cast<const XsHandle *>(handle);
   if (!h->timed) return pgmi_fail(PGM_EINVAL, "xs_phase_ms: the handle has no completed run");
-  std::copy(h->phase_ms, h->phase_ms + PGM_XS_PHASES, ms);
+  std::copy(h->phase_ms, h->phase_ms + h->timed, ms);
   return PGM_OK;
 }
 }

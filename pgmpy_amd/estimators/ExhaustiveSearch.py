@@ -5,7 +5,8 @@ scores, so the same maximum comes from the dynamic programme of Silander and Myl
 best parent set of every node within every candidate set, then the best sink of every set, then a walk down from the
 full set (include/pgmhip.h "Exact structure search").  `estimate` enumerates the families on the host, scores them
 with the scorer's batched `local_scores` and runs the programme on the device (pgm_xs_run): n * 2^(n-1) table cells,
-up to 24 variables.
+up to 24 variables.  `edge_posteriors` takes the same families through the same lattice with a log-sum-exp in place
+of the maximum (pgm_xs_posterior) and returns the exact posterior probability of every edge.
 
 Deviations: `estimate` takes `max_indegree` and `expert_knowledge` (required and forbidden edges), which
 the reference does not have; among DAGs of equal score the one the recurrence's tie rules pick is returned (fewer
@@ -65,6 +66,7 @@ class ExhaustiveSearch(BaseEstimator):
             _, self.scoring_method = get_scoring_method(scoring_method, self.data, use_cache)
         self.best_score = None  # R[V] of the last estimate()
         self.n_families = None  # families it scored
+        self.log_marginal = None  # F[V] of the last edge_posteriors()
         self._cache = {}
 
     def _nodes(self):
@@ -85,13 +87,9 @@ class ExhaustiveSearch(BaseEstimator):
         arc = self.scoring_method.structure_prior_ratio("+") if arc_prior else 0
         return [self._cache[f] + bin(f[1]).count("1") * arc for f in families]
 
-    def estimate(self, max_indegree=None, expert_knowledge=None, show_progress=True):
-        """A CPD-less DiscreteBayesianNetwork of the highest score over all the data's variables, among the DAGs
-        whose nodes have at most `max_indegree` parents and that hold every required and no forbidden edge.
-        `show_progress` is accepted and ignored."""
-        from ..models import DiscreteBayesianNetwork
-        from ._xs import XsPlan
-
+    def _scored_families(self, max_indegree, expert_knowledge):
+        """(nodes, families, scores) of `estimate` and `edge_posteriors`: their checks, the families that
+        `max_indegree` and the required and forbidden edges leave, and their scores with the per-arc prior."""
         nodes = self._nodes()
         n = len(nodes)
         if n > N.XS_MAX_NODES:
@@ -110,7 +108,17 @@ class ExhaustiveSearch(BaseEstimator):
         index = {v: i for i, v in enumerate(nodes)}
         as_index = lambda edges: [(index[u], index[v]) for u, v in edges]
         families = enumerate_families(n, max_indegree, as_index(forbidden), as_index(required))
-        scores = self._scores(nodes, families)
+        return nodes, families, self._scores(nodes, families)
+
+    def estimate(self, max_indegree=None, expert_knowledge=None, show_progress=True):
+        """A CPD-less DiscreteBayesianNetwork of the highest score over all the data's variables, among the DAGs
+        whose nodes have at most `max_indegree` parents and that hold every required and no forbidden edge.
+        `show_progress` is accepted and ignored."""
+        from ..models import DiscreteBayesianNetwork
+        from ._xs import XsPlan
+
+        nodes, families, scores = self._scored_families(max_indegree, expert_knowledge)
+        n = len(nodes)
         res = XsPlan(n).run([v for v, _ in families], [m for _, m in families], scores)
         self.n_families, self.best_score = len(families), res["score"]
         if res["infeasible"]:
@@ -119,6 +127,29 @@ class ExhaustiveSearch(BaseEstimator):
         model.add_nodes_from(nodes)
         model.add_edges_from((nodes[u], nodes[v]) for v, mask in enumerate(res["parents"]) for u in range(n) if mask >> u & 1)
         return model
+
+    def edge_posteriors(self, max_indegree=None, expert_knowledge=None):
+        """The exact posterior probability of every edge, as a DataFrame indexed by parent with the children as
+        columns, summed over all DAGs that `estimate` would search (pgm_xs_posterior: the same lattice with a
+        log-sum-exp for the maximum, after Koivisto and Sood).  Sets `log_marginal`, the log of the data's marginal
+        likelihood summed over orders and DAGs, and `n_families`.  The diagonal and every forbidden edge are exactly
+        0; a required edge is 1 up to rounding.
+
+        The prior is order-modular: uniform over the linear orders of the variables, times whatever prior the family
+        scores carry.  A DAG consistent with more orders therefore weighs more than under a uniform prior over DAGs;
+        that is the price of an exact sum and is not corrected.  The numbers are posteriors only when a family's score
+        is a log marginal likelihood plus a log prior (K2, BDeu, BDs); any StructureScore is accepted, and BIC or AIC
+        give the approximation that their penalty is.  The checks and errors are `estimate`'s."""
+        import pandas as pd
+
+        from ._xs import XsPlan
+
+        nodes, families, scores = self._scored_families(max_indegree, expert_knowledge)
+        res = XsPlan(len(nodes)).posterior([v for v, _ in families], [m for _, m in families], scores)
+        self.n_families, self.log_marginal = len(families), float(res["log_z"][0])
+        if res["infeasible"]:
+            raise ValueError("ExhaustiveSearch: no DAG meets max_indegree and the required edges")
+        return pd.DataFrame(res["edge_post"], index=nodes, columns=nodes)
 
     # ------------------------------------------------------------------ every DAG, on the host (small n)
     def all_dags(self, nodes=None):

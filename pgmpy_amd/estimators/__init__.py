@@ -37,6 +37,7 @@ calibration of the entropic mirror descent runs in one launch, one workgroup per
 Exact search: ExhaustiveSearch returns the highest-scoring DAG over up to 24 variables.  The families are scored in
 batches by any StructureScore; the dynamic programme over the subset lattice (best parents by a max-zeta transform
 through LDS tiles, best sinks by popcount layers, a read-back walk) runs on the device (pgm_xs_run).
+ExhaustiveSearch.edge_posteriors runs the same lattice in log space for the exact posterior of every edge (pgm_xs_posterior).
 """
 from .base import BaseEstimator, MarginalEstimator, ParameterEstimator
 from .MLE import MaximumLikelihoodEstimator

@@ -9,7 +9,10 @@ the host checks, the staging of the families, the fill, scatter, zeta, sink and 
 of the record, on a host clock around the call (it ends in a stream synchronise).  The tables are allocated by the
 first, untimed run.  Beside it the device time of each phase of the same runs (pgm_xs_phase_ms: HIP events around the
 fill and scatter, the zeta launches, the sink launches; the rest of a run is host work).  At the first size the numpy restatement of the recurrence (tests/xs_cases.py recurrence) runs on
-the same families in the same process, and the device result must equal it.  Real: BIC on the first 16 columns of rows
+the same families in the same process, and the device result must equal it.  Then the edge posteriors of the same
+families on the same handle (pgm_xs_posterior), on the same clocks: the whole call, and its four phases (fill and
+scatter; the alpha passes; F and B; gamma, its superset sums and the edge sums); every mass must be 1 and F[V] = B[V]
+to 1e-9, and at the first size the matrix must agree with tests/xsp_cases.py recurrence in float64.  Real: BIC on the first 16 columns of rows
 forward-sampled from alarm, ExhaustiveSearch.estimate(max_indegree) split into family scoring (local_scores) and the
 programme; HillClimbSearch's score on the same data beside it.  `warmup` untimed runs, the median and minimum of `steps`.
 Not measured: single launches within a phase (a kernel trace would give them), hardware counters, the tilings other
@@ -60,6 +63,7 @@ def main():
     from pgmpy_amd.utils import get_example_model
     from pgmpy_amd.utils.sampling import forward_sample_codes
     from tests.xs_cases import recurrence
+    from tests.xsp_cases import recurrence as posterior_recurrence
 
     assert torch.cuda.is_available(), "xs_bench needs a HIP device"
     _native.lib()
@@ -96,6 +100,25 @@ def main():
             want = recurrence(n, nodes, masks, scores)
             row["numpy_restatement_ms"] = (time.perf_counter() - t0) * 1e3
             assert got["score"] == want["score"] and got["parents"] == want["parents"], "device and restatement differ"
+        # the edge posteriors of the same families on the same handle (pgm_xs_posterior), timed the same way
+        phases = []
+
+        def post_step():
+            plan.posterior(nodes, masks, scores)
+            phases.append(plan.phase_ms())
+
+        med, lo = clock_ms(post_step, args.steps, args.warmup)
+        post = plan.posterior(nodes, masks, scores)
+        z = abs(post["log_z"][0])
+        assert not post["infeasible"] and np.abs(post["mass"] - 1).max() < 1e-9 and abs(post["log_z"][0] - post["log_z"][1]) < 1e-9 * z
+        row["posterior"] = {"run_ms_median": med, "run_ms_min": lo, "log_z": float(post["log_z"][0]),
+                            "lse2_evaluations": (n - 1) * cells + n * (1 << n),
+                            **{f"{k}_ms_median": float(np.median([p[k] for p in phases[args.warmup:]])) for k in phases[0]}}
+        if k == 0:
+            t0 = time.perf_counter()
+            want = posterior_recurrence(n, (nodes, masks, scores))
+            row["posterior"]["numpy_restatement_ms"] = (time.perf_counter() - t0) * 1e3
+            assert np.abs(post["edge_post"] - want["edge_post"]).max() < 1e-9, "device and restatement differ"
         synthetic.append(row)
         del plan
 
